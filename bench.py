@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- tiles/s of one full DINO multi-crop training step (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config c3|c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config c3|c2] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the line.  --full adds what takes runs of its own: the roofline of the
+dominant kernel (a few more steps with per-launch timing) and the CPU oracle baseline.  --dump-outputs DIR writes what the last
+timed step left for its caller as DIR/<name>.npy (float32; fixed, seeded samples of the large arrays), so that two builds can be
+compared output for output on identical inputs.
 
 One process per GPU.  Under torchrun (RANK/LOCAL_RANK/WORLD_SIZE in the environment) this process IS one
 rank; started bare with --gpus N > 1 it is only a launcher: it touches no GPU, starts N copies of itself
@@ -63,6 +68,29 @@ def cpu_baseline(arch, n_local, warmup=2, steps=5):
     dt = time.time() - t0
     return {"value": round(B * steps / dt, 4), "unit": "tiles/s", "cores": cores, "kind": "port",
             "sample": f"{steps} oracle steps of B={B} tiles (2x224+{n_local}x96 crops, {arch}, K=65536) after {warmup} warm-up steps (BASELINE.md section 3 protocol)"}
+
+
+DUMP_SAMPLE = 3_000_000             # positions drawn from each large output (repeats dropped): at most 12 MB of float32 per array, 49 MB in all
+
+
+def dump_outputs(eng, out_dir):
+    """After the timed steps: the loss, the DINO centre, the student and teacher parameters (every parameter flattened in model
+    order, padding left out, so the sample does not depend on the arena layout) and the step's student / teacher logits."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(x, seed):
+        x = x.reshape(-1)
+        if x.numel() <= DUMP_SAMPLE:
+            return x
+        idx = torch.randint(0, x.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).unique()
+        return x[idx.to(x.device)]
+    a = eng.arena
+    flat = lambda buf: torch.cat([a.view(buf, n).reshape(-1) for n in a.specs])
+    outs = {"loss": eng.loss, "center": eng.center, "student_params": sample(flat(a.p), 1), "teacher_params": sample(flat(a.t), 1),
+            "student_logits": sample(eng.hb_s.logits, 2), "teacher_logits": sample(eng.hb_t.logits, 3)}
+    for name, t in outs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def launch_children(n: int, argv, child=None, timeout=None, poll_s: float = 0.2):
@@ -142,7 +170,10 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="tiles per GPU per step")
     ap.add_argument("--config", default="c3", choices=["c3", "c2"])
     ap.add_argument("--arch", default="vit_small")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure the dominant kernel's roofline (steps of their own with per-launch "
+                    "timing) and the CPU oracle baseline; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU oracle baseline out")
     ap.add_argument("--micro", type=int, default=1, help="micro-batches of --batch tiles per optimizer step (gradient accumulation: BASELINE "
                     "config 5 is --arch vit_base --batch 64 --micro 8 = 512 tiles per GPU and step); a parity-case run, not the headline line")
     ap.add_argument("--random-crops", action="store_true", help="cut random-resized crops on the device every step (gv_crop_resize) instead of "
@@ -255,9 +286,11 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t)
     loss = float(eng.loss)
-    # roofline of the dominant kernel: a few more steps of the same workload with per-launch timing on -- run by EVERY rank (the
-    # steps contain the data-parallel all-reduces), reported from rank 0
-    roof = roofline.dominant_kernel_roofline(lambda: on_main(lambda: eng.step(tiles)), steps=3, vit=eng.vit)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
+    # --full: roofline of the dominant kernel, a few more steps of the same workload with per-launch timing on -- run by EVERY rank
+    # (the steps contain the data-parallel all-reduces), reported from rank 0
+    roof = roofline.dominant_kernel_roofline(lambda: on_main(lambda: eng.step(tiles)), steps=3, vit=eng.vit) if args.full else None
 
     # FLOPs actually executed per tile: BASELINE.md's count prices every token of every block (what the reference's module + autograd
     # compute); with the CLS-only last block (engine.VitRunner.cls_last) the projection + MLP of that block skip the non-CLS rows --
@@ -287,7 +320,7 @@ def main():
             "final_loss": round(loss, 4),
         }
         out["roofline"] = roof
-        out["cpu_baseline"] = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(args.arch, n_local)
+        out["cpu_baseline"] = None if (not args.full or args.no_cpu_baseline or world > 1) else cpu_baseline(args.arch, n_local)
         print(json.dumps(out), flush=True)
     if world > 1 or force_dist:
         torch.distributed.destroy_process_group()

@@ -59,15 +59,14 @@ def test_loss_scaler_state_interchanges_with_torch_gradscaler():
     back.load_state_dict({k: out[k] for k in torch_state})          # and torch reads ours
 
 
-def test_struct_layout_matches_header():
+def test_struct_layout_matches_header(tmp_path):
     """sizeof of every args struct as the C compiler sees it == ctypes' view."""
     from gipvit import _lib
     structs = list(_lib.ENTRY_POINTS.values()) + [_lib.gv_linear_timing_row]
     names = sorted(s.__name__ for s in structs)
     src = '#include <stdio.h>\n#include "gipvit.h"\nint main(){' + "".join(
         f'printf("{n} %zu\\n", sizeof({n}));' for n in names) + "return 0;}"
-    exe = os.path.join(ROOT, "gpurun_out", "_sizeof_test")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    exe = str(tmp_path / "sizeof_test")
     r = subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src, text=True, capture_output=True)
     assert r.returncode == 0, r.stderr
     out = dict(l.split() for l in subprocess.run([exe], capture_output=True, text=True).stdout.splitlines())
@@ -493,6 +492,41 @@ def test_bench_launcher_spawns_ranks_with_torchrun_env(tmp_path):
                         f"bench.launch_children = lambda n, argv, **k: (0, 'LAUNCHED %d %s\\n' % (n, ' '.join(argv)))\n"
                         "bench.main()"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "LAUNCHED 2 --gpus 2 --steps 1" in r.stdout, (r.stdout, r.stderr)
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: float32 .npy files, the large arrays sampled at fixed seeded positions (the same in every
+    run), parameters taken in model order without the arena's padding, and the whole dump within 64 MB at the real sample size."""
+    import types
+    import numpy as np
+    from collections import OrderedDict
+    from gipvit import engine as E
+    sys.path.insert(0, ROOT)
+    import bench
+    assert 4 * 4 * bench.DUMP_SAMPLE + 4 * 65536 + 4 <= 64 << 20
+    specs = OrderedDict(("backbone." + k, v) for k, v in E.vit_param_specs("vit_tiny", 64, 0).items())
+    specs.update(("head." + k, v) for k, v in E.dino_head_specs(192, 256, hidden=64).items())
+    a = E.Arena(specs, "cpu", teacher=True)
+    total = 0
+    for n, shape in specs.items():                                     # parameter values = their position in model order
+        k = a.view(a.p, n).numel()
+        a.view(a.p, n).copy_(torch.arange(total, total + k, dtype=torch.float32).view(shape))
+        total += k
+    a.t.copy_(-a.p)
+    eng = types.SimpleNamespace(arena=a, loss=torch.tensor([1.5]), center=torch.linspace(0, 1, 256),
+                                hb_s=types.SimpleNamespace(logits=torch.randn(40, 256)), hb_t=types.SimpleNamespace(logits=torch.randn(8, 256)))
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 4096)
+    for d in ("a", "b"):
+        bench.dump_outputs(eng, str(tmp_path / d))
+    names = {"loss", "center", "student_params", "teacher_params", "student_logits", "teacher_logits"}
+    assert {f[:-4] for f in os.listdir(tmp_path / "a")} == names
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert all(v.dtype == np.float32 for v in got.values()) and all(np.array_equal(v, np.load(tmp_path / "b" / f"{n}.npy")) for n, v in got.items())
+    assert got["loss"].tolist() == [1.5] and np.array_equal(got["center"], eng.center.numpy())
+    sp = got["student_params"]
+    assert 3500 < sp.size <= 4096 and np.all(np.diff(sp) > 0) and sp[-1] < total and np.array_equal(got["teacher_params"], -sp)
+    assert got["student_logits"].size <= 4096 and np.isin(got["student_logits"], eng.hb_s.logits.numpy()).all()
+    assert np.array_equal(got["teacher_logits"], eng.hb_t.logits.numpy().ravel())          # small enough to be written whole
 
 
 def test_lr_schedule_and_checkpoint_saver(tmp_path):
