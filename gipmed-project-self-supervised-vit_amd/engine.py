@@ -21,6 +21,7 @@ goes to one side stream ordered by events.
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import os
 from collections import OrderedDict
@@ -58,6 +59,68 @@ def _empty(shape, dt, device):
 
 def _round_up(n: int, m: int) -> int:
     return (n + m - 1) // m * m
+
+
+@dataclasses.dataclass(frozen=True)
+class EngineSwitches:
+    """The engine's runtime switches, read from the environment once, when a runner / engine is built: field ``x`` is
+    ``GIPVIT_X`` (a boolean is off at "0").  Every default is the fast path; the others exist for A/B runs (README)."""
+    fused_ln: bool = True          # full-row Linear + LayerNorm kernels (csrc/panel.hip) at the ViT-S width
+    group_dw: bool = True          # a block's four weight gradients as one launch
+    cls_only_last: bool = True     # the last block's projection / MLP on the CLS rows only
+    fused_mlp: bool = True         # forward-only passes: the MLP as one launch
+    cls_qlimit: bool = True        # under cls_only_last, that block's attention for the CLS queries only
+    varlen_attn: bool = True       # the crop lengths of a multi-crop pass in one attention launch
+    dw_stream: bool = True         # work that feeds nothing downstream on a side stream
+    side_priority: int = 0         # that stream's priority
+    teacher_side: bool = True      # the teacher's forward on the side stream, beside the student's
+    bucket_mb: int = 25            # size of the gradient all-reduce ranges (dist.reduction_plan)
+
+    @classmethod
+    def from_env(cls) -> "EngineSwitches":
+        kw = {}
+        for f in dataclasses.fields(cls):
+            v = os.environ.get("GIPVIT_" + f.name.upper())
+            if v is not None:
+                kw[f.name] = v != "0" if isinstance(f.default, bool) else int(v)
+        return cls(**kw)
+
+
+class SideStream:
+    """Work that feeds nothing downstream, queued on a side stream beside the main stream (the caller's current stream when
+    the helper is made) and ordered by events.  ``run(fn)``: the side stream waits for what main has
+    queued so far, ``fn()`` is queued there and the event that marks its end is returned; ``join(ev)``: main waits for it
+    before it overwrites what ``fn`` still reads; ``then(fn)``: ``fn()`` behind the side stream's own work only (no events).
+    With no side stream ``fn`` runs inline and ``run`` returns None.  Events come from ``pool``, a list its owner keeps
+    across steps, in the order they are asked for (a step asks for the same ones every time)."""
+
+    def __init__(self, side, pool: list):
+        self.main = torch.cuda.current_stream() if side is not None else None
+        self.side, self.pool, self.n = side, pool, 0
+
+    def _event(self):
+        if self.n == len(self.pool):
+            self.pool.append(torch.cuda.Event())
+        self.n += 1
+        return self.pool[self.n - 1]
+
+    def run(self, fn):
+        if self.side is None:
+            fn()
+            return None
+        e0 = self._event(); e0.record(self.main); self.side.wait_event(e0)
+        with torch.cuda.stream(self.side):
+            fn()
+            e1 = self._event(); e1.record(self.side)
+        return e1
+
+    def then(self, fn):
+        with torch.cuda.stream(self.side):      # (a no-op context without a side stream)
+            fn()
+
+    def join(self, ev):
+        if ev is not None:
+            self.main.wait_event(ev)
 
 
 # --------------------------------------------------------------------------- #
@@ -316,45 +379,47 @@ class VitGroup:
 
 
 class VitRunner:
-    def __init__(self, arch: str, img_size: int, device, fp32: bool = False):
+    def __init__(self, arch: str, img_size: int, device, fp32: bool = False, sw: Optional[EngineSwitches] = None):
+        """``sw``: the switches of the engine that owns this runner (read from the environment when not given)."""
         a = ARCHS[arch]
         self.arch, self.D, self.depth, self.H, self.img_size = arch, a["embed_dim"], a["depth"], a["num_heads"], img_size
         self.fp32 = fp32    # fp32 operand mode: one f32 kernel per op (no fused Linear + LayerNorm, no grouped dW)
         self.scale = 64 ** -0.5
+        self.sw = sw = EngineSwitches.from_env() if sw is None else sw
         # full-row Linear + LayerNorm kernels (csrc/panel.hip) exist for the ViT-S width; GIPVIT_FUSED_LN=0 keeps the
         # round-1 pair (128x128-tile GEMM + stand-alone LayerNorm pass) for A/B runs
-        self.fused = self.D == 384 and not fp32 and os.environ.get("GIPVIT_FUSED_LN", "1") != "0"
+        self.fused = self.D == 384 and not fp32 and sw.fused_ln
         # the four weight-gradient products of a block as ONE split-K launch (gv_linear_dw_group): a quarter of the slab
         # traffic and four times longer k-loops than four launches (ViT-S: 165 us per block at 950 TFLOP/s against
         # 4 x (51 + 7) us).  GIPVIT_GROUP_DW=0 keeps one launch per product for A/B runs.
-        self.group_dw = not fp32 and os.environ.get("GIPVIT_GROUP_DW", "1") != "0"
+        self.group_dw = not fp32 and sw.group_dw
         # Only the CLS row of the last block's output feeds the head (vit.pyc@L248-253: forward returns x[:, 0]), so that block's
         # attention projection, MLP and residual adds for the other tokens -- and their whole backward except the K / V path --
         # are dead values: the last block runs them on the n_img CLS rows only (same loss and gradients; ~5.7 % fewer FLOPs of a
         # ViT-S DINO step).  GIPVIT_CLS_ONLY_LAST=0 computes every token of every block, as the reference's module + autograd do.
-        self.cls_last = os.environ.get("GIPVIT_CLS_ONLY_LAST", "1") != "0"
+        self.cls_last = sw.cls_only_last
         # forward-only passes (teacher, inference) run the MLP as one launch; GIPVIT_FUSED_MLP=0 keeps fc1 / fc2 apart (A/B runs)
-        self.fused_mlp = os.environ.get("GIPVIT_FUSED_MLP", "1") != "0"
-        # the CLS-only tail of the last block (n_img rows): fused Linear + LayerNorm kernels, or the tiled GEMM + a LayerNorm pass
-        self.cls_tail_fused = os.environ.get("GIPVIT_CLS_TAIL_FUSED", "0") != "0"
+        self.fused_mlp = sw.fused_mlp
         self.partials = _empty((L.LN_PARTIAL_BLOCKS, 3, self.D), f32, device)
         self.partials_ring = [self.partials] + [_empty((L.LN_PARTIAL_BLOCKS, 3, self.D), f32, device) for _ in range(2)]
         self.cs_ws = _empty((64 * 4 * self.D,), f32, device)
         self.one = torch.ones(1, dtype=f32, device=device)
-        self.ws = _empty((L.lib.gv_linear_workspace_bytes() // 4,), f32, device)   # split-K slabs of the stream the weight gradients run on (the side stream when there is one)
-        self.ws_main = _empty((16 << 20) // 4, f32, device)                              # ... of the few-row products of the CLS-only tail queued on the other one
-        cuda = torch.device(device).type == "cuda"
+        # split-K slabs per stream: the weight gradients' (on the side stream, or inline when there is none) and those of the
+        # few-row products of the CLS-only tail queued on the main stream.  gv_linear picks its split count from the size.
+        self.ws_side = _empty((L.lib.gv_linear_workspace_bytes() // 4,), f32, device)
+        self.ws_main = _empty((16 << 20) // 4, f32, device)
         self.side = None
-        if cuda and os.environ.get("GIPVIT_DW_STREAM", "1") != "0":
-            prio = os.environ.get("GIPVIT_SIDE_PRIORITY")
-            self.side = torch.cuda.Stream(device, priority=int(prio)) if prio is not None else torch.cuda.Stream(device)
+        if torch.device(device).type == "cuda" and sw.dw_stream:
+            self.side = torch.cuda.Stream(device, priority=sw.side_priority)
         self._events: List[torch.cuda.Event] = []
 
     # ---- forward: tiles -> CLS features written into feats[row_off + seg.img0 ...]
-    def forward(self, W: Weights, G: VitGroup, tiles_u8, windows, mean, std, feats, row_off: int = 0, fill=None):
+    def forward(self, W: Weights, G: VitGroup, tiles_u8, windows, mean, std, feats, row_off: int = 0, fill=None, on_side: bool = False):
         """windows: one list of (y0, x0) crop origins per segment; tiles_u8: one NHWC u8 tensor for all
         segments, or one per segment (pre-cut crops: each with the single window (0, 0)).  ``fill``: per-tile normalised
-        fill boxes of the augmentation (gipvit.augment: Cutout after Normalize, MeanPixelRegularization), f32 [n_tiles, 8]."""
+        fill boxes of the augmentation (gipvit.augment: Cutout after Normalize, MeanPixelRegularization), f32 [n_tiles, 8].
+        ``on_side``: the call is queued on the side stream (the teacher beside the student): its split-K products take that
+        stream's scratch."""
         D, T, H = self.D, G.T, self.H
         E = L
         pos_full = W.f("pos_embed").view(-1, D)
@@ -390,8 +455,8 @@ class VitRunner:
                 ops.layernorm_fwd(xa, W.f(b + "norm1.weight"), W.f(b + "norm1.bias"), T, D, y=G.xn1[s], mean=st[0], rstd=st[1])
             ops.linear(G.xn1[s], W.w(b + "attn.qkv.weight"), G.qkv[s], T, 3 * D, D, epilogue=E.EPI_BIAS, bias=W.f(b + "attn.qkv.bias"))
             # the last block under the CLS-only tail: only the CLS query's attention output is used (row 0 of every image)
-            ql = 1 if (self._cls_tail(G) and i == self.depth - 1 and os.environ.get("GIPVIT_CLS_QLIMIT", "1") != "0") else 0
-            if len(G.segs) > 1 and os.environ.get("GIPVIT_VARLEN_ATTN", "1") != "0":
+            ql = 1 if (self._cls_tail(G) and i == self.depth - 1 and self.sw.cls_qlimit) else 0
+            if len(G.segs) > 1 and self.sw.varlen_attn:
                 # the crop lengths of a multi-crop pass in ONE call (gv_attention_fwd_varlen: the 37-token pairs fill the 197-token
                 # launch's half-empty last round); GIPVIT_VARLEN_ATTN=0 keeps one launch per segment for A/B runs
                 ops.attention_fwd_varlen(G.qkv[s], G.o[s], [(sg.n_img, sg.N, sg.lse[s]) for sg in G.segs], H, self.scale, q_limit=ql)
@@ -399,7 +464,7 @@ class VitRunner:
                 for sg in G.segs:
                     ops.attention_fwd(sg.rows(G.qkv[s]), sg.n_img, sg.N, H, self.scale, o=sg.rows(G.o[s]), lse=sg.lse[s], q_limit=ql)
             if self._cls_tail(G) and i == self.depth - 1:
-                self._last_block_tail_fwd(W, G, i, xa, fused and self.cls_tail_fused)
+                self._last_block_tail_fwd(W, G, i, xa, on_side)
                 break
             if fused:
                 ops.linear_ln_fwd(G.o[s], W.w(b + "attn.proj.weight"), xb, T, D, bias=W.f(b + "attn.proj.bias"), resid=xa,
@@ -455,30 +520,23 @@ class VitRunner:
         weight-gradient path and without --drop, whose backward this build restates for that case.)"""
         return self.cls_last and G.dropout is None and (not G.save or self.group_dw)
 
-    def _last_block_tail_fwd(self, W: Weights, G: VitGroup, i: int, xa: torch.Tensor, fused: bool):
+    def _last_block_tail_fwd(self, W: Weights, G: VitGroup, i: int, xa: torch.Tensor, on_side: bool):
         """x + proj(attention) -> norm2 -> MLP -> residual of block i for the CLS rows only (vit.pyc@L146-152 on the rows that
-        VisionTransformer.forward returns, L248-253): n_img rows through the same kernels the full blocks use."""
+        VisionTransformer.forward returns, L248-253): n_img rows through the tiled GEMM and a LayerNorm pass (a full-row kernel
+        streams a whole weight matrix per workgroup at this row count)."""
         G.alloc_cls()
         D, n, s, E, b = self.D, G.n_img, G.slot(i), L, f"blocks.{i}."
         rs_a, rs_m = (G.drop_img[i, 0], G.drop_img[i, 1]) if G.rs is not None else (None, None)       # per image = per CLS row
         G.gather_cls(G.o[s], G.c_o)
         G.gather_cls(xa, G.c_xa)
-        if fused:
-            ops.linear_ln_fwd(G.c_o, W.w(b + "attn.proj.weight"), G.c_xb, n, D, bias=W.f(b + "attn.proj.bias"), resid=G.c_xa,
-                              gamma=W.f(b + "norm2.weight"), beta=W.f(b + "norm2.bias"), y=G.c_xn2, mean=G.c_stats[0], rstd=G.c_stats[1], row_scale=rs_a)
-        else:
-            ops.linear(G.c_o, W.w(b + "attn.proj.weight"), G.c_xb, n, D, D, epilogue=E.EPI_BIAS | E.EPI_RESID,
-                       bias=W.f(b + "attn.proj.bias"), resid=G.c_xa, row_scale=rs_a)
-            ops.layernorm_fwd(G.c_xb, W.f(b + "norm2.weight"), W.f(b + "norm2.bias"), n, D, y=G.c_xn2, mean=G.c_stats[0], rstd=G.c_stats[1])
+        ops.linear(G.c_o, W.w(b + "attn.proj.weight"), G.c_xb, n, D, D, epilogue=E.EPI_BIAS | E.EPI_RESID,
+                   bias=W.f(b + "attn.proj.bias"), resid=G.c_xa, row_scale=rs_a)
+        ops.layernorm_fwd(G.c_xb, W.f(b + "norm2.weight"), W.f(b + "norm2.bias"), n, D, y=G.c_xn2, mean=G.c_stats[0], rstd=G.c_stats[1])
         ops.linear(G.c_xn2, W.w(b + "mlp.fc1.weight"), G.c_h, n, 4 * D, D, epilogue=E.EPI_BIAS | E.EPI_GELU | (E.EPI_SAVE_PRE if G.save else 0),
                    bias=W.f(b + "mlp.fc1.bias"), aux_out=G.c_hp if G.save else None)
-        if fused:
-            ops.linear_ln_fwd(G.c_h, W.w(b + "mlp.fc2.weight"), G.c_xc, n, 4 * D, bias=W.f(b + "mlp.fc2.bias"), resid=G.c_xb, row_scale=rs_m)
-        else:
-            # (a few hundred rows, a 4 D-deep reduction: gv_linear splits K when handed a scratch -- the one of the stream this pass is queued on)
-            on_side = self.side is not None and xa.is_cuda and torch.cuda.current_stream() == self.side
-            ops.linear(G.c_h, W.w(b + "mlp.fc2.weight"), G.c_xc, n, D, 4 * D, epilogue=E.EPI_BIAS | E.EPI_RESID,
-                       bias=W.f(b + "mlp.fc2.bias"), resid=G.c_xb, row_scale=rs_m, workspace=self.ws if on_side else self.ws_main)
+        # (a few hundred rows, a 4 D-deep reduction: gv_linear splits K when handed a scratch -- the one of the stream this pass is queued on)
+        ops.linear(G.c_h, W.w(b + "mlp.fc2.weight"), G.c_xc, n, D, 4 * D, epilogue=E.EPI_BIAS | E.EPI_RESID,
+                   bias=W.f(b + "mlp.fc2.bias"), resid=G.c_xb, row_scale=rs_m, workspace=self.ws_side if on_side else self.ws_main)
 
     def prepare_backward(self, G: VitGroup):
         """Zero the backward scratch that is accumulated into or only partly written: the residual gradient (the final norm's backward
@@ -535,94 +593,43 @@ class VitRunner:
         # The weight-gradient GEMMs are off the critical path (nothing in backward consumes dW):
         # they run on a side stream beside the dX chain, so their tiles fill the tail of every
         # main-stream kernel (a 345 x 3-tile GEMM occupies 2.02 rounds of the 512 workgroup slots).
-        # fork(): side waits for what main has enqueued; join(ev): main waits for a side event
-        # before it overwrites a buffer a dW product still reads (gb / dh / dqkv).
-        main = torch.cuda.current_stream() if xl.is_cuda else None
-        side = self.side if (main is not None and self.side is not None) else None
-        evs = self._events
-        n_ev = [0]
-
-        def new_event():
-            if n_ev[0] == len(evs):
-                evs.append(torch.cuda.Event())
-            n_ev[0] += 1
-            return evs[n_ev[0] - 1]
+        # join(ev): main waits for a side event before it overwrites a buffer a dW product still reads (gb / dh / dqkv).
+        sx = SideStream(self.side if xl.is_cuda else None, self._events)
+        join = sx.join
 
         def dw(A, Bm, Cg, M, N, colsum_a=None):
             """dW (+)= A^T Bm on the side stream once main's work so far is done; returns the event that marks its end."""
-            if side is None:
-                ops.linear(A, Bm, Cg, M, N, T, trans_a=True, trans_b=True, epilogue=ACC, colsum_a=colsum_a, workspace=self.ws)
-                return None
-            e0 = new_event(); e0.record(main); side.wait_event(e0)
-            with torch.cuda.stream(side):
-                ops.linear(A, Bm, Cg, M, N, T, trans_a=True, trans_b=True, epilogue=ACC, colsum_a=colsum_a, workspace=self.ws)
-                e1 = new_event(); e1.record(side)
-            return e1
-
-        def join(ev):
-            if ev is not None:
-                main.wait_event(ev)
+            return sx.run(lambda: ops.linear(A, Bm, Cg, M, N, T, trans_a=True, trans_b=True, epilogue=ACC, colsum_a=colsum_a,
+                                             workspace=self.ws_side))
 
         # LayerNorm backward leaves per-block column sums in a partials buffer; folding them into the gamma / beta /
         # bias gradients (ln_finalize) is parameter-gradient work too, so it also goes to the side stream.  Three
         # partials buffers rotate; one is rewritten only after the finalize that read it (three calls ago) has run.
-        ring, fin_ev, ring_i, last_side = self.partials_ring, [None, None, None], [0], [None]
+        ring, fin_ev, ring_i, last_fin = self.partials_ring, [None, None, None], 0, None
 
         def ln_bwd(dy, x, mean, rstd, gamma, gb, d0, d1, d2, dx_of=None, gb_scale=None, rows=None, g=None):
             """LayerNorm backward into the residual gradient.  ``dx_of = (dY, W, K)``: the dX product that produces ``dy``
             runs fused with it (gv_linear_ln_bwd) and ``dy`` never exists in HBM.  ``rows`` / ``g``: a row count and residual
-            gradient other than the group's T rows / G.g (the last block's CLS-only tail)."""
-            k = ring_i[0]
-            ring_i[0] = (k + 1) % 3
+            gradient other than the group's T rows / G.g (the last block's CLS-only tail: the unfused pair)."""
+            nonlocal ring_i, last_fin
+            k = ring_i
+            ring_i = (k + 1) % 3
             join(fin_ev[k])
             M_, g_ = (T if rows is None else rows), (G.g if g is None else g)
-            if dx_of is not None and fused_b and (rows is None or self.cls_tail_fused):
+            if dx_of is not None and fused_b and rows is None:
                 nblk = ops.linear_ln_bwd(dx_of[0], dx_of[1], x, mean, rstd, gamma, g_, gb, ring[k], M_, dx_of[2], gb_scale=gb_scale)
             else:
                 if dx_of is not None:
                     ops.linear(dx_of[0], dx_of[1], dy, M_, D, dx_of[2], trans_b=True, workspace=self.ws_main if rows is not None else None)
                 ops.layernorm_bwd(dy, x, mean, rstd, gamma, g_, gb, ring[k], M_, D, gb_scale=gb_scale)
                 nblk = L.LN_PARTIAL_BLOCKS
-            if side is None:
-                ops.ln_finalize(ring[k], nblk, D, d0, d1, d2)
-                return
-            e0 = new_event(); e0.record(main); side.wait_event(e0)
-            with torch.cuda.stream(side):
-                ops.ln_finalize(ring[k], nblk, D, d0, d1, d2)
-                e1 = new_event(); e1.record(side)
-            fin_ev[k] = last_side[0] = e1
-
-        def dw_group(problems):
-            """all weight gradients of one block in one launch on the side stream; returns the event that marks its end."""
-            if side is None:
-                ops.linear_dw_group(problems, T, self.ws)
-                return None
-            e0 = new_event(); e0.record(main); side.wait_event(e0)
-            with torch.cuda.stream(side):
-                ops.linear_dw_group(problems, T, self.ws)
-                e1 = new_event(); e1.record(side)
-            return e1
-
-        def on_side(fn):
-            """``fn()`` on the side stream once main's work so far is done; returns the event that marks its end."""
-            if side is None:
-                fn()
-                return None
-            e0 = new_event(); e0.record(main); side.wait_event(e0)
-            with torch.cuda.stream(side):
-                fn()
-                e1 = new_event(); e1.record(side)
-            return e1
+            fin_ev[k] = last_fin = sx.run(lambda: ops.ln_finalize(ring[k], nblk, D, d0, d1, d2))
 
         def report(i):
             if on_block_done is not None:
                 # the block's weight gradients are produced by the side stream: report the block from
                 # there, so a data-parallel all-reduce queues behind the dW products and main never waits
-                if side is None:
-                    on_block_done(i)
-                else:
-                    with torch.cuda.stream(side):
-                        on_block_done(i)
+                sx.then(lambda: on_block_done(i))
 
         done_grp = [None, None]
         for i in reversed(range(self.depth) if grouped else ()):
@@ -645,19 +652,19 @@ class VitRunner:
                 G.scatter_cls(G.c_g, G.g)                 # (G.g was zeroed above)
                 # dO is zero behind every image's CLS row: the attention backward skips the other queries (their dQ rows come out zero)
                 ops.attention_bwd_varlen(G.qkv[i], G.o[i], G.do, dqkv, [(sg.n_img, sg.N, sg.lse[i]) for sg in G.segs], H, self.scale,
-                                         q_limit=1 if os.environ.get("GIPVIT_CLS_QLIMIT", "1") != "0" else 0)
+                                         q_limit=1 if self.sw.cls_qlimit else 0)
                 ln_bwd(G.dxn, G.x[2 * i], st[0], st[1], W.f(b + "norm1.weight"), gb_next,
                        W.g(b + "norm1.weight"), W.g(b + "norm1.bias"), W.g(f"blocks.{i - 1}.mlp.fc2.bias") if i > 0 else None,
                        dx_of=(dqkv, W.w(b + "attn.qkv.weight"), 3 * D), gb_scale=None if (rs is None or i == 0) else rs[i - 1, 1])
 
                 def last_block_dw():
                     # three weight gradients reduce over the n CLS rows, the qkv one over all tokens
-                    ops.linear(G.c_gb, G.c_h, W.g(b + "mlp.fc2.weight"), D, 4 * D, n, trans_a=True, trans_b=True, epilogue=ACC, workspace=self.ws)
+                    ops.linear(G.c_gb, G.c_h, W.g(b + "mlp.fc2.weight"), D, 4 * D, n, trans_a=True, trans_b=True, epilogue=ACC, workspace=self.ws_side)
                     ops.linear(G.c_dh, G.c_xn2, W.g(b + "mlp.fc1.weight"), 4 * D, D, n, trans_a=True, trans_b=True, epilogue=ACC,
-                               colsum_a=W.g(b + "mlp.fc1.bias"), workspace=self.ws)
-                    ops.linear(G.c_gb_att, G.c_o, W.g(b + "attn.proj.weight"), D, D, n, trans_a=True, trans_b=True, epilogue=ACC, workspace=self.ws)
-                    ops.linear_dw_group([(dqkv, G.xn1[i], W.g(b + "attn.qkv.weight"), W.g(b + "attn.qkv.bias"))], T, self.ws)
-                done_grp[par] = on_side(last_block_dw)
+                               colsum_a=W.g(b + "mlp.fc1.bias"), workspace=self.ws_side)
+                    ops.linear(G.c_gb_att, G.c_o, W.g(b + "attn.proj.weight"), D, D, n, trans_a=True, trans_b=True, epilogue=ACC, workspace=self.ws_side)
+                    ops.linear_dw_group([(dqkv, G.xn1[i], W.g(b + "attn.qkv.weight"), W.g(b + "attn.qkv.bias"))], T, self.ws_side)
+                done_grp[par] = sx.run(last_block_dw)
                 report(i)
                 continue
             if dp:
@@ -678,7 +685,7 @@ class VitRunner:
                      (dh, G.xn2[i], W.g(b + "mlp.fc1.weight"), W.g(b + "mlp.fc1.bias")),
                      (gb_att, G.o[i], W.g(b + "attn.proj.weight"), None),
                      (dqkv, G.xn1[i], W.g(b + "attn.qkv.weight"), W.g(b + "attn.qkv.bias"))]
-            done_grp[par] = dw_group(probs)
+            done_grp[par] = sx.run(lambda: ops.linear_dw_group(probs, T, self.ws_side))
             join(done_grp[par ^ 1])                       # block i + 1's group read gb_next (its MLP-half dY)
             ln_bwd(G.dxn, G.x[2 * i], st[0], st[1], W.f(b + "norm1.weight"), gb_next,
                    W.g(b + "norm1.weight"), W.g(b + "norm1.bias"), W.g(f"blocks.{i - 1}.mlp.fc2.bias") if (i > 0 and not dp) else None,
@@ -717,8 +724,8 @@ class VitRunner:
                    W.g(b + "norm1.weight"), W.g(b + "norm1.bias"), W.g(f"blocks.{i - 1}.mlp.fc2.bias") if (i > 0 and not dp) else None,
                    dx_of=(G.dqkv, W.w(b + "attn.qkv.weight"), 3 * D), gb_scale=None if (rs is None or i == 0) else rs[i - 1, 1])
             report(i)
-        join(done_qkv)          # every dW product is in (the side stream runs them in order); ws is free again
-        join(last_side[0])      # ... and the last finalize
+        join(done_qkv)          # every dW product is in (the side stream runs them in order); ws_side is free again
+        join(last_fin)          # ... and the last finalize
         if dp:
             ops.dropout(G.g, dseed(0, 0), dp[0], n=T * D)                                 # pos_drop's mask on the token gradient
         # token assembly + patch embedding, per segment
@@ -728,7 +735,7 @@ class VitRunner:
             # d cls_token = sum over images of the CLS-row gradient = dpos row 0
             ops.small_matmul(self.one, sg.dpos, W.g("cls_token").view(1, D), 1, D, 1, sam=0, sak=0, sbk=0, sbn=1, accumulate=True)
             ops.linear(sg.gpatch, sg.patches, W.g("patch_embed.proj.weight").view(D, 768), D, 768, sg.n_img * sg.P,
-                       trans_a=True, trans_b=True, epilogue=ACC, workspace=self.ws)
+                       trans_a=True, trans_b=True, epilogue=ACC, workspace=self.ws_side)
             ops.colsum(sg.dpos[1:], sg.P, D, self.cs_ws, W.g("patch_embed.proj.bias"), accumulate=True)
             if sg.pos is None:
                 ops.small_matmul(self.one, sg.dpos, gpos, 1, sg.N * D, 1, sam=0, sak=0, sbk=0, sbn=1, accumulate=True)
@@ -762,17 +769,15 @@ class HeadRunner:
     def __init__(self, D: int, K: int, hidden: int, bott: int, device):
         self.D, self.K, self.hidden, self.bott = D, K, hidden, bott
         self.cs_ws = _empty((64 * max(hidden, bott),), f32, device)
-        self.ws = _empty((L.lib.gv_linear_workspace_bytes() // 4,), f32, device)   # split-K slabs
-        self.ws_side = None                                                           # second one, for products queued on a side stream
+        # split-K slabs per stream (a few hundred rows against 2048-deep reductions: gv_linear splits K when handed a scratch)
+        self.ws_main = _empty((L.lib.gv_linear_workspace_bytes() // 4,), f32, device)
+        self.ws_side = _empty((L.lib.gv_linear_workspace_bytes() // 4,), f32, device)
 
     def forward(self, W: Weights, wn: torch.Tensor, hb: HeadBuffers, on_side: bool = False):
         """``on_side``: the call is queued on the engine's side stream (the teacher's head beside the student's forward): its
-        split-K products then take the side stream's scratch.  (A few hundred rows against 2048-deep reductions: gv_linear
-        splits K when it is handed a scratch buffer.)"""
+        split-K products then take the side stream's scratch."""
         R, D, Hd, Bt, K, E = hb.R, self.D, self.hidden, self.bott, self.K, L
-        if on_side and self.ws_side is None:
-            self.ws_side = _empty((L.lib.gv_linear_workspace_bytes() // 4,), f32, hb.feats.device)
-        ws = self.ws_side if on_side else self.ws
+        ws = self.ws_side if on_side else self.ws_main
         ops.linear(hb.feats, W.w("mlp.0.weight"), hb.h1, R, Hd, D, epilogue=E.EPI_BIAS | E.EPI_GELU | E.EPI_SAVE_PRE,
                    bias=W.f("mlp.0.bias"), aux_out=hb.h1p)
         ops.linear(hb.h1, W.w("mlp.2.weight"), hb.h2, R, Hd, Hd, epilogue=E.EPI_BIAS | E.EPI_GELU | E.EPI_SAVE_PRE,
@@ -781,40 +786,31 @@ class HeadRunner:
         ops.l2norm_fwd(hb.z, hb.zn, hb.inv, R, Bt)
         ops.linear(hb.zn, wn, hb.logits, R, K, Bt)
 
-    def backward(self, W: Weights, wn: torch.Tensor, hb: HeadBuffers, train_last_layer: bool = True, side=None):
-        """``side``: a stream for the weight-gradient products (they feed nothing in backward); each is queued
-        there behind an event that marks its operands ready, with a split-K workspace of its own."""
+    def backward(self, W: Weights, wn: torch.Tensor, hb: HeadBuffers, train_last_layer: bool, sx: SideStream):
+        """The weight-gradient products (they feed nothing in backward) go through ``sx``, the engine's side stream: each is
+        queued there once its operands are ready, with the scratch of the stream it runs on."""
         R, D, Hd, Bt, K, E = hb.R, self.D, self.hidden, self.bott, self.K, L
         ACC = E.EPI_ACCUM
-        if side is not None and self.ws_side is None:
-            self.ws_side = _empty((L.lib.gv_linear_workspace_bytes() // 4,), f32, hb.feats.device)
-        main = torch.cuda.current_stream() if side is not None else None
+        ws = self.ws_side if sx.side is not None else self.ws_main
 
-        def on_side(fn):
-            if side is None:
-                return fn(self.ws)
-            ev = torch.cuda.Event(); ev.record(main); side.wait_event(ev)
-            with torch.cuda.stream(side):
-                fn(self.ws_side)
-
-        def dw_last(ws):   # dW_n = dlogits^T zn, then through weight_norm (g frozen: norm_last_layer)
+        def dw_last():     # dW_n = dlogits^T zn, then through weight_norm (g frozen: norm_last_layer)
             ops.linear(hb.dlogits, hb.zn, hb.dwn, K, Bt, R, trans_a=True, trans_b=True)
             ops.weightnorm_bwd(hb.dwn, W.f("last_layer.weight_v"), W.f("last_layer.weight_g").view(-1),
                                W.g("last_layer.weight_v"), None, K, Bt, accumulate=True)
         if train_last_layer:
-            on_side(dw_last)
+            sx.run(dw_last)
         hb.dzn.zero_()         # split-K over the K=65536 classes accumulates with atomics
-        ops.linear(hb.dlogits, wn, hb.dzn, R, Bt, K, trans_b=True, epilogue=ACC, workspace=self.ws)
+        ops.linear(hb.dlogits, wn, hb.dzn, R, Bt, K, trans_b=True, epilogue=ACC, workspace=self.ws_main)
         ops.l2norm_bwd(hb.dzn, hb.zn, hb.inv, hb.dz, R, Bt)
-        on_side(lambda ws: ops.linear(hb.dz, hb.h2, W.g("mlp.4.weight"), Bt, Hd, R, trans_a=True, trans_b=True, epilogue=ACC,
-                                      colsum_a=W.g("mlp.4.bias"), workspace=ws))
+        sx.run(lambda: ops.linear(hb.dz, hb.h2, W.g("mlp.4.weight"), Bt, Hd, R, trans_a=True, trans_b=True, epilogue=ACC,
+                                  colsum_a=W.g("mlp.4.bias"), workspace=ws))
         ops.linear(hb.dz, W.w("mlp.4.weight"), hb.dh2, R, Hd, Bt, trans_b=True, epilogue=E.EPI_DGELU, aux_in=hb.h2p)
-        on_side(lambda ws: ops.linear(hb.dh2, hb.h1, W.g("mlp.2.weight"), Hd, Hd, R, trans_a=True, trans_b=True, epilogue=ACC,
-                                      colsum_a=W.g("mlp.2.bias"), workspace=ws))
-        ops.linear(hb.dh2, W.w("mlp.2.weight"), hb.dh1, R, Hd, Hd, trans_b=True, epilogue=E.EPI_DGELU, aux_in=hb.h1p, workspace=self.ws)
-        on_side(lambda ws: ops.linear(hb.dh1, hb.feats, W.g("mlp.0.weight"), Hd, D, R, trans_a=True, trans_b=True, epilogue=ACC,
-                                      colsum_a=W.g("mlp.0.bias"), workspace=ws))
-        ops.linear(hb.dh1, W.w("mlp.0.weight"), hb.dfeats, R, D, Hd, trans_b=True, workspace=self.ws)
+        sx.run(lambda: ops.linear(hb.dh2, hb.h1, W.g("mlp.2.weight"), Hd, Hd, R, trans_a=True, trans_b=True, epilogue=ACC,
+                                  colsum_a=W.g("mlp.2.bias"), workspace=ws))
+        ops.linear(hb.dh2, W.w("mlp.2.weight"), hb.dh1, R, Hd, Hd, trans_b=True, epilogue=E.EPI_DGELU, aux_in=hb.h1p, workspace=self.ws_main)
+        sx.run(lambda: ops.linear(hb.dh1, hb.feats, W.g("mlp.0.weight"), Hd, D, R, trans_a=True, trans_b=True, epilogue=ACC,
+                                  colsum_a=W.g("mlp.0.bias"), workspace=ws))
+        ops.linear(hb.dh1, W.w("mlp.0.weight"), hb.dfeats, R, D, Hd, trans_b=True, workspace=self.ws_main)
 
 
 # --------------------------------------------------------------------------- #
@@ -869,7 +865,8 @@ class DinoEngine:
         self.arena = Arena(specs, dev, teacher=True)
         self.sW, self.tW = Weights(self.arena, "backbone.", fp32=fp32), Weights(self.arena, "backbone.", teacher=True, fp32=fp32)
         self.sH, self.tH = Weights(self.arena, "head.", fp32=fp32), Weights(self.arena, "head.", teacher=True, fp32=fp32)
-        self.vit = VitRunner(arch, img_size, dev, fp32=fp32)
+        self.sw = EngineSwitches.from_env()
+        self.vit = VitRunner(arch, img_size, dev, fp32=fp32, sw=self.sw)
         self.head = HeadRunner(D, out_dim, hidden, bottleneck, dev)
         B = batch
         segs = [(n_global * B, gsize)] + ([(n_local * B, lsize)] if n_local else [])
@@ -894,10 +891,7 @@ class DinoEngine:
         self.reducer = reducer if reducer is not None else NoReducer()
         self._n_micro = 1
         self._plan = None             # gradient all-reduce ranges (dist.reduction_plan), built on first use
-        # the teacher's forward runs on the side stream beside the student's; GIPVIT_TEACHER_SIDE=0 queues it in front instead (A/B runs)
-        self._teacher_on_side = os.environ.get("GIPVIT_TEACHER_SIDE", "1") != "0"
-        if torch.device(device).type == "cuda":
-            self._ev_fork, self._ev_join, self._ev_zero = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
+        self._events: List[torch.cuda.Event] = []       # the SideStream pool of forward_backward
         # contiguous arena range of every block's weight-decayed matrices (arena order = backward order)
         self._block_range = {}
         for i in range(ARCHS[arch]["depth"]):
@@ -1014,35 +1008,28 @@ class DinoEngine:
                 else:
                     ops.crop_augment(tiles_u8, bl, views[1], self._vstats, self.lsize, out=self._lcrops)
                 s_src.append(self._lcrops); s_win.append([(0, 0)])
-        # the teacher's forward shares nothing with the student's until the loss: it runs on the
-        # side stream beside the student forward (fills the tail of each other's kernels)
-        side = self.vit.side if tiles_u8.is_cuda else None
-        t_side = side if self._teacher_on_side else None
-        # fills nothing in the forward depends on (the gradient arena, the backward's zero-initialised scratch) go to the side
-        # stream, beside the forward pass; the main stream picks their event up before the head backward
-        if side is not None:
-            main = torch.cuda.current_stream()
-            self._ev_fork.record(main); side.wait_event(self._ev_fork)
-            with torch.cuda.stream(side):
-                if first:
-                    a.g.zero_()
-                self.vit.prepare_backward(self.g_stu)
-                self._ev_zero.record(side)
-        else:
+        sx = SideStream(self.vit.side if tiles_u8.is_cuda else None, self._events)
+
+        def fills():
+            # fills nothing in the forward depends on (the gradient arena, the backward's zero-initialised scratch): on the side
+            # stream, beside the forward pass (without one, the backward zeroes its scratch when it starts)
             if first:
                 a.g.zero_()
-        if t_side is not None:
-            with torch.cuda.stream(side):
-                self.vit.forward(self.tW, self.g_teach, t_src, t_win, self.mean, self.std, self.hb_t.feats, fill=fill)
-                self.head.forward(self.tH, self.wn_t, self.hb_t, on_side=True)
-                self._ev_join.record(side)
-        else:
-            self.vit.forward(self.tW, self.g_teach, t_src, t_win, self.mean, self.std, self.hb_t.feats, fill=fill)
-            self.head.forward(self.tH, self.wn_t, self.hb_t)
+            if sx.side is not None:
+                self.vit.prepare_backward(self.g_stu)
+
+        # the teacher's forward shares nothing with the student's until the loss: it runs on the
+        # side stream beside the student forward (fills the tail of each other's kernels)
+        t_side = sx.side is not None and self.sw.teacher_side
+
+        def teacher():
+            self.vit.forward(self.tW, self.g_teach, t_src, t_win, self.mean, self.std, self.hb_t.feats, fill=fill, on_side=t_side)
+            self.head.forward(self.tH, self.wn_t, self.hb_t, on_side=t_side)
+        ev_zero = sx.run(fills)
+        ev_teacher = sx.run(teacher) if t_side else teacher()
         self.vit.forward(self.sW, self.g_stu, s_src, s_win, self.mean, self.std, self.hb_s.feats, fill=fill)
         self.head.forward(self.sH, self.wn_s, self.hb_s)
-        if t_side is not None:
-            main.wait_event(self._ev_join)
+        sx.join(ev_teacher)
         ops.dino_loss(self.hb_s.logits, self.hb_t.logits, self.center, self.hb_s.dlogits, self.loss, self.center_sum,
                       self.loss_ws, B, V, G, self.K, self.ts, self.tt, hyper=self.hyper,
                       loss_scale=self.scaler.scale if self.scaler is not None else None)
@@ -1055,9 +1042,8 @@ class DinoEngine:
                 self.loss.copy_(self._loss_acc / mn); self.center_sum.copy_(self._center_acc)
         if last:
             self.reducer.reduce_tensor(self.center_sum)
-        if side is not None:
-            main.wait_event(self._ev_zero)
-        self.head.backward(self.sH, self.wn_s, self.hb_s, self.train_last_layer, side=side)
+        sx.join(ev_zero)
+        self.head.backward(self.sH, self.wn_s, self.hb_s, self.train_last_layer, sx)
         if not last:        # more micro-batches follow: gradients keep accumulating locally
             self.vit.backward(self.sW, self.g_stu, self.hb_s.dfeats)
             return
@@ -1073,11 +1059,7 @@ class DinoEngine:
                 for trg, lo, hi in plan:
                     if trg == trigger:
                         self.reducer.reduce_range(a.g, lo, hi)
-        if side is not None:              # the head's weight gradients were queued on the side stream
-            with torch.cuda.stream(side):
-                release("head")
-        else:
-            release("head")
+        sx.then(lambda: release("head"))     # behind the head's weight gradients, which were queued on the side stream
         self.vit.backward(self.sW, self.g_stu, self.hb_s.dfeats, on_block_done=release)
         release("end")
         self.reducer.finish()
@@ -1088,7 +1070,7 @@ class DinoEngine:
             a = self.arena
             head_names = [n for n in a.order if n.startswith("head.") and a.off[n] < a.n_decay]
             head_span = (min(a.off[n] for n in head_names), max(a.span(n)[1] for n in head_names)) if head_names else None
-            self._plan = reduction_plan(head_span, self._block_range, a.n, bucket_bytes=int(os.environ.get("GIPVIT_BUCKET_MB", "25")) << 20)
+            self._plan = reduction_plan(head_span, self._block_range, a.n, bucket_bytes=self.sw.bucket_mb << 20)
         return self._plan
 
     def optimizer_step(self):

@@ -183,7 +183,9 @@ def _gloo_worker(rank, world, port, q):
     red.reduce_range(g, 0, 384)          # head range first, as the engine does
     red.reduce_range(g, 384, 1000)
     red.finish()
-    q.put((rank, g.clone(), c.clone(), shard_range(64, rank, world)))
+    # numpy copies travel by value: a tensor would go through torch's shared-memory handover, whose file descriptor the parent
+    # fetches from THIS process -- which may have exited by then (EOFError / FileNotFoundError in the parent's q.get)
+    q.put((rank, g.numpy().copy(), c.numpy().copy(), shard_range(64, rank, world)))
     dist.destroy_process_group()
 
 
@@ -201,6 +203,7 @@ def test_reducer_world_size_2_gloo():
     res = sorted([q.get(timeout=120) for _ in ps], key=lambda t: t[0])
     [p.join(60) for p in ps]
     for rank, g, c, shard in res:
+        g, c = torch.from_numpy(g), torch.from_numpy(c)
         assert torch.equal(g, torch.arange(1000, dtype=torch.float32) * 3)   # (1 + 2) x
         assert torch.equal(c, torch.full((16,), 3.0))
         assert shard == (32 * rank, 32 * rank + 32)
@@ -242,6 +245,69 @@ def test_reduction_plan_tiles_the_arena_in_backward_order():
     # a one-block model and a headless one still tile
     assert reduction_plan(None, {0: (0, 100)}, 130) == [("end", 0, 130)]
     assert reduction_plan((0, 50), {1: (50, 80), 0: (80, 100)}, 130, bucket_bytes=1 << 30) == [("head", 0, 50), (1, 50, 80), ("end", 80, 130)]
+
+
+def test_engine_switches_from_env(monkeypatch):
+    """engine.EngineSwitches.from_env: the fast-path defaults with no GIPVIT_* variable set; "0" switches a boolean off and any
+    other value leaves it on; the side stream's priority and the all-reduce range size are read as integers."""
+    import dataclasses
+    from gipvit.engine import EngineSwitches
+    for k in list(os.environ):
+        if k.startswith("GIPVIT_"):
+            monkeypatch.delenv(k)
+    sw = EngineSwitches.from_env()
+    assert sw == EngineSwitches() and sw.side_priority == 0 and sw.bucket_mb == 25
+    flags = [f.name for f in dataclasses.fields(EngineSwitches) if isinstance(f.default, bool)]
+    assert len(flags) == 8 and all(getattr(sw, n) for n in flags)
+    for n in flags:
+        monkeypatch.setenv("GIPVIT_" + n.upper(), "0")
+        assert [getattr(EngineSwitches.from_env(), m) for m in flags] == [m != n for m in flags], n
+        monkeypatch.setenv("GIPVIT_" + n.upper(), "1")
+        assert getattr(EngineSwitches.from_env(), n)
+    monkeypatch.setenv("GIPVIT_SIDE_PRIORITY", "-1")
+    monkeypatch.setenv("GIPVIT_BUCKET_MB", "64")
+    sw = EngineSwitches.from_env()
+    assert sw.side_priority == -1 and sw.bucket_mb == 64
+    with pytest.raises(dataclasses.FrozenInstanceError):
+        sw.group_dw = False
+
+
+def test_engine_switches_are_read_in_one_place_and_documented():
+    """engine.py touches the environment only in EngineSwitches.from_env and in _empty (GIPVIT_POISON), so a switch cannot change
+    between the launches of a step; every switch is in README's list; the retired GIPVIT_CLS_TAIL_FUSED is gone from the package."""
+    import ast
+    import dataclasses
+    from gipvit.engine import EngineSwitches
+    pkg = os.path.join(ROOT, "gipmed-project-self-supervised-vit_amd")
+    tree = ast.parse(open(os.path.join(pkg, "engine.py")).read())
+    allowed = set()
+    for node in ast.walk(tree):
+        if isinstance(node, ast.FunctionDef) and node.name in ("from_env", "_empty"):
+            allowed |= {id(n) for n in ast.walk(node)}
+    uses = [n for n in ast.walk(tree) if isinstance(n, ast.Attribute) and n.attr in ("environ", "getenv")]
+    assert len(uses) == 2 and all(id(n) in allowed for n in uses), [n.lineno for n in uses]
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    switches = readme[readme.index("Runtime switches"):]
+    switches = switches[:switches.index("\n\n")]
+    for f in dataclasses.fields(EngineSwitches):
+        assert f"`GIPVIT_{f.name.upper()}" in switches, f.name
+    for dirpath, _, files in os.walk(pkg):
+        for fn in files:
+            if fn.endswith((".py", ".hip", ".h", ".cpp", ".sh")):
+                assert "GIPVIT_CLS_TAIL_FUSED" not in open(os.path.join(dirpath, fn), errors="replace").read(), fn
+
+
+def test_side_stream_helper_runs_inline_without_a_side_stream():
+    """engine.SideStream with no side stream (FeatureExtractor, GIPVIT_DW_STREAM=0, roofline's exclusive runs): the work runs
+    inline, in call order, and no event is made or waited for."""
+    from gipvit.engine import SideStream
+    pool, ran = [], []
+    sx = SideStream(None, pool)
+    assert sx.main is None
+    assert sx.run(lambda: ran.append("run")) is None
+    sx.then(lambda: ran.append("then"))
+    sx.join(None)
+    assert ran == ["run", "then"] and pool == []
 
 
 def test_comm_setup_environment_contract(monkeypatch):
