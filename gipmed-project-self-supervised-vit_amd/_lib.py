@@ -35,6 +35,9 @@ gv_patchify_args = _struct("gv_patchify_args", [
     ("tiles", vp), ("patches", vp), ("n_img", i32), ("tile_h", i32), ("tile_w", i32), ("img_stride", i64),
     ("n_win", i32), ("win_y", i32 * 16), ("win_x", i32 * 16), ("crop", i32), ("mean", f32 * 3), ("std", f32 * 3),
     ("n_tiles", i32), ("fill", vp)])
+gv_patchify_nchw_args = _struct("gv_patchify_nchw_args", [
+    ("images", vp), ("patches", vp), ("n_img", i32), ("n_tiles", i32), ("img_h", i32), ("img_w", i32),
+    ("stride_n", i64), ("stride_c", i64), ("stride_h", i64), ("n_win", i32), ("win_y", i32 * 16), ("win_x", i32 * 16), ("crop", i32)])
 gv_augment_params = _struct("gv_augment_params", [
     ("n_color", i32), ("order", i32 * 4), ("bf", f32), ("cf", f32), ("sf", f32), ("hue", i32), ("blur", i32), ("kc", f32), ("ks", f32),
     ("sigma", f32), ("seed", C.c_uint32), ("d4", i32), ("zoom", i32), ("a0", i32), ("a2", i32), ("cut", i32 * 4)])
@@ -135,7 +138,7 @@ gv_lamb_args = _struct("gv_lamb_args", [
 
 # entry point -> argument struct (every `int gv_*(const args*, void* stream)` of the header)
 ENTRY_POINTS = {
-    "gv_patchify": gv_patchify_args, "gv_crop_resize": gv_crop_resize_args, "gv_crop_augment": gv_crop_augment_args, "gv_augment": gv_augment_args, "gv_layernorm_fwd": gv_layernorm_fwd_args, "gv_layernorm_bwd": gv_layernorm_bwd_args,
+    "gv_patchify": gv_patchify_args, "gv_patchify_nchw": gv_patchify_nchw_args, "gv_crop_resize": gv_crop_resize_args, "gv_crop_augment": gv_crop_augment_args, "gv_augment": gv_augment_args, "gv_layernorm_fwd": gv_layernorm_fwd_args, "gv_layernorm_bwd": gv_layernorm_bwd_args,
     "gv_colsum_finalize": gv_colsum_finalize_args, "gv_ln_finalize": gv_ln_finalize_args, "gv_colsum": gv_colsum_args, "gv_linear": gv_linear_args,
     "gv_linear_ln_fwd": gv_linear_ln_fwd_args, "gv_mlp_ln_fwd": gv_mlp_ln_fwd_args, "gv_linear_ln_bwd": gv_linear_ln_bwd_args, "gv_expand_rows": gv_expand_rows_args, "gv_linear_dw_group": gv_linear_dw_group_args,
     "gv_attention_fwd": gv_attention_fwd_args, "gv_attention_fwd_varlen": gv_attention_fwd_varlen_args, "gv_attention_bwd": gv_attention_bwd_args, "gv_attention_bwd_varlen": gv_attention_bwd_varlen_args, "gv_cls_rows": gv_cls_rows_args,
@@ -146,7 +149,7 @@ ENTRY_POINTS = {
     "gv_adamw_ema": gv_adamw_ema_args, "gv_loss_scale_update": gv_loss_scale_update_args, "gv_lamb": gv_lamb_args, "gv_agc": gv_agc_args, "gv_dropout": gv_dropout_args, "gv_dropout_add": gv_dropout_add_args,
     # fp32 operand mode: the same structs with every bf16 buffer read / written as f32
     "gv_linear_f32": gv_linear_args, "gv_attention_fwd_f32": gv_attention_fwd_args, "gv_attention_bwd_f32": gv_attention_bwd_args,
-    "gv_layernorm_fwd_f32": gv_layernorm_fwd_args, "gv_layernorm_bwd_f32": gv_layernorm_bwd_args, "gv_patchify_f32": gv_patchify_args,
+    "gv_layernorm_fwd_f32": gv_layernorm_fwd_args, "gv_layernorm_bwd_f32": gv_layernorm_bwd_args, "gv_patchify_f32": gv_patchify_args, "gv_patchify_nchw_f32": gv_patchify_nchw_args,
     "gv_tokens_bwd_f32": gv_tokens_bwd_args, "gv_l2norm_fwd_f32": gv_l2norm_fwd_args, "gv_l2norm_bwd_f32": gv_l2norm_bwd_args,
     "gv_weightnorm_fwd_f32": gv_weightnorm_fwd_args, "gv_dino_loss_f32": gv_dino_loss_args,
 }

@@ -133,6 +133,81 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(gv_crop_resize_args a)
     dst[0] = pk[0]; dst[1] = pk[1]; dst[2] = pk[2];
 }
 
+
+// ---- patchify_nchw: crop windows of an ALREADY NORMALISED float32 NCHW batch -> patch rows (the reference's own
+// input, Data [B, 3, H, W] after ToTensor + Normalize, train.py:1027-1033).  Same output layout as patchify; no mean / std:
+// the value is only rounded to the build's 16-bit format (RNE, the hardware convert: bit-equal to torch's .to()) or copied
+// (f32 rows).  HBM-bound: algorithmic bytes / image crop^2 * 12 in + (crop/16)^2 * 768 * sizeof(out) out.
+//
+// One workgroup per strip of up to 16 patches of one patch row: phase 1 reads its 3 channels x 16 pixel rows with 16-B loads
+// (a row segment is contiguous in W; NCHW_U loads in flight per lane) and stores them converted into an LDS image
+// [c][py][x]; phase 2 writes the strip's patch rows -- one contiguous run of n_patch * 768 elements -- with 16-B stores, each
+// lane's 16 B being 16 B of one LDS image row.  A row segment that does not start 16-B aligned (a window at an odd column, an
+// odd stride) takes four 4-B loads per item instead.
+constexpr int NCHW_MAXP = 16, NCHW_U = 6;
+
+template <typename OT>
+__global__ __launch_bounds__(256) void patchify_nchw_kernel(gv_patchify_nchw_args a, int side, int n_chunk) {
+    constexpr int V = 16 / (int)sizeof(OT);                       // elements per 16-B store
+    constexpr int ROW = NCHW_MAXP * 16 + 16 / (int)sizeof(OT);    // LDS image row (+16 B: rows start on different banks)
+    __shared__ __attribute__((aligned(16))) OT img_lds[3 * 16 * ROW];
+    const int bid = blockIdx.x;
+    const int chunk = bid % n_chunk, prow = (bid / n_chunk) % side, img = bid / (n_chunk * side);
+    const int tile = img % a.n_tiles, win = img / a.n_tiles;
+    const int p0 = chunk * NCHW_MAXP, np = min(NCHW_MAXP, side - p0);
+    const int y0 = a.win_y[win] + prow * 16, x0 = a.win_x[win] + p0 * 16;
+    const float* base = a.images + (long)tile * a.stride_n + (long)y0 * a.stride_h + x0;
+    // phase 1: item = (channel, pixel row, 4-pixel group); 48 row segments of np * 16 pixels
+    const int q = np * 4, n_items = 48 * q;
+    for (int b0 = threadIdx.x; b0 < n_items; b0 += 256 * NCHW_U) {
+        f32x4 v[NCHW_U];
+#pragma unroll
+        for (int u = 0; u < NCHW_U; ++u) {
+            const int it = b0 + u * 256;
+            if (it < n_items) {
+                const int seg = it / q, g = it - seg * q;
+                const float* src = base + (long)(seg >> 4) * a.stride_c + (long)(seg & 15) * a.stride_h + g * 4;
+                if (((uintptr_t)src & 15) == 0) {
+                    v[u] = *(const f32x4*)src;
+                } else {
+                    v[u] = f32x4{src[0], src[1], src[2], src[3]};
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < NCHW_U; ++u) {
+            const int it = b0 + u * 256;
+            if (it < n_items) {
+                const int seg = it / q, g = it - seg * q;
+                OT* d = img_lds + seg * ROW + g * 4;
+                if constexpr (sizeof(OT) == 4) {
+                    *(f32x4*)d = v[u];
+                } else {
+                    bf16x4 o;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) o[i] = (bf16)v[u][i];
+                    *(bf16x4*)d = o;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // phase 2: the strip's rows [(img * side + prow) * side + p0, + np) x 768, contiguous; element e = p*768 + c*256 + py*16 + px
+    OT* out = (OT*)a.patches + ((long)(img * side + prow) * side + p0) * 768;
+    const int n_out = np * 768 / V;
+    for (int o = threadIdx.x; o < n_out; o += 256) {
+        const int e = o * V;
+        const int p = e / 768, k = e - p * 768;
+        const int c = k >> 8, py = (k >> 4) & 15, px = k & 15;
+        const OT* s = img_lds + (c * 16 + py) * ROW + p * 16 + px;
+        if constexpr (sizeof(OT) == 4) {
+            *(f32x4*)(out + e) = *(const f32x4*)s;
+        } else {
+            *(bf16x8*)(out + e) = *(const bf16x8*)s;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int gv_crop_resize(const gv_crop_resize_args* a, void* stream) {
@@ -167,3 +242,27 @@ template <bool F32OUT> static int patchify_launch(const gv_patchify_args* a, voi
 }
 extern "C" int gv_patchify(const gv_patchify_args* a, void* stream) { return patchify_launch<false>(a, stream); }
 extern "C" int gv_patchify_f32(const gv_patchify_args* a, void* stream) { return patchify_launch<true>(a, stream); }
+
+template <typename OT> static int patchify_nchw_launch(const gv_patchify_nchw_args* a, void* stream, const char* name) {
+    GV_REQUIRE(a && a->images && a->patches, GV_E_NULL, "%s: null pointer", name);
+    GV_REQUIRE(a->crop > 0 && a->crop % 16 == 0, GV_E_SHAPE, "%s: crop=%d must be a positive multiple of 16", name, a->crop);
+    GV_REQUIRE(a->n_win >= 1 && a->n_win <= 16 && a->n_tiles >= 1 && a->n_img == a->n_win * a->n_tiles, GV_E_SHAPE,
+               "%s: n_img (%d) must equal n_win (%d) * n_tiles (%d), 1 <= n_win <= 16", name, a->n_img, a->n_win, a->n_tiles);
+    GV_REQUIRE(a->img_h > 0 && a->img_w > 0 && a->stride_n >= 0 && a->stride_c >= 0 && a->stride_h >= 0, GV_E_SHAPE,
+               "%s: bad image shape %dx%d or negative stride", name, a->img_h, a->img_w);
+    for (int w = 0; w < a->n_win; ++w)
+        GV_REQUIRE(a->win_y[w] >= 0 && a->win_x[w] >= 0 && a->win_y[w] + a->crop <= a->img_h && a->win_x[w] + a->crop <= a->img_w,
+                   GV_E_SHAPE, "%s: window %d (%d,%d)+%d leaves the %dx%d image", name, w, a->win_y[w], a->win_x[w], a->crop, a->img_h, a->img_w);
+    GV_REQUIRE(gv_aligned(a->images, 4), GV_E_ALIGN, "%s: images must be 4-byte aligned", name);
+    GV_REQUIRE(gv_aligned(a->patches, 16), GV_E_ALIGN, "%s: patches must be 16-byte aligned", name);
+    const int side = a->crop / 16, n_chunk = (side + NCHW_MAXP - 1) / NCHW_MAXP;
+    const long blocks = (long)a->n_img * side * n_chunk;
+    GV_REQUIRE(blocks < (1L << 31), GV_E_SHAPE, "%s: %ld workgroups exceed the grid", name, blocks);
+    hipLaunchKernelGGL(patchify_nchw_kernel<OT>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *a, side, n_chunk);
+    GV_LAUNCH_CHECK(name);
+    return GV_OK;
+}
+extern "C" int gv_patchify_nchw(const gv_patchify_nchw_args* a, void* stream) { return patchify_nchw_launch<bf16>(a, stream, "gv_patchify_nchw"); }
+extern "C" int gv_patchify_nchw_f32(const gv_patchify_nchw_args* a, void* stream) {
+    return patchify_nchw_launch<float>(a, stream, "gv_patchify_nchw_f32");
+}

@@ -183,6 +183,14 @@ def select_fold(slides, test_fold, train: bool):
     return keep
 
 
+def probe_hook_format(slides, transform: Callable, tile_size: int) -> str:
+    """Batch format ("u8_nhwc" / "f32_nchw") a transform hook implies: the hook is called once, on the first tile of the
+    first slide (``scan_slides`` order).  Output in neither accepted form raises TypeError."""
+    from .transformations import hook_output_format
+    t = read_tile_file(slides[0][1][0])[:tile_size, :tile_size, :3]
+    return hook_output_format(transform(t), tile_size)
+
+
 class TileFolder:
     """Training source over ``root/<slide>/tile_<i>.data`` (+ ``root/labels.csv``).
 
@@ -190,7 +198,12 @@ class TileFolder:
     one uniformly random tile of slide ``i % len(slides)`` (datasets.py:445-466).  Draws are sharded over ranks
     after truncation to a common length, so every rank runs the same number of batches (the reference gives every
     rank the whole set, train.py:732 -- DESIGN.md section 6).  ``fill(out, targets)`` reads the next batch into
-    caller buffers with ``workers`` reader threads; iteration yields the batch dict like the other sources."""
+    caller buffers with ``workers`` reader threads; iteration yields the batch dict like the other sources.
+
+    ``batch_format`` is ``"u8_nhwc"`` (uint8 [B, tile, tile, 3]: no hook, or a hook returning uint8 HWC tiles) or
+    ``"f32_nchw"`` (float32 [B, 3, tile, tile]: a hook returning the reference's normalised FloatTensor[3, tile, tile],
+    transformations.py:199-200).  A user hook is probed once, on the first tile of the first slide, when the format is
+    first asked for."""
 
     def __init__(self, root: str, batch: int, transform: Optional[Callable] = None, rank: int = 0, world: int = 1, seed: int = 0,
                  tile_size: int = 256, n_tiles: int = 10, test_fold=None, train: bool = True, target: Optional[str] = None,
@@ -210,9 +223,30 @@ class TileFolder:
         self.pool = ThreadPoolExecutor(max_workers=max(1, int(workers)))
         self._order = None
         self._pos = 0
+        self._format = None
 
     def __len__(self):
         return self.per_rank // self.B
+
+    def _hook_applies(self) -> bool:
+        return self.transform is not None and bool(getattr(self.transform, "ops", True))
+
+    @property
+    def batch_format(self) -> str:
+        if self._format is None:
+            from .transformations import TileTransform, hook_output_format
+            if not self._hook_applies() or isinstance(self.transform, TileTransform):
+                self._format = "u8_nhwc"
+            else:
+                self._format = probe_hook_format(self.slides, self.transform, self.tile_size)
+        return self._format
+
+    def batch_shape(self) -> Tuple[Tuple[int, ...], np.dtype]:
+        """(shape, numpy dtype) of one batch in this source's ``batch_format``."""
+        t = self.tile_size
+        if self.batch_format == "f32_nchw":
+            return (self.B, 3, t, t), np.float32
+        return (self.B, t, t, 3), np.uint8
 
     def _start_epoch(self):
         order = self.rng.permutation(len(self.slides) * self.n_tiles)[: self.per_rank * self.world]
@@ -232,7 +266,12 @@ class TileFolder:
         return out
 
     def fill(self, out: np.ndarray, targets: np.ndarray):
-        """Read the next batch into ``out`` [B, H, W, 3] u8 / ``targets`` [B, 1] i64; returns futures to wait on."""
+        """Read the next batch into ``out`` (``batch_shape()``: [B, H, W, 3] u8, or [B, 3, H, W] f32 in float mode) /
+        ``targets`` [B, 1] i64; returns futures to wait on."""
+        fmt = self.batch_format
+        want = self.batch_shape()
+        if fmt == "f32_nchw" and (out.shape[1:] != want[0][1:] or out.dtype != want[1]):
+            raise TypeError(f"TileFolder.fill: {fmt} batches need a {np.dtype(want[1]).name} {want[0]} buffer, got {out.dtype} {out.shape}")
         items = self.plan()
         for j, (_, y) in enumerate(items):
             targets[j, 0] = y
@@ -246,16 +285,18 @@ class TileFolder:
             self._read_one(items[j][0], out[j])
 
     def _read_one(self, path, dst):
-        if self.transform is None or not getattr(self.transform, "ops", True):
+        if not self._hook_applies():
             read_tile_into(path, dst)
         else:
+            from .transformations import hook_output_array
             t = read_tile_file(path)[: self.tile_size, : self.tile_size, :3]
-            dst[...] = self.transform(t)
+            dst[...] = hook_output_array(self.transform(t))
 
     def __iter__(self):
         self._start_epoch()
+        shape, dt = self.batch_shape()
         for _ in range(len(self)):
-            out = np.empty((self.B, self.tile_size, self.tile_size, 3), np.uint8)
+            out = np.empty(shape, dt)
             tgt = np.empty((self.B, 1), np.int64)
             for f in self.fill(out, tgt):
                 f.result()
@@ -357,8 +398,16 @@ class DevicePrefetcher:
     def __init__(self, source, device, tile_shape: Tuple[int, int, int, int], augmenter=None):
         """``augmenter`` (gipvit.augment.TileAugmenter): its per-tile draws for the batch are made while the batch is
         staged and travel in the same pinned slot / on the same copy stream (``'AugParams'``, ``'Fill'`` in the batch dict);
-        a pageable copy issued from the launch loop would block it behind the tile transfer."""
+        a pageable copy issued from the launch loop would block it behind the tile transfer.
+        ``tile_shape`` is (B, H, W, 3); a source whose ``batch_format`` is ``"f32_nchw"`` (TileFolder with a float-returning
+        hook) is staged as float32 [B, 3, H, W] instead (no augmenter: the device recipes work on uint8 tiles)."""
         self.src, self.dev = source, torch.device(device)
+        self.batch_format = getattr(source, "batch_format", "u8_nhwc")
+        dt = torch.uint8
+        if self.batch_format == "f32_nchw":
+            if augmenter is not None:
+                raise ValueError("DevicePrefetcher: the device augmentation recipes work on uint8 tiles, the source delivers float32 NCHW")
+            tile_shape, dt = (tile_shape[0], 3, tile_shape[1], tile_shape[2]), torch.float32
         self.copy = torch.cuda.Stream(self.dev)
         B = tile_shape[0]
         self.aug = augmenter
@@ -369,9 +418,9 @@ class DevicePrefetcher:
             self.d_a = [torch.empty(B * rec, dtype=torch.uint8, device=self.dev) for _ in range(2)]
             self.d_f = [torch.zeros(B, 8, dtype=torch.float32, device=self.dev) for _ in range(2)]
             self.has_fill = [False, False]
-        self.pin = [torch.empty(tile_shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.pin = [torch.empty(tile_shape, dtype=dt).pin_memory() for _ in range(2)]
         self.pin_t = [torch.empty((B, 1), dtype=torch.int64).pin_memory() for _ in range(2)]
-        self.dbuf = [torch.empty(tile_shape, dtype=torch.uint8, device=self.dev) for _ in range(2)]
+        self.dbuf = [torch.empty(tile_shape, dtype=dt, device=self.dev) for _ in range(2)]
         self.dtgt = [torch.empty((B, 1), dtype=torch.int64, device=self.dev) for _ in range(2)]
         self.ready = [torch.cuda.Event() for _ in range(2)]       # H2D of slot k done
         self.freed = [None, None]                                   # consumer's last use of slot k (recorded on its stream)

@@ -57,6 +57,28 @@ def _empty(shape, dt, device):
     return t
 
 
+def input_form(x, n: Optional[int], hw: Optional[Tuple[int, int]], float_extras: Sequence[Tuple[str, object]] = ()) -> str:
+    """The two image forms every engine entry point takes: ``"u8"`` for uint8 NHWC tiles [n, H, W, 3] (ToTensor + Normalize
+    fused into gv_patchify, the fast path) or ``"f32"`` for float32 NCHW [n, 3, H, W] already normalised (the reference's
+    ``Data``, train.py:1027-1033: gv_patchify_nchw, W stride 1).  Float input must have ``n`` images of ``hw`` = (H, W) (either
+    None: not checked; uint8 tiles keep their callers' own checks); ``float_extras``: (name, value) of the arguments that
+    belong to the u8 pipeline -- any of them set with float input is a ValueError."""
+    u8 = isinstance(x, torch.Tensor) and x.dtype == torch.uint8 and x.dim() == 4 and x.shape[-1] == 3
+    fl = isinstance(x, torch.Tensor) and x.dtype == f32 and x.dim() == 4 and x.shape[1] == 3 and x.stride(-1) == 1
+    if not (u8 or fl):
+        got = f"{x.dtype} {tuple(x.shape)} strides {x.stride()}" if isinstance(x, torch.Tensor) else type(x).__name__
+        raise TypeError("images: expected uint8 NHWC tiles [n, H, W, 3] or float32 NCHW [n, 3, H, W] already normalised "
+                        f"(W stride 1), got {got}")
+    if fl:
+        want = (x.shape[0] if n is None else n, 3) + (tuple(x.shape[2:]) if hw is None else tuple(hw))
+        if tuple(x.shape) != want:
+            raise ValueError(f"images: expected float32 NCHW of shape {want}, got {tuple(x.shape)}")
+        for name, v in float_extras:
+            if v is not None:
+                raise ValueError(f"{name}= works on uint8 tiles (its boxes / crops are u8-pipeline objects): not with float32 NCHW input")
+    return "u8" if u8 else "f32"
+
+
 def _round_up(n: int, m: int) -> int:
     return (n + m - 1) // m * m
 
@@ -416,7 +438,8 @@ class VitRunner:
     # ---- forward: tiles -> CLS features written into feats[row_off + seg.img0 ...]
     def forward(self, W: Weights, G: VitGroup, tiles_u8, windows, mean, std, feats, row_off: int = 0, fill=None, on_side: bool = False):
         """windows: one list of (y0, x0) crop origins per segment; tiles_u8: one NHWC u8 tensor for all
-        segments, or one per segment (pre-cut crops: each with the single window (0, 0)).  ``fill``: per-tile normalised
+        segments, or one per segment (pre-cut crops: each with the single window (0, 0)).  A float32 NCHW source (already
+        normalised, engine.input_form) goes through gv_patchify_nchw instead, without mean / std.  ``fill``: per-tile normalised
         fill boxes of the augmentation (gipvit.augment: Cutout after Normalize, MeanPixelRegularization), f32 [n_tiles, 8].
         ``on_side``: the call is queued on the side stream (the teacher beside the student): its split-K products take that
         stream's scratch."""
@@ -426,7 +449,12 @@ class VitRunner:
         x0 = G.xbuf(0)
         for k, (sg, wins) in enumerate(zip(G.segs, windows)):
             src = tiles_u8[k] if isinstance(tiles_u8, (list, tuple)) else tiles_u8
-            ops.patchify(src, wins, sg.crop, mean, std, out=sg.patches, fill=fill)
+            if src.dtype == f32:
+                if fill is not None:
+                    raise ValueError("fill= works on uint8 tiles: not with float32 NCHW input")
+                ops.patchify_nchw(src, wins, sg.crop, out=sg.patches)
+            else:
+                ops.patchify(src, wins, sg.crop, mean, std, out=sg.patches, fill=fill)
             if sg.pos is None:
                 pos = pos_full
             else:   # interpolate_pos_encoding: row 0 = cls pos, rows 1.. = M @ pos[1:]
@@ -974,8 +1002,11 @@ class DinoEngine:
         micro-batch j of n (gradient accumulation): gradients, loss and centre sums add up over
         the n calls and the data-parallel reduction is issued from the last one only.
         ``views``: (global, local) packed per-crop records of multicrop.ViewAugmentSampler.sample -- with ``boxes``, every crop
-        gets its own colour jitter / grayscale / blur / solarisation in the pass that cuts it (gv_crop_augment)."""
+        gets its own colour jitter / grayscale / blur / solarisation in the pass that cuts it (gv_crop_augment).
+        ``tiles_u8``: uint8 [B, tile, tile, 3] or float32 NCHW [B, 3, tile, tile] already normalised (engine.input_form): float
+        input runs the fixed crop windows only (no ``boxes`` / ``views`` / ``fill``)."""
         B, G, V = self.B, self.G, self.V
+        input_form(tiles_u8, B, (self.tile, self.tile), (("fill", fill), ("boxes", boxes), ("views", views)))
         a = self.arena
         mj, mn = micro
         first, last = mj == 0, mj == mn - 1
@@ -1110,7 +1141,8 @@ class DinoEngine:
         n = len(tile_batches)
         self.set_hyper(n_micro=n, **sched)
         for j, tb in enumerate(tile_batches):
-            assert tb.shape == (self.B, self.tile, self.tile, 3) and tb.dtype == torch.uint8
+            if input_form(tb, self.B, (self.tile, self.tile)) == "u8":
+                assert tb.shape == (self.B, self.tile, self.tile, 3)
             self.forward_backward(tb, micro=(j, n))
         self._n_micro = n
         try:
@@ -1120,10 +1152,11 @@ class DinoEngine:
         return self.loss
 
     def step(self, tiles_u8: torch.Tensor, boxes=None, fill=None, views=None, **sched) -> torch.Tensor:
-        """One full training step on [B, tile, tile, 3] uint8 NHWC tiles.  Returns the
-        (device, un-synchronised) loss tensor.  ``boxes``: (global, local) int32 device tensors from
-        multicrop.MultiCropSampler.sample -- random-resized crops instead of the fixed parity windows."""
-        assert tiles_u8.shape == (self.B, self.tile, self.tile, 3) and tiles_u8.dtype == torch.uint8
+        """One full training step on [B, tile, tile, 3] uint8 NHWC tiles (or float32 NCHW [B, 3, tile, tile] already normalised,
+        on the fixed windows).  Returns the (device, un-synchronised) loss tensor.  ``boxes``: (global, local) int32 device tensors
+        from multicrop.MultiCropSampler.sample -- random-resized crops instead of the fixed parity windows."""
+        if input_form(tiles_u8, self.B, (self.tile, self.tile), (("fill", fill), ("boxes", boxes), ("views", views))) == "u8":
+            assert tiles_u8.shape == (self.B, self.tile, self.tile, 3)
         self.set_hyper(**sched)
         self.forward_backward(tiles_u8, boxes=boxes, fill=fill, views=views)
         self.optimizer_step()
@@ -1236,8 +1269,11 @@ class SupervisedEngine:
                 for n in self.arena.specs}
 
     def forward(self, tiles_u8, ema: bool = False, fill=None):
-        """Inference / features: returns (logits f32 [B,C], CLS features bf16 [B,D]); ``ema``: with the EMA weights."""
+        """Inference / features: returns (logits f32 [B,C], CLS features bf16 [B,D]); ``ema``: with the EMA weights.
+        ``tiles_u8``: uint8 NHWC [B, H, W, 3] or float32 NCHW [B, 3, H, W] already normalised (engine.input_form); the
+        image is its top-left img_size window."""
         B, C, D, W = self.B, self.C, self.D, (self.Wema if ema else self.W)
+        input_form(tiles_u8, B, None, (("fill", fill),))
         self.vit.forward(W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats, fill=fill)
         ops.small_matmul(self.feats, W.f("head.weight"), self.logits, B, C, D, sam=D, sak=1, sbk=1, sbn=D, bias=W.f("head.bias"))
         return self.logits, self.feats
@@ -1299,7 +1335,7 @@ class SupervisedEngine:
             self.scaler.update(self.gnorm_sq)
 
     def step(self, tiles_u8, target, lr=None, fill=None):
-        assert tiles_u8.dtype == torch.uint8 and target.dtype == torch.int64
+        assert target.dtype == torch.int64
         self.forward_backward(tiles_u8, target, fill=fill)
         self.optimizer_step(lr)
         return self.loss
@@ -1338,15 +1374,17 @@ class FeatureExtractor:
         self.grp = VitGroup(arch, [(batch, img_size)], img_size, dev, save=False, act=act)
         self.feats = _empty((batch, self.D), act, dev)
         self.logits = _empty((batch, num_classes), f32, dev) if num_classes else None
-        self._pad = None
+        self._pad = self._pad_f32 = None
 
     def load_state(self, state: Dict[str, torch.Tensor]):
         self.arena.load(state)
         ops.cast_bf16(self.arena.p, self.arena.pb)
 
     def forward(self, tiles_u8: torch.Tensor):
-        """tiles_u8 [B, img, img, 3] u8 NHWC -> (CLS features bf16 [B, D], logits f32 [B, C] or None)."""
-        assert tiles_u8.shape == (self.B, self.img, self.img, 3) and tiles_u8.dtype == torch.uint8
+        """tiles_u8 [B, img, img, 3] u8 NHWC, or float32 NCHW [B, 3, img, img] already normalised -> (CLS features bf16 [B, D],
+        logits f32 [B, C] or None)."""
+        if input_form(tiles_u8, self.B, (self.img, self.img)) == "u8":
+            assert tiles_u8.shape == (self.B, self.img, self.img, 3)
         self.vit.forward(self.W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats)
         if self.C:
             ops.small_matmul(self.feats, self.W.f("head.weight"), self.logits, self.B, self.C, self.D, sam=self.D, sak=1, sbk=1, sbn=self.D,
@@ -1354,8 +1392,10 @@ class FeatureExtractor:
         return self.feats, self.logits
 
     def run(self, tiles_u8: torch.Tensor):
-        """Any number of tiles (one chunk of a slide, datasets.py:699-700 ``tiles_per_iter``): batches of B, the last
-        one padded.  -> (features f32 [n, D], logits f32 [n, C] or None), device tensors owned by the caller."""
+        """Any number of tiles (one chunk of a slide, datasets.py:699-700 ``tiles_per_iter``), uint8 NHWC or float32 NCHW as
+        ``forward``: batches of B, the last one padded.  -> (features f32 [n, D], logits f32 [n, C] or None), device tensors
+        owned by the caller."""
+        form = input_form(tiles_u8, None, (self.img, self.img))
         n = tiles_u8.shape[0]
         feats = torch.empty(n, self.D, dtype=f32, device=self.dev)
         logits = torch.empty(n, self.C, dtype=f32, device=self.dev) if self.C else None
@@ -1363,10 +1403,16 @@ class FeatureExtractor:
             hi = min(n, lo + self.B)
             part = tiles_u8[lo:hi]
             if hi - lo < self.B:
-                if self._pad is None:
-                    self._pad = torch.zeros(self.B, self.img, self.img, 3, dtype=torch.uint8, device=self.dev)
-                self._pad[: hi - lo].copy_(part)
-                part = self._pad
+                if form == "u8":
+                    if self._pad is None:
+                        self._pad = torch.zeros(self.B, self.img, self.img, 3, dtype=torch.uint8, device=self.dev)
+                    pad = self._pad
+                else:
+                    if self._pad_f32 is None:
+                        self._pad_f32 = torch.zeros(self.B, 3, self.img, self.img, dtype=f32, device=self.dev)
+                    pad = self._pad_f32
+                pad[: hi - lo].copy_(part)
+                part = pad
             f, l = self.forward(part)
             feats[lo:hi].copy_(f[: hi - lo])
             if logits is not None:

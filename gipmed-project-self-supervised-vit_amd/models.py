@@ -207,12 +207,23 @@ class VitModel:
 
     to = cuda
 
+    @staticmethod
+    def _images(x: torch.Tensor) -> torch.Tensor:
+        # a channels_last float batch (W stride != 1) is made contiguous here: gv_patchify_nchw reads whole rows of W
+        if isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3 and x.stride(-1) != 1:
+            return x.contiguous()
+        return x
+
     def forward_features(self, tiles_u8: torch.Tensor) -> torch.Tensor:
-        return self.engine.forward(tiles_u8)[1]
+        """As ``__call__``, returning the CLS features [batch, embed_dim] (the engine's buffer)."""
+        return self.engine.forward(self._images(tiles_u8))[1]
 
     def __call__(self, tiles_u8: torch.Tensor) -> torch.Tensor:
-        """NHWC uint8 tiles [batch, H, W, 3] already on the device -> logits f32 [batch, num_classes] (the engine's buffer)."""
-        return self.engine.forward(tiles_u8)[0]
+        """Images already on the device -> logits f32 [batch, num_classes] (the engine's buffer).  Either form:
+        NHWC uint8 tiles [batch, H, W, 3] (ToTensor + Normalize fused on the device), or the reference's own ``Data``
+        float32 NCHW [batch, 3, H, W] already normalised (``model(input)``, train.py:1044); a ``channels_last`` float
+        tensor is made contiguous first (one copy).  Anything else raises TypeError."""
+        return self.engine.forward(self._images(tiles_u8))[0]
 
 
 def create_model(model_name: str, pretrained: bool = False, in_chans: int = 3, num_classes: Optional[int] = None,

@@ -79,6 +79,32 @@ def patchify(tiles_u8: torch.Tensor, windows: Sequence[Sequence[int]], crop: int
     return out
 
 
+def patchify_nchw(images_f32: torch.Tensor, windows: Sequence[Sequence[int]], crop: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """images_f32 [n_tiles, 3, H, W] f32 NCHW, already normalised (any N / C / H strides, W stride 1); windows [(y0, x0)] of
+    side ``crop``.  Returns patches [(len(windows) * n_tiles) * (crop/16)^2, 768] in the build's 16-bit format (the value
+    rounded, no mean / std), or exact f32 rows when ``out`` is f32; images crop-major as ``patchify``."""
+    _chk(images_f32, f32, "images")
+    if images_f32.dim() != 4 or images_f32.shape[1] != 3 or images_f32.stride(-1) != 1:
+        raise ValueError(f"images: expected float32 [n, 3, H, W] with W stride 1, got shape {tuple(images_f32.shape)} "
+                         f"strides {images_f32.stride()}")
+    n_tiles, _, H, W = images_f32.shape
+    n_img = n_tiles * len(windows)
+    P = (crop // 16) ** 2
+    if out is None:
+        out = torch.empty(n_img * P, 768, dtype=bf16, device=images_f32.device)
+    sfx = _sfx(out)
+    if out.numel() < n_img * P * 768 or not out.is_contiguous():
+        raise ValueError(f"out: need a contiguous buffer of {n_img * P} x 768, got {tuple(out.shape)}")
+    a = L.gv_patchify_nchw_args()
+    a.images, a.patches, a.n_img, a.n_tiles, a.img_h, a.img_w = images_f32.data_ptr(), out.data_ptr(), n_img, n_tiles, H, W
+    a.stride_n, a.stride_c, a.stride_h = images_f32.stride(0), images_f32.stride(1), images_f32.stride(2)
+    a.n_win, a.crop = len(windows), crop
+    for i, (y, x) in enumerate(windows):
+        a.win_y[i], a.win_x[i] = int(y), int(x)
+    L.call("gv_patchify_nchw" + sfx, a, _stream())
+    return out
+
+
 def crop_resize(tiles_u8: torch.Tensor, boxes: torch.Tensor, out_size: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Random-resized crops on the device: tiles_u8 [n_tiles, H, W, 3] u8, boxes int32 [n, 6] =
     (tile, y0, x0, h, w, flip) on the same device -> u8 [n, out_size, out_size, 3]; see gv_crop_resize."""

@@ -15,6 +15,10 @@ the returned object carries ``device_recipe`` and the driver hands the tiles, on
 byte-exact against oracle/augment_oracle.py, which is pinned against PIL).  Called directly on a host tile the
 object applies only the flips / 90-degree rotations ('flip', 'rvf'); the other recipes have no CPU path.
 The DINO random-resized crops + flips are cut on the device too (gipvit.multicrop.MultiCropSampler + gv_crop_resize).
+
+A user hook may also return what the reference's own hooks return: a float tensor / array [3, H, W] already normalised
+(ToTensor + Normalize, transformations.py:124-128).  ``hook_output_format`` tells the two forms apart; a source whose hook
+returns floats delivers float32 NCHW batches, which the engines take through gv_patchify_nchw (no fused normalise).
 """
 from __future__ import annotations
 
@@ -100,3 +104,35 @@ def define_transformations(transform_type: Union[str, Callable], train: bool, ti
         ops = [_rot90, _vflip]
     return TileTransform(ops, mean, std, tile_size, seed, device_recipe=transform_type if (train and transform_type != "none") else None,
                          color_param=color_param)
+
+
+HOOK_FORMS = "uint8 [tile, tile, 3] (HWC, normalised on the device) or float [3, tile, tile] (CHW, already normalised)"
+
+
+def hook_output_format(out, tile_size: int) -> str:
+    """Batch format implied by one output of a transform hook: ``"u8_nhwc"`` or ``"f32_nchw"``.  Accepts numpy arrays,
+    CPU torch tensors and anything ``np.asarray`` takes (a PIL image); any other dtype or shape raises TypeError."""
+    try:
+        import torch
+        if isinstance(out, torch.Tensor):
+            out = out.detach().cpu().numpy()
+    except ImportError:         # pragma: no cover - torch is a dependency of the package
+        pass
+    a = np.asarray(out)
+    t = tile_size
+    if a.dtype == np.uint8 and a.shape == (t, t, 3):
+        return "u8_nhwc"
+    if np.issubdtype(a.dtype, np.floating) and a.shape == (3, t, t):
+        return "f32_nchw"
+    raise TypeError(f"transform hook returned {a.dtype} {a.shape}: expected {HOOK_FORMS.replace('tile', str(t))}")
+
+
+def hook_output_array(out) -> np.ndarray:
+    """A hook output as a numpy array (CPU torch tensors without a copy where possible)."""
+    try:
+        import torch
+        if isinstance(out, torch.Tensor):
+            return out.detach().cpu().numpy()
+    except ImportError:         # pragma: no cover
+        pass
+    return np.asarray(out)

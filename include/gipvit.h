@@ -75,6 +75,22 @@ typedef struct {
 } gv_patchify_args;
 int gv_patchify(const gv_patchify_args* a, void* stream);
 
+/* ---- patchify_nchw: the same patch rows from the reference's own hot-path input, Data [B, 3, H, W] float32 ALREADY
+ * normalised by ToTensor + Normalize (train.py:1027-1033, datasets.py:614-621, transformations.py:124-128), or a
+ * user hook's FloatTensor[3, H, W] (transformations.py:199-200).  No mean / std: each value is only rounded to the
+ * build's 16-bit format, round-to-nearest-even (bit-identical to torch's .to(bfloat16) / .to(float16) for finite
+ * input; NaN stays NaN, +-Inf stays +-Inf).  Windows may start at any pixel; strides let a slice of a larger batch in
+ * without a copy.  Same image order, rows and column order k = c*256 + py*16 + px as gv_patchify. */
+typedef struct {
+    const float* images;          /* [n_tiles, 3, img_h, img_w] f32, strides below (elements); the W stride is 1 */
+    void* patches;                /* 16-bit (f32 for _f32) [n_img * (crop/16)^2, 768], 16-byte aligned          */
+    int32_t n_img, n_tiles, img_h, img_w;
+    int64_t stride_n, stride_c, stride_h;
+    /* image index i -> tile i % n_tiles, window i / n_tiles (crop-major); crop multiple of 16 */
+    int32_t n_win, win_y[16], win_x[16], crop;
+} gv_patchify_nchw_args;
+int gv_patchify_nchw(const gv_patchify_nchw_args* a, void* stream);
+
 /* ---- random-resized crops of the tiles (DINO multi-crop input stage; absent from the
  * reference, whose tiles are augmented on the CPU by transformations.py:103-209 -- SURVEY 8f rank 1).
  * For crop n: box (y0, x0, h, w) of tile `tile` is resampled to out_size x out_size with
@@ -613,6 +629,7 @@ int gv_attention_bwd_f32(const gv_attention_bwd_args* a, void* stream);
 int gv_layernorm_fwd_f32(const gv_layernorm_fwd_args* a, void* stream);
 int gv_layernorm_bwd_f32(const gv_layernorm_bwd_args* a, void* stream);
 int gv_patchify_f32(const gv_patchify_args* a, void* stream);
+int gv_patchify_nchw_f32(const gv_patchify_nchw_args* a, void* stream);    /* exact copy into f32 patch rows */
 int gv_tokens_bwd_f32(const gv_tokens_bwd_args* a, void* stream);
 /* DINO head: zn / dz (l2norm), the weight-normalised last-layer matrix, and the student-logit gradient as f32 */
 int gv_l2norm_fwd_f32(const gv_l2norm_fwd_args* a, void* stream);

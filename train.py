@@ -211,9 +211,39 @@ def teacher_temp_at(args, epoch: int) -> float:
     return args.warmup_teacher_temp + (args.teacher_temp - args.warmup_teacher_temp) * epoch / (n - 1)
 
 
-def main(argv=None):
+def hook_batch_format(args, transform, argv=None) -> str:
+    """Batch format a caller's transform hook (``main(transform=...)``) implies, found before any GPU work by calling it on
+    the first tile of the dataset: "u8_nhwc" or "f32_nchw" (the reference's normalised FloatTensor[3, H, W],
+    transformations.py:199-200).  Float batches skip the uint8 pipeline, so what only exists there is refused here."""
+    from gipvit import data as D, transformations as T
+    if args.dataset in ("", "synthetic") or not (args.dataset.startswith("tiles:") or args.data_dir):
+        raise SystemExit("main(transform=...): the hook transforms tiles read from disk -- pass --dataset tiles:<dir> (or --data_dir)")
+    if isinstance(transform, T.TileTransform):
+        return "u8_nhwc"
+    root = args.dataset[6:] if args.dataset.startswith("tiles:") else args.data_dir
+    fmt = D.probe_hook_format(D.scan_slides(root, args.target), transform, args.tile_size)
+    if fmt == "f32_nchw":
+        why = "the transform hook returns float32 [3, H, W] images (already normalised)"
+        if args.random_crops:
+            raise SystemExit(f"--random-crops: {why}; random-resized crops are cut from uint8 tiles on the device -- "
+                             "run the fixed crop windows (drop the flag) or return uint8 [H, W, 3] tiles from the hook")
+        if args.view_augment:
+            raise SystemExit(f"--view-augment: {why}; the per-crop view augmentation works on uint8 tiles on the device")
+        given = sys.argv[1:] if argv is None else list(argv)
+        if any(a == "--transform_type" or a.startswith("--transform_type=") for a in given) and args.transform_type in T.DEVICE_RECIPES:
+            raise SystemExit(f"--transform_type {args.transform_type}: {why}; the named recipes augment uint8 tiles on the device "
+                             "and the hook replaces them -- drop the flag")
+    return fmt
+
+
+def main(argv=None, transform=None):
+    """``transform``: a custom augmentation hook in place of ``--transform_type`` (the reference's "any callable is the
+    transform", transformations.py:199-200), applied by the tile reader threads.  It maps a uint8 [H, W, 3] tile to a uint8
+    tile of the same form, or to a float [3, H, W] image already normalised -- then the batches are float32 NCHW, no
+    device augmentation runs, and --random-crops / --view-augment / a named --transform_type are refused."""
     args, args_text = parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
+    hook_format = hook_batch_format(args, transform, argv) if transform is not None else None
     if not torch.cuda.is_available() or not str(args.device).startswith("cuda"):
         raise SystemExit("train.py: an MI355X is required (device=%s, cuda available=%s); the HIP hot path has no CPU fallback"
                          % (args.device, torch.cuda.is_available()))
@@ -267,13 +297,16 @@ def main(argv=None):
 
     # ---- data (batch dict contract of the reference: 'Data', 'Target'; inference: Infer_Dataset's dict)
     synthetic = args.dataset in ("", "synthetic")
-    transform = T.define_transformations(args.transform_type if not synthetic else "none", True, tile, args.c_param, "Ron")
+    transform = T.define_transformations(transform if transform is not None else args.transform_type if not synthetic else "none", True, tile,
+                                         args.c_param, "Ron")
     # the named recipes run on the DEVICE once the tiles are in HBM (gv_augment); the reader threads then deliver raw tiles
     augmenter = None
     if getattr(transform, "device_recipe", None):
         from gipvit.augment import TileAugmenter
         augmenter = TileAugmenter(transform.device_recipe, tile, transform.color_param, mean, std, seed=args.seed + 31 * rank, device=dev)
         transform = None
+    if hook_format == "f32_nchw" and primary:
+        _logger.info("transform hook returns float32 [3, H, W]: batches are float32 NCHW, patchified without the fused normalise")
     inf_loader = None
     if synthetic:
         source = D.SyntheticTiles(B, tile, args.batches_per_epoch, args.num_classes or 2, seed=args.seed + rank)
