@@ -538,7 +538,123 @@ int launch_fwd_any(const gv_attention_fwd_args* a, hipStream_t s) {
     return launch_fwd<18>(a, s);
 }
 
+// ---------------------------------------------------------------------------------
+// attention probabilities (get_last_selfattention, vit.pyc@L255-262): P = exp(scale q.k - lse[q]) with the forward's lse,
+// one pass, no row reduction.  S = Q K^T with queries on MFMA rows and keys on lanes: for a fixed (g, r) the 16 lanes li hold
+// 16 consecutive keys of one query row, so each store instruction writes 4 rows x 64 contiguous bytes with 4-byte stores --
+// P rows start anywhere (N = 257: 1 028-byte rows), nothing is assumed about their alignment.  Each element is computed and
+// stored as soon as its MFMA tile is done: no score registers are held across key tiles.
+// ---------------------------------------------------------------------------------
+constexpr float LOG2E = 1.4426950408889634f;
+
+// one 16-query tile of one (image, head) pair against every key tile; kf(kt, ks) returns the K fragment of key row kt*16 + li.
+// UNR: key tiles unrolled (NKT where the fragments sit in registers; 2 where they come from LDS: fully unrolled, the LDS reads
+// of every tile are hoisted and 172 registers leave 2 waves per SIMD)
+template <int NKT, int UNR, class KF>
+__device__ __forceinline__ void probs_tile(const gv_attention_probs_args& a, const bf16* qbase, long ld, long pair, int q0, int li, int g, KF&& kf) {
+    const int N = a.N, QR = a.q_rows;
+    int qrow = q0 + li;
+    qrow = qrow < QR ? qrow : QR - 1;
+    bf16x8 qf[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) qf[ks] = *(const bf16x8*)(qbase + (long)qrow * ld + ks * 32 + g * 8);
+    // rows of this lane's accumulator: q0 + 4g + r; lse rows >= q_rows are never read
+    float nl[4];
+    bool qok[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int q = q0 + 4 * g + r;
+        qok[r] = q < QR;
+        nl[r] = -a.lse[pair * N + (qok[r] ? q : QR - 1)] * LOG2E;
+    }
+    const float c = a.scale * LOG2E;
+    float* prow = a.p + (pair * QR + q0 + 4 * g) * (long)N;
+#pragma unroll UNR
+    for (int kt = 0; kt < NKT; ++kt) {
+        f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) s = MFMA16(qf[ks], kf(kt, ks), s);
+        const int key = kt * 16 + li;
+        if (key < N) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (qok[r]) prow[(long)r * N + key] = __builtin_amdgcn_exp2f(fmaf(s[r], c, nl[r]));
+        }
+    }
+}
+
+// all query rows: one workgroup per (image, head) pair, K staged once into the swizzled LDS image by LDS-DMA, the pair's
+// 16-query tiles spread over the waves
+template <int NKT>
+__global__ __launch_bounds__(256) void attn_probs_kernel(gv_attention_probs_args a) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    GV_LDS char* Kimg = (GV_LDS char*)smem_raw;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+    const int N = a.N, H = a.H;
+    const long ld = 3L * H * 64, pair = blockIdx.x;
+    const int img = (int)(pair / H), h = (int)(pair - (long)img * H);
+    const bf16* qbase = (const bf16*)a.qkv + (long)img * N * ld + h * 64;
+    stage_rows(qbase + H * 64, ld, N, NKT * 16, Kimg, wave, nw, lane);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const int li = lane & 15, g = lane >> 4;
+    const int n_qt = (a.q_rows + 15) >> 4;
+    for (int qt = wave; qt < n_qt; qt += nw)
+        probs_tile<NKT, 2>(a, qbase, ld, pair, qt * 16, li, g, [&](int kt, int ks) { return read_nat(Kimg, kt * 16 + li, ks * 4 + g); });
+}
+
+// q_rows <= 16 (the CLS row): a GEMV per pair -- one wave per pair, K fragments straight from global (every K element is read
+// once), all of them issued before the first MFMA
+template <int NKT>
+__global__ __launch_bounds__(256) void attn_probs_row_kernel(gv_attention_probs_args a, int n_pairs) {
+    const int lane = threadIdx.x & 63;
+    const long pair = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pair >= n_pairs) return;
+    const int N = a.N, H = a.H;
+    const long ld = 3L * H * 64;
+    const int img = (int)(pair / H), h = (int)(pair - (long)img * H);
+    const bf16* qbase = (const bf16*)a.qkv + (long)img * N * ld + h * 64;
+    const int li = lane & 15, g = lane >> 4;
+    bf16x8 kreg[NKT][2];
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+        int key = kt * 16 + li;
+        key = key < N ? key : N - 1;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) kreg[kt][ks] = *(const bf16x8*)(qbase + H * 64 + (long)key * ld + ks * 32 + g * 8);
+    }
+    probs_tile<NKT, NKT>(a, qbase, ld, pair, 0, li, g, [&](int kt, int ks) { return kreg[kt][ks]; });
+}
+
+template <int NKT> int launch_probs(const gv_attention_probs_args* a, hipStream_t s) {
+    const int n_pairs = a->n_img * a->H;
+    if (a->q_rows <= 16) {
+        hipLaunchKernelGGL(attn_probs_row_kernel<NKT>, dim3((n_pairs + 3) / 4), dim3(256), 0, s, *a, n_pairs);
+    } else {
+        constexpr int LDS = NKT * 16 * 128;
+        static GvLdsOptIn opt_in;
+        if (int rc = gv_lds_opt_in(opt_in, (const void*)attn_probs_kernel<NKT>, LDS, "gv_attention_probs")) return rc;
+        const int n_qt = (a->q_rows + 15) / 16, nw = n_qt < 4 ? n_qt : 4;
+        hipLaunchKernelGGL(attn_probs_kernel<NKT>, dim3(n_pairs), dim3(nw * 64), LDS, s, *a);
+    }
+    GV_LAUNCH_CHECK("gv_attention_probs");
+    return GV_OK;
+}
+
 }  // namespace
+
+extern "C" int gv_attention_probs(const gv_attention_probs_args* a, void* stream) {
+    GV_REQUIRE(a && a->qkv && a->lse && a->p, GV_E_NULL, "gv_attention_probs: null pointer");
+    GV_REQUIRE(a->n_img > 0 && a->H > 0 && a->N > 0 && a->N <= 288, GV_E_SHAPE, "gv_attention_probs: need n_img > 0, H > 0, 0 < N <= 288 (got N = %d)", a->N);
+    GV_REQUIRE(a->q_rows >= 1 && a->q_rows <= a->N, GV_E_SHAPE, "gv_attention_probs: need 1 <= q_rows <= N (got q_rows = %d, N = %d)", a->q_rows, a->N);
+    GV_REQUIRE(gv_aligned(a->qkv, 16), GV_E_ALIGN, "gv_attention_probs: qkv must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (a->N <= 32) return launch_probs<2>(a, s);
+    if (a->N <= 64) return launch_probs<4>(a, s);
+    if (a->N <= 128) return launch_probs<8>(a, s);
+    if (a->N <= 224) return launch_probs<14>(a, s);
+    return launch_probs<18>(a, s);
+}
 
 extern "C" int gv_attention_fwd_varlen(const gv_attention_fwd_varlen_args* v, void* stream) {
     GV_REQUIRE(v && v->qkv && v->o, GV_E_NULL, "gv_attention_fwd_varlen: null pointer");

@@ -357,6 +357,29 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_f32_kernel(gv_attention_bwd_
     }
 }
 
+// attention probabilities (gv_attention_probs_f32): P = exp(scale q.k - lse[q]) with the forward's lse.  One (image, head) pair x
+// 4 query rows per workgroup, K staged as above; a wave takes one query row, lane j the keys j, j + 64, ...
+__global__ __launch_bounds__(256) void attn_probs_f32_kernel(gv_attention_probs_args a) {
+    extern __shared__ float sm[];
+    const int N = a.N, H = a.H, QR = a.q_rows, pair = blockIdx.x, img = pair / H, h = pair % H, D3 = 3 * H * 64;
+    float* Ks = sm;
+    float* Qw = Ks + N * ALD;          // [4][64]
+    const float* base = (const float*)a.qkv + (long)img * N * D3 + h * 64;
+    stage_rows(Ks, base + H * 64, D3, N);
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, q = blockIdx.y * 4 + w;
+    const bool ok = q < QR;
+    Qw[w * 64 + lane] = ok ? base[(long)q * D3 + lane] : 0.f;
+    __syncthreads();
+    if (!ok) return;
+    const float lse = a.lse[(long)pair * N + q];
+    float* prow = a.p + ((long)pair * QR + q) * N;
+    for (int j = lane; j < N; j += 64) {
+        float s = 0.f;
+        for (int d = 0; d < 64; ++d) s = fmaf(Qw[w * 64 + d], Ks[j * ALD + d], s);
+        prow[j] = expf(s * a.scale - lse);
+    }
+}
+
 template <typename Kern> int set_lds(Kern kern, int bytes, const char* name) {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e != hipSuccess) { gv_set_error("%s: hipFuncSetAttribute(%d): %s", name, bytes, hipGetErrorString(e)); return (int)e; }
@@ -438,5 +461,18 @@ extern "C" int gv_attention_bwd_f32(const gv_attention_bwd_args* a, void* stream
     hipLaunchKernelGGL(attn_bwd_dq_f32_kernel, grid, dim3(256), lds_q, (hipStream_t)stream, *a);
     hipLaunchKernelGGL(attn_bwd_dkv_f32_kernel, grid, dim3(256), lds_kv, (hipStream_t)stream, *a);
     GV_LAUNCH_CHECK("gv_attention_bwd_f32");
+    return GV_OK;
+}
+
+extern "C" int gv_attention_probs_f32(const gv_attention_probs_args* a, void* stream) {
+    GV_REQUIRE(a && a->qkv && a->lse && a->p, GV_E_NULL, "gv_attention_probs_f32: null pointer");
+    GV_REQUIRE(a->n_img > 0 && a->H > 0 && a->N > 0 && a->N <= AMAXN, GV_E_SHAPE, "gv_attention_probs_f32: need n_img > 0, H > 0, 0 < N <= %d (got N = %d)", AMAXN, a->N);
+    GV_REQUIRE(a->q_rows >= 1 && a->q_rows <= a->N, GV_E_SHAPE, "gv_attention_probs_f32: need 1 <= q_rows <= N (got q_rows = %d, N = %d)", a->q_rows, a->N);
+    GV_REQUIRE(gv_aligned(a->qkv, 16), GV_E_ALIGN, "gv_attention_probs_f32: qkv must be 16-byte aligned");
+    const int lds = (a->N * ALD + 4 * 64) * 4;
+    int rc = set_lds(attn_probs_f32_kernel, lds, "gv_attention_probs_f32");
+    if (rc != GV_OK) return rc;
+    hipLaunchKernelGGL(attn_probs_f32_kernel, dim3(a->n_img * a->H, (a->q_rows + 3) / 4), dim3(256), lds, (hipStream_t)stream, *a);
+    GV_LAUNCH_CHECK("gv_attention_probs_f32");
     return GV_OK;
 }

@@ -400,6 +400,20 @@ class VitGroup:
         return i if self.save else 0
 
 
+@dataclasses.dataclass
+class Capture:
+    """Extra outputs of one forward-only pass (``VitRunner.forward(capture=...)``; the reference's get_last_selfattention /
+    get_intermediate_layers, vit.pyc@L255-272), written into caller buffers on the pass's stream.  ``attn``: f32 [n_img, H,
+    attn_rows, N], the last block's softmax for query rows 0..attn_rows-1 (1 = the CLS row: the pass keeps its CLS-only tail and
+    q_limit; more rows run that block's attention for every query).  ``tokens``: n f32 [T, D] buffers, the final norm over every
+    token after each of the last n blocks (the CLS-only tail is off for that pass); ``stats``: f32 [2, T] scratch for their
+    LayerNorm statistics.  One segment (single-crop groups) only."""
+    attn: Optional[torch.Tensor] = None
+    attn_rows: int = 1
+    tokens: Sequence[torch.Tensor] = ()
+    stats: Optional[torch.Tensor] = None
+
+
 class VitRunner:
     def __init__(self, arch: str, img_size: int, device, fp32: bool = False, sw: Optional[EngineSwitches] = None):
         """``sw``: the switches of the engine that owns this runner (read from the environment when not given)."""
@@ -436,14 +450,24 @@ class VitRunner:
         self._events: List[torch.cuda.Event] = []
 
     # ---- forward: tiles -> CLS features written into feats[row_off + seg.img0 ...]
-    def forward(self, W: Weights, G: VitGroup, tiles_u8, windows, mean, std, feats, row_off: int = 0, fill=None, on_side: bool = False):
+    def forward(self, W: Weights, G: VitGroup, tiles_u8, windows, mean, std, feats, row_off: int = 0, fill=None, on_side: bool = False,
+                capture: Optional[Capture] = None):
         """windows: one list of (y0, x0) crop origins per segment; tiles_u8: one NHWC u8 tensor for all
         segments, or one per segment (pre-cut crops: each with the single window (0, 0)).  A float32 NCHW source (already
         normalised, engine.input_form) goes through gv_patchify_nchw instead, without mean / std.  ``fill``: per-tile normalised
         fill boxes of the augmentation (gipvit.augment: Cutout after Normalize, MeanPixelRegularization), f32 [n_tiles, 8].
         ``on_side``: the call is queued on the side stream (the teacher beside the student): its split-K products take that
-        stream's scratch."""
+        stream's scratch.  ``capture``: extra outputs of a forward-only pass (``Capture``); None issues exactly the default launches."""
         D, T, H = self.D, G.T, self.H
+        cap = capture
+        if cap is not None:
+            assert not G.save and len(G.segs) == 1, "capture: forward-only single-crop groups"
+        tok0 = self.depth - len(cap.tokens) if cap is not None else self.depth        # first block whose normed tokens are captured
+        cls_tail = self._cls_tail(G) and tok0 == self.depth
+        all_q = cap is not None and cap.attn is not None and cap.attn_rows > 1
+
+        def capture_tokens(i, xc):
+            ops.layernorm_fwd(xc, W.f("norm.weight"), W.f("norm.bias"), T, D, y=cap.tokens[i - tok0], mean=cap.stats[0], rstd=cap.stats[1])
         E = L
         pos_full = W.f("pos_embed").view(-1, D)
         x0 = G.xbuf(0)
@@ -483,7 +507,7 @@ class VitRunner:
                 ops.layernorm_fwd(xa, W.f(b + "norm1.weight"), W.f(b + "norm1.bias"), T, D, y=G.xn1[s], mean=st[0], rstd=st[1])
             ops.linear(G.xn1[s], W.w(b + "attn.qkv.weight"), G.qkv[s], T, 3 * D, D, epilogue=E.EPI_BIAS, bias=W.f(b + "attn.qkv.bias"))
             # the last block under the CLS-only tail: only the CLS query's attention output is used (row 0 of every image)
-            ql = 1 if (self._cls_tail(G) and i == self.depth - 1 and self.sw.cls_qlimit) else 0
+            ql = 1 if (cls_tail and i == self.depth - 1 and self.sw.cls_qlimit and not all_q) else 0
             if len(G.segs) > 1 and self.sw.varlen_attn:
                 # the crop lengths of a multi-crop pass in ONE call (gv_attention_fwd_varlen: the 37-token pairs fill the 197-token
                 # launch's half-empty last round); GIPVIT_VARLEN_ATTN=0 keeps one launch per segment for A/B runs
@@ -491,7 +515,10 @@ class VitRunner:
             else:
                 for sg in G.segs:
                     ops.attention_fwd(sg.rows(G.qkv[s]), sg.n_img, sg.N, H, self.scale, o=sg.rows(G.o[s]), lse=sg.lse[s], q_limit=ql)
-            if self._cls_tail(G) and i == self.depth - 1:
+            if cap is not None and cap.attn is not None and i == self.depth - 1:
+                sg = G.segs[0]
+                ops.attention_probs(G.qkv[s], sg.lse[s], sg.n_img, sg.N, H, self.scale, cap.attn_rows, p=cap.attn)
+            if cls_tail and i == self.depth - 1:
                 self._last_block_tail_fwd(W, G, i, xa, on_side)
                 break
             if fused:
@@ -514,6 +541,8 @@ class VitRunner:
                                bias2=W.f(b + "mlp.fc2.bias"), resid=xb, gamma=W.f(nb + "norm1.weight") if nxt else None,
                                beta=W.f(nb + "norm1.bias") if nxt else None, y=G.xn1[ns] if nxt else None,
                                mean=G.stats[ns][0] if nxt else None, rstd=G.stats[ns][1] if nxt else None, row_scale=rs_m)
+                if i >= tok0:
+                    capture_tokens(i, xc)
                 continue
             ops.linear(G.xn2[s], W.w(b + "mlp.fc1.weight"), G.h[s], T, 4 * D, D,
                        epilogue=E.EPI_BIAS | E.EPI_GELU | (E.EPI_SAVE_PRE if G.save else 0),   # a forward-only group keeps no pre-activation
@@ -533,10 +562,12 @@ class VitRunner:
             else:
                 ops.linear(G.h[s], W.w(b + "mlp.fc2.weight"), xc, T, D, 4 * D, epilogue=E.EPI_BIAS | E.EPI_RESID,
                            bias=W.f(b + "mlp.fc2.bias"), resid=xb, row_scale=rs_m)
+            if i >= tok0:
+                capture_tokens(i, xc)
         xl = G.xbuf(2 * self.depth)
         for sg in G.segs:
             r0 = row_off + sg.img0
-            if self._cls_tail(G):         # the last block left its output for the CLS rows only, contiguous
+            if cls_tail:         # the last block left its output for the CLS rows only, contiguous
                 ops.layernorm_fwd(G.c_xc[sg.img0:sg.img0 + sg.n_img], W.f("norm.weight"), W.f("norm.bias"), sg.n_img, D,
                                   y=feats[r0:r0 + sg.n_img], mean=sg.fstats[0], rstd=sg.fstats[1])
             else:
@@ -1375,30 +1406,28 @@ class FeatureExtractor:
         self.feats = _empty((batch, self.D), act, dev)
         self.logits = _empty((batch, num_classes), f32, dev) if num_classes else None
         self._pad = self._pad_f32 = None
+        self._scratch: Dict[str, torch.Tensor] = {}      # capture buffers of a padded last batch (_out_or_scratch)
+        self._tok_stats = None                             # f32 [2, T]: LayerNorm statistics of captured tokens
 
     def load_state(self, state: Dict[str, torch.Tensor]):
         self.arena.load(state)
         ops.cast_bf16(self.arena.p, self.arena.pb)
 
-    def forward(self, tiles_u8: torch.Tensor):
+    def forward(self, tiles_u8: torch.Tensor, capture: Optional[Capture] = None):
         """tiles_u8 [B, img, img, 3] u8 NHWC, or float32 NCHW [B, 3, img, img] already normalised -> (CLS features bf16 [B, D],
-        logits f32 [B, C] or None)."""
+        logits f32 [B, C] or None).  ``capture``: attention / token outputs of the same pass (``Capture``)."""
         if input_form(tiles_u8, self.B, (self.img, self.img)) == "u8":
             assert tiles_u8.shape == (self.B, self.img, self.img, 3)
-        self.vit.forward(self.W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats)
+        self.vit.forward(self.W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats, capture=capture)
         if self.C:
             ops.small_matmul(self.feats, self.W.f("head.weight"), self.logits, self.B, self.C, self.D, sam=self.D, sak=1, sbk=1, sbn=self.D,
                              bias=self.W.f("head.bias"))
         return self.feats, self.logits
 
-    def run(self, tiles_u8: torch.Tensor):
-        """Any number of tiles (one chunk of a slide, datasets.py:699-700 ``tiles_per_iter``), uint8 NHWC or float32 NCHW as
-        ``forward``: batches of B, the last one padded.  -> (features f32 [n, D], logits f32 [n, C] or None), device tensors
-        owned by the caller."""
+    def _batches(self, tiles_u8: torch.Tensor):
+        """(lo, hi, batch) over any number of tiles: batches of B, the last one padded (its rows >= hi - lo are zeros)."""
         form = input_form(tiles_u8, None, (self.img, self.img))
         n = tiles_u8.shape[0]
-        feats = torch.empty(n, self.D, dtype=f32, device=self.dev)
-        logits = torch.empty(n, self.C, dtype=f32, device=self.dev) if self.C else None
         for lo in range(0, n, self.B):
             hi = min(n, lo + self.B)
             part = tiles_u8[lo:hi]
@@ -1413,8 +1442,80 @@ class FeatureExtractor:
                     pad = self._pad_f32
                 pad[: hi - lo].copy_(part)
                 part = pad
-            f, l = self.forward(part)
+            yield lo, hi, part
+
+    def run(self, tiles_u8: torch.Tensor):
+        """Any number of tiles (one chunk of a slide, datasets.py:699-700 ``tiles_per_iter``), uint8 NHWC or float32 NCHW as
+        ``forward``: batches of B, the last one padded.  -> (features f32 [n, D], logits f32 [n, C] or None), device tensors
+        owned by the caller."""
+        return self._run(tiles_u8, None)
+
+    def run_with_attention(self, tiles_u8: torch.Tensor):
+        """As ``run``, plus the CLS query's attention over every token in the last block, from the same forward (one extra small
+        launch per batch) -> (features, logits, attention f32 [n, H, N]).  ``attention[:, :, 1:]`` reshaped to
+        (img / 16, img / 16) is DINO's attention map of each head."""
+        self._check_size(tiles_u8)
+        attn = torch.empty(tiles_u8.shape[0], self.vit.H, self.grp.segs[0].N, dtype=f32, device=self.dev)
+        feats, logits = self._run(tiles_u8, attn)
+        return feats, logits, attn
+
+    def _run(self, tiles_u8, attn):
+        n = tiles_u8.shape[0]
+        feats = torch.empty(n, self.D, dtype=f32, device=self.dev)
+        logits = torch.empty(n, self.C, dtype=f32, device=self.dev) if self.C else None
+        for lo, hi, part in self._batches(tiles_u8):
+            cap = None if attn is None else Capture(attn=self._out_or_scratch(attn, lo, hi, "_cls_attn"), attn_rows=1)
+            f, l = self.forward(part, cap)
             feats[lo:hi].copy_(f[: hi - lo])
             if logits is not None:
                 logits[lo:hi].copy_(l[: hi - lo])
+            if cap is not None and hi - lo < self.B:
+                attn[lo:hi].copy_(cap.attn[: hi - lo])
         return feats, logits
+
+    def _out_or_scratch(self, out: torch.Tensor, lo: int, hi: int, name: str) -> torch.Tensor:
+        """The capture buffer of batch [lo, hi): the output rows themselves when the batch is full, else a B-row scratch (kept)."""
+        if hi - lo == self.B:
+            return out[lo:hi]
+        buf = self._scratch.get(name)
+        if buf is None or buf.shape[1:] != out.shape[1:]:
+            buf = self._scratch[name] = torch.empty((self.B,) + tuple(out.shape[1:]), dtype=out.dtype, device=self.dev)
+        return buf
+
+    def _check_size(self, tiles_u8: torch.Tensor):
+        form = input_form(tiles_u8, None, (self.img, self.img))       # (float32 NCHW of another size: ValueError there)
+        if form == "u8" and tuple(tiles_u8.shape[1:3]) != (self.img, self.img):
+            raise ValueError(f"images: expected {self.img} x {self.img} tiles, got {tuple(tiles_u8.shape[1:3])} (no pos-embed "
+                             "interpolation at inference)")
+
+    def last_selfattention(self, tiles_u8: torch.Tensor, cls_only: bool = False) -> torch.Tensor:
+        """The reference's get_last_selfattention (vit.pyc@L255-262) over any number of tiles (batched and padded as ``run``):
+        the last block's softmax attention f32 [n, H, N, N], or only the CLS query's row, [n, H, 1, N], with ``cls_only``."""
+        self._check_size(tiles_u8)
+        N, H = self.grp.segs[0].N, self.vit.H
+        q = 1 if cls_only else N
+        out = torch.empty(tiles_u8.shape[0], H, q, N, dtype=f32, device=self.dev)
+        for lo, hi, part in self._batches(tiles_u8):
+            buf = self._out_or_scratch(out, lo, hi, "_attn_buf")
+            self.forward(part, Capture(attn=buf, attn_rows=q))
+            if hi - lo < self.B:
+                out[lo:hi].copy_(buf[: hi - lo])
+        return out
+
+    def intermediate_layers(self, tiles_u8: torch.Tensor, n: int = 1) -> List[torch.Tensor]:
+        """The reference's get_intermediate_layers (vit.pyc@L264-272) over any number of tiles: ``norm(x)`` over every token after
+        each of the last ``n`` blocks, in block order -- a list of n f32 [n_tiles, N, D]."""
+        self._check_size(tiles_u8)
+        if not 1 <= n <= self.vit.depth:
+            raise ValueError(f"intermediate_layers: n = {n}, need 1 <= n <= depth = {self.vit.depth}")
+        N, D, T = self.grp.segs[0].N, self.D, self.grp.T
+        outs = [torch.empty(tiles_u8.shape[0], N, D, dtype=f32, device=self.dev) for _ in range(n)]
+        if self._tok_stats is None:
+            self._tok_stats = torch.empty(2, T, dtype=f32, device=self.dev)
+        for lo, hi, part in self._batches(tiles_u8):
+            bufs = [self._out_or_scratch(o, lo, hi, f"_tok_buf{k}") for k, o in enumerate(outs)]
+            self.forward(part, Capture(tokens=[b.view(T, D) for b in bufs], stats=self._tok_stats))
+            if hi - lo < self.B:
+                for o, b in zip(outs, bufs):
+                    o[lo:hi].copy_(b[: hi - lo])
+        return outs

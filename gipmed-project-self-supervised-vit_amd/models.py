@@ -155,6 +155,7 @@ class VitModel:
         self._params = OrderedDict((n, Param(n, a.view(a.p, n))) for n in a.specs)
         self.head = _Head(self._params["head.weight"], self._params["head.bias"])
         self.training = True
+        self._fx = None           # forward-only runner over the engine's live weights (get_last_selfattention / get_intermediate_layers)
 
     def parameters(self):
         return iter(self._params.values())
@@ -217,6 +218,25 @@ class VitModel:
     def forward_features(self, tiles_u8: torch.Tensor) -> torch.Tensor:
         """As ``__call__``, returning the CLS features [batch, embed_dim] (the engine's buffer)."""
         return self.engine.forward(self._images(tiles_u8))[1]
+
+    def _extractor(self):
+        """A ``FeatureExtractor`` over the engine's live weights (fp32 mode follows the engine), built on first use.  Its own
+        forward-only activations: the training group's saved activations are never touched."""
+        if self._fx is None:
+            from .engine import FeatureExtractor
+            e = self.engine
+            self._fx = FeatureExtractor(self.arch, e.img, e.B, 0, e.mean, e.std, e.dev, weights=e.W)
+        return self._fx
+
+    def get_last_selfattention(self, x: torch.Tensor) -> torch.Tensor:
+        """vit.pyc@L255-262: blocks[:-1], then the last block's softmax attention -> f32 [batch, num_heads, N, N].  Evaluation
+        semantics (no stochastic depth, no dropout: the reference under ``model.eval()``); any batch size; images of img_size."""
+        return self._extractor().last_selfattention(self._images(x))
+
+    def get_intermediate_layers(self, x: torch.Tensor, n: int = 1):
+        """vit.pyc@L264-272: ``norm(x)`` over every token after each of the last ``n`` blocks -> a list of n f32 [batch, N,
+        embed_dim], in block order.  Evaluation semantics as ``get_last_selfattention``."""
+        return self._extractor().intermediate_layers(self._images(x), n)
 
     def __call__(self, tiles_u8: torch.Tensor) -> torch.Tensor:
         """Images already on the device -> logits f32 [batch, num_classes] (the engine's buffer).  Either form:

@@ -275,6 +275,23 @@ def attention_fwd(qkv, n_img: int, N: int, H: int, scale: float, o=None, lse=Non
     return o, lse
 
 
+def attention_probs(qkv, lse, n_img: int, N: int, H: int, scale: float, q_rows: int, p=None):
+    """The softmax matrix of the attention that ``attention_fwd`` computed from the same ``qkv`` and left ``lse`` for:
+    f32 [n_img, H, q_rows, N], query rows 0..q_rows-1 of every image (1 = the CLS row; lse must be valid for them); see
+    gv_attention_probs.  ``p``: a caller buffer of that many elements (contiguous), written in place."""
+    if p is None:
+        p = torch.empty(n_img, H, q_rows, N, dtype=f32, device=qkv.device)
+    if p.dtype != f32 or lse.dtype != f32:
+        raise TypeError(f"attention_probs: p and lse must be float32, got {p.dtype} / {lse.dtype}")
+    if not p.is_contiguous() or p.numel() != n_img * H * q_rows * N:
+        raise ValueError(f"attention_probs: p must be a contiguous buffer of {n_img} x {H} x {q_rows} x {N}, got {tuple(p.shape)}")
+    if qkv.numel() < n_img * N * 3 * H * 64 or lse.numel() < n_img * H * N:
+        raise ValueError("attention_probs: qkv / lse are smaller than n_img * N rows")
+    a = L.gv_attention_probs_args(qkv.data_ptr(), lse.data_ptr(), p.data_ptr(), n_img, N, H, scale, q_rows)
+    L.call("gv_attention_probs" + _sfx(qkv), a, _stream())
+    return p
+
+
 def attention_fwd_varlen(qkv, o, segments, H: int, scale: float, q_limit: int = 0):
     """All segments of a token-concatenated row space in one call: ``segments`` = [(n_img, N, lse f32 [n_img, H, N]), ...] in row
     order; qkv [T, 3 H 64], o [T, H 64].  bf16: gv_attention_fwd_varlen (a long + a short segment share ONE launch); the fp32

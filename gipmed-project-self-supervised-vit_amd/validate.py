@@ -8,7 +8,9 @@ double softmax of train.py:1046/1053) -> top-1 / top-5 (train.py:1250).  When a 
 (``'Is Last Batch'``), its tile scores are appended to the per-patch pool and their mean becomes the slide score
 (train.py:1288-1293); AUC per patch and per slide at the end (train.py:1334-1343).  With ``extract_features`` the
 slide's CLS features are written to ``<out_dir>/<slide>_features.pt`` instead (train.py:1281-1282; 384-d for
-ViT-S, train.py:1203).
+ViT-S, train.py:1203), and with ``extract_attention`` also ``<out_dir>/<slide>_attention.pt``: f32 [n_tiles, H, N], the CLS
+query's attention over every token in the last block (get_last_selfattention's row 0, vit.pyc@L255-262), computed in the same
+forward as the features; ``[:, :, 1:]`` reshaped to (img / 16, img / 16) is DINO's attention map of each head.
 
 Deviations from the reference, all deliberate: a slide is closed when its LAST chunk arrives --
 the reference also closes it whenever ``batch_idx % log_interval == 0`` (the bookkeeping sits inside the logging
@@ -47,7 +49,7 @@ def _auc(y: np.ndarray, score: np.ndarray) -> float:
         return float("nan")
 
 
-def validate(runner, loader, *, extract_features: bool = False, smoothing: float = 0.1, log_interval: int = 50,
+def validate(runner, loader, *, extract_features: bool = False, extract_attention: bool = False, smoothing: float = 0.1, log_interval: int = 50,
              out_dir: str = "./TCGA_500", log_suffix: str = "", primary: bool = True, reference_layout: bool = False,
              log: Optional[logging.Logger] = None) -> "OrderedDict[str, float]":
     """runner: ``engine.FeatureExtractor`` (``run(tiles) -> (features, logits)``); loader: ``data.InferTiles`` /
@@ -56,12 +58,14 @@ def validate(runner, loader, *, extract_features: bool = False, smoothing: float
     log = log or _logger
     dev = runner.dev
     C = runner.C
+    if extract_attention and not extract_features:
+        raise ValueError("validate: extract_attention writes next to the features: it needs extract_features=True")
     if not extract_features and not C:
         raise ValueError("validate: scoring needs a classifier head (num_classes > 0); use extract_features=True for an encoder without one")
     loss_sum = n_seen = 0.0
     top1_sum = top5_sum = 0.0
     all_out, all_tgt, slide_out, slide_tgt = [], [], [], []
-    cur_out, cur_tgt, cur_feat = [], [], []
+    cur_out, cur_tgt, cur_feat, cur_attn = [], [], [], []
     loss_buf = torch.zeros(1, dtype=torch.float32, device=dev)
     slide_num = 0
     batch_time = 0.0
@@ -77,7 +81,11 @@ def validate(runner, loader, *, extract_features: bool = False, smoothing: float
         data = data.to(dev, non_blocking=True)
         n = data.shape[0]
         label = int(mb["Label"].reshape(-1)[0])
-        feats, logits = runner.run(data)
+        if extract_attention:
+            feats, logits, attn = runner.run_with_attention(data)
+            cur_attn.append(attn.cpu())
+        else:
+            feats, logits = runner.run(data)
         if extract_features:
             cur_feat.append(feats.cpu())
         else:
@@ -105,7 +113,9 @@ def validate(runner, loader, *, extract_features: bool = False, smoothing: float
                         torch.save(np.concatenate((np.zeros((1, f.shape[1])), f.numpy().astype(np.float64)), axis=0), path)
                     else:
                         torch.save(f, path)
-                cur_feat = []
+                    if extract_attention:
+                        torch.save(torch.cat(cur_attn), os.path.join(out_dir, f"{name}_attention.pt"))
+                cur_feat, cur_attn = [], []
             else:
                 so, st = np.concatenate(cur_out), np.concatenate(cur_tgt)
                 all_out.append(so); all_tgt.append(st)

@@ -422,6 +422,23 @@ typedef struct {
 } gv_attention_bwd_varlen_args;
 int gv_attention_bwd_varlen(const gv_attention_bwd_varlen_args* a, void* stream);
 
+/* ---- attention probabilities: the softmax matrix of Attention.forward (vit.pyc@L119-131) that the reference returns from
+ * get_last_selfattention (vit.pyc@L255-262: blocks[:-1], then the last block with return_attention=True, L146-152).
+ * gv_attention_fwd never writes it; this call recomputes it from the same q / k and the lse that forward left:
+ *     p[img, h, q, key] = exp(scale * q.k - lse[img, h, q])     for q < q_rows, key < N
+ * so P is exactly the softmax that produced o (one pass, no row reduction).  p is compact and need not be aligned: at N = 257 a
+ * row is 1 028 bytes.  q_rows = 1 is the CLS row (a forward with q_limit = 1 leaves lse valid for it); q_rows = N needs a
+ * forward with q_limit = 0.  N <= 288, head_dim 64 (the _f32 entry point: N <= 260, every 16-bit buffer as f32).            */
+typedef struct {
+    const void*  qkv;   /* 16-bit [n_img*N, 3, H, 64], as gv_attention_fwd read it                          */
+    const float* lse;   /* f32 [n_img, H, N], as gv_attention_fwd left it: rows [0, q_rows) must be valid */
+    float*       p;     /* f32 [n_img, H, q_rows, N] compact: p = exp(q.k * scale - lse[q])               */
+    int32_t n_img, N, H; float scale;
+    int32_t q_rows;     /* 1..N: query rows 0..q_rows-1 of every image (1 = the CLS row)                  */
+} gv_attention_probs_args;
+int gv_attention_probs(const gv_attention_probs_args* a, void* stream);
+int gv_attention_probs_f32(const gv_attention_probs_args* a, void* stream);   /* every 16-bit buffer as f32 */
+
 /* ---- token assembly (vit.pyc@L235-246 prepare_tokens: CLS row) ---------
  * x[i*N + 0, :] = cls[:] + pos[0, :] for every image i.                    */
 typedef struct { float* x; const float* cls; const float* pos; int32_t n_img, N, D; } gv_cls_rows_args;

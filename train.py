@@ -99,6 +99,9 @@ def build_parser():
     g.add_argument("--synthetic-slides", type=int, default=4, help="synthetic source only: slides of the inference set")
     g.add_argument("--no-validate", action="store_true", help="skip the per-epoch slide-level validation")
     g.add_argument("--features-dir", default="./TCGA_500", help="where --extract_features writes <slide>_features.pt (train.py:1282)")
+    g.add_argument("--extract-attention", action="store_true", help="with --extract_features: also write <slide>_attention.pt, f32 "
+                   "[n_tiles, heads, N] = the CLS query's last-block attention over every token (get_last_selfattention row 0); "
+                   "[:, :, 1:] reshaped to (img/16, img/16) is DINO's attention map")
     g.add_argument("--device", default="cuda", help="must be a GPU: the hot path has no CPU fallback")
     g.add_argument("--precision", default="bf16", choices=("bf16", "fp32"), help="bf16: bf16 GEMM / attention operands, f32 accumulation, f32 "
                    "residual stream and master weights (the training path).  fp32: every operand f32 -- the reference's arithmetic "
@@ -177,6 +180,8 @@ def check_supported(args, log=_logger.warning):
         raise SystemExit("--amp asks for mixed precision, --precision fp32 for f32 operands throughout: pick one")
     if args.view_augment and not (args.dino and args.random_crops):
         raise SystemExit("--view-augment augments the crops that --dino --random-crops cuts on the device: pass both")
+    if args.extract_attention and not args.extract_features:
+        raise SystemExit("--extract-attention writes <slide>_attention.pt next to the features: it needs --extract_features")
     if args.supervised and args.dino:
         raise SystemExit("--supervised (fine-tune with labels, train.py:715-717) and --dino (self-supervised) exclude each other")
     return img
@@ -532,7 +537,8 @@ def main(argv=None, transform=None):
                 train_metrics["auc"] = float("nan")
         eval_metrics = OrderedDict()
         if runner is not None:
-            eval_metrics = validate(runner, inf_loader, extract_features=bool(args.extract_features), smoothing=args.smoothing,
+            eval_metrics = validate(runner, inf_loader, extract_features=bool(args.extract_features),
+                                    extract_attention=bool(args.extract_attention), smoothing=args.smoothing,
                                     log_interval=args.log_interval, out_dir=args.features_dir, primary=primary)
             if runner_ema is not None and not args.extract_features:       # train.py:943-955: the EMA model's metrics win
                 eval_metrics = validate(runner_ema, inf_loader, smoothing=args.smoothing, log_interval=args.log_interval, primary=primary,
