@@ -38,6 +38,12 @@ gv_patchify_args = _struct("gv_patchify_args", [
 gv_patchify_nchw_args = _struct("gv_patchify_nchw_args", [
     ("images", vp), ("patches", vp), ("n_img", i32), ("n_tiles", i32), ("img_h", i32), ("img_w", i32),
     ("stride_n", i64), ("stride_c", i64), ("stride_h", i64), ("n_win", i32), ("win_y", i32 * 16), ("win_x", i32 * 16), ("crop", i32)])
+# one row of the device mix table (gipvit.mixup packs them) and the two patchify calls that take one
+gv_mix_row = _struct("gv_mix_row", [("partner", i32), ("mode", i32), ("lam", f32), ("one_minus_lam", f32),
+                                    ("yl", i32), ("yh", i32), ("xl", i32), ("xh", i32)])
+gv_patchify_mix_args = _struct("gv_patchify_mix_args", [("p", gv_patchify_args), ("mix", vp)])
+gv_patchify_nchw_mix_args = _struct("gv_patchify_nchw_mix_args", [("p", gv_patchify_nchw_args), ("mix", vp)])
+MIX_LOSS_SOFT_CE, MIX_LOSS_BCE = 0, 1
 gv_augment_params = _struct("gv_augment_params", [
     ("n_color", i32), ("order", i32 * 4), ("bf", f32), ("cf", f32), ("sf", f32), ("hue", i32), ("blur", i32), ("kc", f32), ("ks", f32),
     ("sigma", f32), ("seed", C.c_uint32), ("d4", i32), ("zoom", i32), ("a0", i32), ("a2", i32), ("cut", i32 * 4)])
@@ -117,6 +123,9 @@ gv_center_update_args = _struct("gv_center_update_args", [
 gv_softmax_lsce_args = _struct("gv_softmax_lsce_args", [
     ("logits", vp), ("target", vp), ("loss", vp), ("dlogits", vp), ("prob", vp), ("B", i32), ("C", i32), ("smoothing", f32),
     ("loss_scale", vp)])
+gv_softmax_mix_loss_args = _struct("gv_softmax_mix_loss_args", [
+    ("logits", vp), ("target", vp), ("partner", vp), ("lam", vp), ("loss", vp), ("dlogits", vp), ("prob", vp), ("B", i32), ("C", i32),
+    ("smoothing", f32), ("kind", i32), ("has_threshold", i32), ("threshold", f32), ("loss_scale", vp)])
 gv_gather_cls_args = _struct("gv_gather_cls_args", [("x", vp), ("y", vp), ("n_img", i32), ("N", i32), ("D", i32)])
 gv_store_f32_args = _struct("gv_store_f32_args", [("dst", vp), ("vals", f32 * 16), ("n", i32)])
 gv_cast_bf16_args = _struct("gv_cast_bf16_args", [("src", vp), ("dst", vp), ("n", i64)])
@@ -148,6 +157,8 @@ ENTRY_POINTS = {
     "gv_tokens_bwd": gv_tokens_bwd_args, "gv_small_matmul": gv_small_matmul_args, "gv_l2norm_fwd": gv_l2norm_fwd_args,
     "gv_l2norm_bwd": gv_l2norm_bwd_args, "gv_weightnorm_fwd": gv_weightnorm_fwd_args, "gv_weightnorm_bwd": gv_weightnorm_bwd_args,
     "gv_dino_loss": gv_dino_loss_args, "gv_center_update": gv_center_update_args, "gv_softmax_lsce": gv_softmax_lsce_args,
+    "gv_patchify_mix": gv_patchify_mix_args, "gv_patchify_nchw_mix": gv_patchify_nchw_mix_args, "gv_softmax_mix_loss": gv_softmax_mix_loss_args,
+    "gv_patchify_mix_f32": gv_patchify_mix_args, "gv_patchify_nchw_mix_f32": gv_patchify_nchw_mix_args,
     "gv_gather_cls": gv_gather_cls_args, "gv_cast_bf16": gv_cast_bf16_args, "gv_store_f32": gv_store_f32_args, "gv_sumsq": gv_sumsq_args,
     "gv_adamw_ema": gv_adamw_ema_args, "gv_loss_scale_update": gv_loss_scale_update_args, "gv_lamb": gv_lamb_args, "gv_agc": gv_agc_args, "gv_dropout": gv_dropout_args, "gv_dropout_add": gv_dropout_add_args,
     # fp32 operand mode: the same structs with every bf16 buffer read / written as f32

@@ -13,19 +13,12 @@
 
 namespace {
 
-template <bool F32OUT>      // fp32 parity mode: f32 patch rows (f32path.hip)
-__global__ __launch_bounds__(256) void patchify_kernel(gv_patchify_args a, int P, int side, float s0, float s1, float s2,
-                                                       float o0, float o1, float o2) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const long total = (long)a.n_img * P * 16;
-    if (t >= total) return;
-    const int py = (int)(t & 15);
-    const long ip = t >> 4;
-    const int patch = (int)(ip % P);
-    const int img = (int)(ip / P);
-    const int tile = img % a.n_tiles, win = img / a.n_tiles;
-    const int prow = patch / side, pcol = patch - prow * side;
-    const int y = a.win_y[win] + prow * 16 + py, x = a.win_x[win] + pcol * 16;
+struct norm_consts { float s0, s1, s2, o0, o1, o2; };
+
+// n(tile, y, x .. x + 15, c): the normalised f32 values of one 16-pixel run of a tile (with its fill box applied) -- the ONE
+// place the value is computed, for the plain and the mixing kernel alike, so both contract it the same way.
+__device__ __forceinline__ void norm_run(const gv_patchify_args& a, const norm_consts& k, int tile, int y, int x, float (&px)[3][16]) {
+    const float s0 = k.s0, s1 = k.s1, s2 = k.s2, o0 = k.o0, o1 = k.o1, o2 = k.o2;
     const uint8_t* src = a.tiles + (long)tile * a.img_stride + ((long)y * a.tile_w + x) * 3;
 
     // 48 bytes at arbitrary alignment -> 12 aligned dwords (+ up to 3 tail bytes)
@@ -50,7 +43,6 @@ __global__ __launch_bounds__(256) void patchify_kernel(gv_patchify_args a, int P
         for (int i = 0; i < 12; ++i) u[i] = (d[i] >> sh) | (d[i + 1] << (32 - sh));
     }
     // byte j of the run = pixel j/3, channel j%3
-    float px[3][16];
 #pragma unroll
     for (int j = 0; j < 48; ++j) {
         const float v = (float)((u[j >> 2] >> (8 * (j & 3))) & 0xFF);
@@ -65,23 +57,96 @@ __global__ __launch_bounds__(256) void patchify_kernel(gv_patchify_args a, int P
                 if ((float)(x + i) >= f[2] && (float)(x + i) < f[3]) { px[0][i] = f[4]; px[1][i] = f[5]; px[2][i] = f[6]; }
         }
     }
+}
+
+// one pixel row of one patch: three runs of 16 values (one per channel) at k = c*256 + py*16
+template <bool F32OUT> __device__ __forceinline__ void store_run(void* patches, long ip, int py, const float (&px)[3][16]) {
     if constexpr (F32OUT) {
-        float* out = (float*)a.patches + ip * 768 + py * 16;
+        float* out = (float*)patches + ip * 768 + py * 16;
 #pragma unroll
         for (int c = 0; c < 3; ++c)
 #pragma unroll
             for (int i = 0; i < 16; i += 4) *(f32x4*)(out + c * 256 + i) = f32x4{px[c][i], px[c][i + 1], px[c][i + 2], px[c][i + 3]};
     } else {
-    bf16* out = (bf16*)a.patches + ip * 768 + py * 16;
+        bf16* out = (bf16*)patches + ip * 768 + py * 16;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        bf16x8 lo, hi;
+        for (int c = 0; c < 3; ++c) {
+            bf16x8 lo, hi;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { lo[i] = (bf16)px[c][i]; hi[i] = (bf16)px[c][8 + i]; }
-        *(bf16x8*)(out + c * 256) = lo;
-        *(bf16x8*)(out + c * 256 + 8) = hi;
+            for (int i = 0; i < 8; ++i) { lo[i] = (bf16)px[c][i]; hi[i] = (bf16)px[c][8 + i]; }
+            *(bf16x8*)(out + c * 256) = lo;
+            *(bf16x8*)(out + c * 256 + 8) = hi;
+        }
     }
+}
+
+template <bool F32OUT>      // fp32 parity mode: f32 patch rows (f32path.hip)
+__global__ __launch_bounds__(256) void patchify_kernel(gv_patchify_args a, int P, int side, norm_consts k) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const long total = (long)a.n_img * P * 16;
+    if (t >= total) return;
+    const int py = (int)(t & 15);
+    const long ip = t >> 4;
+    const int patch = (int)(ip % P);
+    const int img = (int)(ip / P);
+    const int tile = img % a.n_tiles, win = img / a.n_tiles;
+    const int prow = patch / side, pcol = patch - prow * side;
+    const int y = a.win_y[win] + prow * 16 + py, x = a.win_x[win] + pcol * 16;
+    float px[3][16];
+    norm_run(a, k, tile, y, x, px);
+    store_run<F32OUT>(a.patches, ip, py, px);
+}
+
+// mixup's two products and their sum, each rounded on its own (torch: x.mul(lam).add(x.flip(0).mul(1 - lam))): no FMA
+__device__ __forceinline__ float mix_blend(float vi, float vj, float lam, float oml) {
+#pragma clang fp contract(off)
+    const float a = vi * lam;
+    const float b = vj * oml;
+    return a + b;
+}
+
+// A mix row as the kernels use it: anything that is not a well-formed blend / paste row is a copy row.
+struct mix_desc { int partner, mode; float lam, oml; int yl, yh, xl, xh; };
+__device__ __forceinline__ mix_desc load_mix(const gv_mix_row* mix, int img, int n_tiles) {
+    const gv_mix_row r = mix[img];
+    mix_desc m{r.partner, r.mode, r.lam, r.one_minus_lam, r.yl, r.yh, r.xl, r.xh};
+    if ((unsigned)m.partner >= (unsigned)n_tiles || (m.mode != GV_MIX_BLEND && m.mode != GV_MIX_PASTE)) m.mode = GV_MIX_COPY;
+    return m;
+}
+
+// ---- patchify_mix: patchify with timm's Mixup applied to the batch inside the same pass (gv_patchify_mix_args).  Same
+// thread mapping and store pattern as patchify_kernel; the only new traffic is the partner tile's 48 bytes per thread, read
+// by blend rows and by the threads of a paste row whose run meets the box (a run wholly inside it skips its own tile instead).
+template <bool F32OUT>
+__global__ __launch_bounds__(256) void patchify_mix_kernel(gv_patchify_args a, const gv_mix_row* mix, int P, int side, norm_consts k) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const long total = (long)a.n_img * P * 16;
+    if (t >= total) return;
+    const int py = (int)(t & 15);
+    const long ip = t >> 4;
+    const int patch = (int)(ip % P);
+    const int img = (int)(ip / P);                       // n_win == 1: image = tile
+    const int prow = patch / side, pcol = patch - prow * side;
+    const int wy = prow * 16 + py, wx = pcol * 16;       // window coordinates: the box's frame
+    const int y = a.win_y[0] + wy, x = a.win_x[0] + wx;
+    const mix_desc m = load_mix(mix, img, a.n_tiles);
+    // a paste row's run: outside the box, wholly inside it (the partner alone is read), or cut by one of its sides
+    const bool meets = m.mode == GV_MIX_PASTE && wy >= m.yl && wy < m.yh && wx < m.xh && wx + 16 > m.xl;
+    const bool whole = meets && wx >= m.xl && wx + 16 <= m.xh;
+    const bool blend = m.mode == GV_MIX_BLEND;
+    float px[3][16];
+    norm_run(a, k, whole ? m.partner : img, y, x, px);
+    if (blend || (meets && !whole)) {
+        float pj[3][16];
+        norm_run(a, k, m.partner, y, x, pj);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const bool in = wx + i >= m.xl && wx + i < m.xh;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) px[c][i] = blend ? mix_blend(px[c][i], pj[c][i], m.lam, m.oml) : (in ? pj[c][i] : px[c][i]);
+        }
     }
+    store_run<F32OUT>(a.patches, ip, py, px);
 }
 
 // ---- random-resized-crop (+ horizontal flip) of NHWC u8 tiles: the DINO multi-crop input
@@ -146,9 +211,29 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(gv_crop_resize_args a)
 // odd stride) takes four 4-B loads per item instead.
 constexpr int NCHW_MAXP = 16, NCHW_U = 6;
 
-template <typename OT>
-__global__ __launch_bounds__(256) void patchify_nchw_kernel(gv_patchify_nchw_args a, int side, int n_chunk) {
+__device__ __forceinline__ f32x4 nchw_load4(const float* src) {
+    if (((uintptr_t)src & 15) == 0) return *(const f32x4*)src;
+    return f32x4{src[0], src[1], src[2], src[3]};
+}
+
+// bit i set: pixel wx + i of window row wy lies in a paste row's box (0 for copy and blend rows)
+__device__ __forceinline__ int paste_mask4(const mix_desc& m, int wy, int wx) {
+    int mask = 0;
+    if (m.mode == GV_MIX_PASTE && wy >= m.yl && wy < m.yh) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) mask |= (wx + i >= m.xl && wx + i < m.xh) ? 1 << i : 0;
+    }
+    return mask;
+}
+
+// MIX (gv_patchify_nchw_mix, n_win == 1): phase 1 takes each 4-pixel item from the image, from its partner or from both, as
+// the image's mix row says; everything else is the plain kernel.
+template <typename OT, bool MIX>
+__global__ __launch_bounds__(256) void patchify_nchw_kernel(gv_patchify_nchw_args a, int side, int n_chunk, const gv_mix_row* mix) {
     constexpr int V = 16 / (int)sizeof(OT);                       // elements per 16-B store
+    // items per lane and round: MIX holds two sources per item, so half as many keep the loads in flight (and the registers,
+    // hence the workgroups per CU that overlap one strip's loads with another's stores) where the plain kernel has them
+    constexpr int U = MIX ? NCHW_U / 2 : NCHW_U;
     constexpr int ROW = NCHW_MAXP * 16 + 16 / (int)sizeof(OT);    // LDS image row (+16 B: rows start on different banks)
     __shared__ __attribute__((aligned(16))) OT img_lds[3 * 16 * ROW];
     const int bid = blockIdx.x;
@@ -159,26 +244,49 @@ __global__ __launch_bounds__(256) void patchify_nchw_kernel(gv_patchify_nchw_arg
     const float* base = a.images + (long)tile * a.stride_n + (long)y0 * a.stride_h + x0;
     // phase 1: item = (channel, pixel row, 4-pixel group); 48 row segments of np * 16 pixels
     const int q = np * 4, n_items = 48 * q;
-    for (int b0 = threadIdx.x; b0 < n_items; b0 += 256 * NCHW_U) {
-        f32x4 v[NCHW_U];
+    mix_desc m{0, GV_MIX_COPY, 1.f, 0.f, 0, 0, 0, 0};
+    long pdelta = 0;                                                // partner image - this image, in elements
+    if constexpr (MIX) {
+        m = load_mix(mix, img, a.n_tiles);
+        if (m.mode != GV_MIX_COPY) pdelta = (long)(m.partner - tile) * a.stride_n;
+    }
+    for (int b0 = threadIdx.x; b0 < n_items; b0 += 256 * U) {
+        f32x4 v[U];
+        // MIX: w = the partner's 4 pixels, pm = which of the 4 a paste row takes from it.  Every load of the batch of items is
+        // issued before the first value is used (the combine waits for the second loop), as in the plain kernel.
+        f32x4 w[MIX ? U : 1];
+        int pm[MIX ? U : 1];
 #pragma unroll
-        for (int u = 0; u < NCHW_U; ++u) {
+        for (int u = 0; u < U; ++u) {
             const int it = b0 + u * 256;
             if (it < n_items) {
                 const int seg = it / q, g = it - seg * q;
                 const float* src = base + (long)(seg >> 4) * a.stride_c + (long)(seg & 15) * a.stride_h + g * 4;
-                if (((uintptr_t)src & 15) == 0) {
-                    v[u] = *(const f32x4*)src;
+                if constexpr (!MIX) {
+                    v[u] = nchw_load4(src);
                 } else {
-                    v[u] = f32x4{src[0], src[1], src[2], src[3]};
+                    pm[u] = paste_mask4(m, prow * 16 + (seg & 15), p0 * 16 + g * 4);
+                    const bool blend = m.mode == GV_MIX_BLEND;
+                    v[u] = w[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (blend || pm[u] != 15) v[u] = nchw_load4(src);
+                    if (blend || pm[u] != 0) w[u] = nchw_load4(src + pdelta);
                 }
             }
         }
 #pragma unroll
-        for (int u = 0; u < NCHW_U; ++u) {
+        for (int u = 0; u < U; ++u) {
             const int it = b0 + u * 256;
             if (it < n_items) {
                 const int seg = it / q, g = it - seg * q;
+                if constexpr (MIX) {
+                    if (m.mode == GV_MIX_BLEND) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) v[u][i] = mix_blend(v[u][i], w[u][i], m.lam, m.oml);
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) v[u][i] = ((pm[u] >> i) & 1) ? w[u][i] : v[u][i];
+                    }
+                }
                 OT* d = img_lds + seg * ROW + g * 4;
                 if constexpr (sizeof(OT) == 4) {
                     *(f32x4*)d = v[u];
@@ -221,8 +329,14 @@ extern "C" int gv_crop_resize(const gv_crop_resize_args* a, void* stream) {
     return GV_OK;
 }
 
-template <bool F32OUT> static int patchify_launch(const gv_patchify_args* a, void* stream) {
+// mix == nullptr: gv_patchify; else gv_patchify_mix (has_mix says which was called: a NULL table is then an error)
+template <bool F32OUT> static int patchify_launch(const gv_patchify_args* a, void* stream, const gv_mix_row* mix = nullptr, bool has_mix = false) {
     GV_REQUIRE(a && a->tiles && a->patches, GV_E_NULL, "gv_patchify: null pointer");
+    if (has_mix) {
+        GV_REQUIRE(mix, GV_E_NULL, "gv_patchify_mix: null mix table");
+        GV_REQUIRE(gv_aligned(mix, 4), GV_E_ALIGN, "gv_patchify_mix: the mix table must be 4-byte aligned");
+        GV_REQUIRE(a->n_win == 1, GV_E_SHAPE, "gv_patchify_mix: n_win=%d, one window only (the batch is mixed as a whole)", a->n_win);
+    }
     GV_REQUIRE(a->crop > 0 && a->crop % 16 == 0, GV_E_SHAPE, "gv_patchify: crop=%d must be a positive multiple of 16", a->crop);
     GV_REQUIRE(a->n_win >= 1 && a->n_win <= 16 && a->n_tiles >= 1 && a->n_img == a->n_win * a->n_tiles, GV_E_SHAPE,
                "gv_patchify: n_img (%d) must equal n_win (%d) * n_tiles (%d), n_win <= 16", a->n_img, a->n_win, a->n_tiles);
@@ -235,16 +349,36 @@ template <bool F32OUT> static int patchify_launch(const gv_patchify_args* a, voi
     const long total = (long)a->n_img * P * 16;
     const float s0 = 1.0f / (255.0f * a->std[0]), s1 = 1.0f / (255.0f * a->std[1]), s2 = 1.0f / (255.0f * a->std[2]);
     const float o0 = -a->mean[0] / a->std[0], o1 = -a->mean[1] / a->std[1], o2 = -a->mean[2] / a->std[2];
-    hipLaunchKernelGGL(patchify_kernel<F32OUT>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *a, P, side,
-                       s0, s1, s2, o0, o1, o2);
+    const norm_consts k{s0, s1, s2, o0, o1, o2};
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (has_mix) {
+        hipLaunchKernelGGL(patchify_mix_kernel<F32OUT>, grid, dim3(256), 0, (hipStream_t)stream, *a, mix, P, side, k);
+        GV_LAUNCH_CHECK("gv_patchify_mix");
+        return GV_OK;
+    }
+    hipLaunchKernelGGL(patchify_kernel<F32OUT>, grid, dim3(256), 0, (hipStream_t)stream, *a, P, side, k);
     GV_LAUNCH_CHECK("gv_patchify");
     return GV_OK;
 }
 extern "C" int gv_patchify(const gv_patchify_args* a, void* stream) { return patchify_launch<false>(a, stream); }
 extern "C" int gv_patchify_f32(const gv_patchify_args* a, void* stream) { return patchify_launch<true>(a, stream); }
+extern "C" int gv_patchify_mix(const gv_patchify_mix_args* a, void* stream) {
+    GV_REQUIRE(a, GV_E_NULL, "gv_patchify_mix: null pointer");
+    return patchify_launch<false>(&a->p, stream, a->mix, true);
+}
+extern "C" int gv_patchify_mix_f32(const gv_patchify_mix_args* a, void* stream) {
+    GV_REQUIRE(a, GV_E_NULL, "gv_patchify_mix_f32: null pointer");
+    return patchify_launch<true>(&a->p, stream, a->mix, true);
+}
 
-template <typename OT> static int patchify_nchw_launch(const gv_patchify_nchw_args* a, void* stream, const char* name) {
+template <typename OT> static int patchify_nchw_launch(const gv_patchify_nchw_args* a, void* stream, const char* name,
+                                                       const gv_mix_row* mix = nullptr, bool has_mix = false) {
     GV_REQUIRE(a && a->images && a->patches, GV_E_NULL, "%s: null pointer", name);
+    if (has_mix) {
+        GV_REQUIRE(mix, GV_E_NULL, "%s: null mix table", name);
+        GV_REQUIRE(gv_aligned(mix, 4), GV_E_ALIGN, "%s: the mix table must be 4-byte aligned", name);
+        GV_REQUIRE(a->n_win == 1, GV_E_SHAPE, "%s: n_win=%d, one window only (the batch is mixed as a whole)", name, a->n_win);
+    }
     GV_REQUIRE(a->crop > 0 && a->crop % 16 == 0, GV_E_SHAPE, "%s: crop=%d must be a positive multiple of 16", name, a->crop);
     GV_REQUIRE(a->n_win >= 1 && a->n_win <= 16 && a->n_tiles >= 1 && a->n_img == a->n_win * a->n_tiles, GV_E_SHAPE,
                "%s: n_img (%d) must equal n_win (%d) * n_tiles (%d), 1 <= n_win <= 16", name, a->n_img, a->n_win, a->n_tiles);
@@ -258,9 +392,20 @@ template <typename OT> static int patchify_nchw_launch(const gv_patchify_nchw_ar
     const int side = a->crop / 16, n_chunk = (side + NCHW_MAXP - 1) / NCHW_MAXP;
     const long blocks = (long)a->n_img * side * n_chunk;
     GV_REQUIRE(blocks < (1L << 31), GV_E_SHAPE, "%s: %ld workgroups exceed the grid", name, blocks);
-    hipLaunchKernelGGL(patchify_nchw_kernel<OT>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *a, side, n_chunk);
+    if (has_mix)
+        hipLaunchKernelGGL((patchify_nchw_kernel<OT, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *a, side, n_chunk, mix);
+    else
+        hipLaunchKernelGGL((patchify_nchw_kernel<OT, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *a, side, n_chunk, mix);
     GV_LAUNCH_CHECK(name);
     return GV_OK;
+}
+extern "C" int gv_patchify_nchw_mix(const gv_patchify_nchw_mix_args* a, void* stream) {
+    GV_REQUIRE(a, GV_E_NULL, "gv_patchify_nchw_mix: null pointer");
+    return patchify_nchw_launch<bf16>(&a->p, stream, "gv_patchify_nchw_mix", a->mix, true);
+}
+extern "C" int gv_patchify_nchw_mix_f32(const gv_patchify_nchw_mix_args* a, void* stream) {
+    GV_REQUIRE(a, GV_E_NULL, "gv_patchify_nchw_mix_f32: null pointer");
+    return patchify_nchw_launch<float>(&a->p, stream, "gv_patchify_nchw_mix_f32", a->mix, true);
 }
 extern "C" int gv_patchify_nchw(const gv_patchify_nchw_args* a, void* stream) { return patchify_nchw_launch<bf16>(a, stream, "gv_patchify_nchw"); }
 extern "C" int gv_patchify_nchw_f32(const gv_patchify_nchw_args* a, void* stream) {

@@ -302,6 +302,65 @@ __global__ void softmax_lsce_kernel(gv_softmax_lsce_args a) {
     if (threadIdx.x == 0) atomicAdd(a.loss, red[0] / a.B);
 }
 
+// softmax_lsce's sibling for mixed / soft targets (gv_softmax_mix_loss_args): one thread per sample, C <= 64; the dense target
+// of timm's mixup_target lives in registers.  p = softmax(logits); SOFT_CE: L_b = sum_c -t_c log_softmax(p)_c, dL/dp = q sum(t) - t
+// with q = softmax(p) (rows of t sum to 1 up to rounding); BCE: L_b = mean_c bce_with_logits(p_c, t_c), dL/dp = (sigmoid(p) - t) / C.
+// Through the first softmax: dz = p * (w - <w, p>).
+__global__ void softmax_mix_loss_kernel(gv_softmax_mix_loss_args a) {
+    __shared__ float red[256];
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    float l = 0.f;
+    if (b < a.B) {
+        const int C = a.C;
+        const float* z = a.logits + (long)b * C;
+        float p[64], w[64];
+        float mx = -INFINITY;
+        for (int c = 0; c < C; ++c) mx = fmaxf(mx, z[c]);
+        float s = 0.f;
+        for (int c = 0; c < C; ++c) { p[c] = expf(z[c] - mx); s += p[c]; }
+        for (int c = 0; c < C; ++c) p[c] /= s;
+        int pb = a.partner ? a.partner[b] : b;
+        if ((unsigned)pb >= (unsigned)a.B) pb = b;
+        const long y0 = a.target[b], y1 = a.target[pb];
+        const float lam = a.lam ? a.lam[b] : 1.0f, oml = 1.0f - lam;
+        const float off = a.smoothing / C, on = 1.0f - a.smoothing + off;
+        // w holds the target first, then dL/dp
+        float st = 0.f;
+        for (int c = 0; c < C; ++c) {
+            float t = lam * (c == y0 ? on : off) + oml * (c == y1 ? on : off);
+            if (a.has_threshold) t = t > a.threshold ? 1.0f : 0.0f;
+            w[c] = t; st += t;
+        }
+        float dot = 0.f;
+        if (a.kind == GV_MIX_LOSS_SOFT_CE) {
+            float s2 = 0.f;
+            for (int c = 0; c < C; ++c) s2 += expf(p[c]);          // p in [0, 1]: no max shift needed
+            const float lse2 = logf(s2);
+            for (int c = 0; c < C; ++c) {
+                const float t = w[c];
+                l += -t * (p[c] - lse2);
+                w[c] = expf(p[c]) / s2 * st - t;
+                dot += w[c] * p[c];
+            }
+        } else {
+            const float invC = 1.0f / C;
+            for (int c = 0; c < C; ++c) {
+                const float t = w[c], x = p[c];
+                l += (fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)))) * invC;
+                w[c] = (1.0f / (1.0f + expf(-x)) - t) * invC;
+                dot += w[c] * p[c];
+            }
+        }
+        const float gs = (a.loss_scale ? *a.loss_scale : 1.0f) / a.B;
+        for (int c = 0; c < C; ++c) a.dlogits[(long)b * C + c] = p[c] * (w[c] - dot) * gs;
+        if (a.prob) for (int c = 0; c < C; ++c) a.prob[(long)b * C + c] = p[c];
+    }
+    red[threadIdx.x] = l;
+    __syncthreads();
+    for (int o = blockDim.x / 2; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) atomicAdd(a.loss, red[0] / a.B);
+}
+
 }  // namespace
 
 extern "C" int gv_cls_rows(const gv_cls_rows_args* a, void* stream) {
@@ -501,5 +560,20 @@ extern "C" int gv_softmax_lsce(const gv_softmax_lsce_args* a, void* stream) {
     if (e != hipSuccess) GV_FAIL((int)e, "gv_softmax_lsce: memset failed");
     hipLaunchKernelGGL(softmax_lsce_kernel, dim3((a->B + 255) / 256), dim3(256), 0, (hipStream_t)stream, *a);
     GV_LAUNCH_CHECK("gv_softmax_lsce");
+    return GV_OK;
+}
+
+extern "C" int gv_softmax_mix_loss(const gv_softmax_mix_loss_args* a, void* stream) {
+    GV_REQUIRE(a && a->logits && a->target && a->loss && a->dlogits, GV_E_NULL, "gv_softmax_mix_loss: null pointer");
+    GV_REQUIRE(a->B > 0 && a->C > 0 && a->C <= 64, GV_E_SHAPE, "gv_softmax_mix_loss: need 0 < C <= 64");
+    GV_REQUIRE(a->kind == GV_MIX_LOSS_SOFT_CE || a->kind == GV_MIX_LOSS_BCE, GV_E_UNSUPPORTED,
+               "gv_softmax_mix_loss: kind=%d, GV_MIX_LOSS_SOFT_CE or GV_MIX_LOSS_BCE", a->kind);
+    GV_REQUIRE(!(a->has_threshold && a->kind != GV_MIX_LOSS_BCE), GV_E_UNSUPPORTED,
+               "gv_softmax_mix_loss: a target threshold goes with GV_MIX_LOSS_BCE only (timm BinaryCrossEntropy)");
+    GV_REQUIRE(a->smoothing >= 0.f && a->smoothing < 1.f, GV_E_SHAPE, "gv_softmax_mix_loss: need 0 <= smoothing < 1");
+    hipError_t e = hipMemsetAsync(a->loss, 0, sizeof(float), (hipStream_t)stream);
+    if (e != hipSuccess) GV_FAIL((int)e, "gv_softmax_mix_loss: memset failed");
+    hipLaunchKernelGGL(softmax_mix_loss_kernel, dim3((a->B + 255) / 256), dim3(256), 0, (hipStream_t)stream, *a);
+    GV_LAUNCH_CHECK("gv_softmax_mix_loss");
     return GV_OK;
 }

@@ -451,15 +451,19 @@ class VitRunner:
 
     # ---- forward: tiles -> CLS features written into feats[row_off + seg.img0 ...]
     def forward(self, W: Weights, G: VitGroup, tiles_u8, windows, mean, std, feats, row_off: int = 0, fill=None, on_side: bool = False,
-                capture: Optional[Capture] = None):
+                capture: Optional[Capture] = None, mix: Optional[torch.Tensor] = None):
         """windows: one list of (y0, x0) crop origins per segment; tiles_u8: one NHWC u8 tensor for all
         segments, or one per segment (pre-cut crops: each with the single window (0, 0)).  A float32 NCHW source (already
         normalised, engine.input_form) goes through gv_patchify_nchw instead, without mean / std.  ``fill``: per-tile normalised
         fill boxes of the augmentation (gipvit.augment: Cutout after Normalize, MeanPixelRegularization), f32 [n_tiles, 8].
         ``on_side``: the call is queued on the side stream (the teacher beside the student): its split-K products take that
-        stream's scratch.  ``capture``: extra outputs of a forward-only pass (``Capture``); None issues exactly the default launches."""
+        stream's scratch.  ``capture``: extra outputs of a forward-only pass (``Capture``); None issues exactly the default launches.
+        ``mix``: a device mix table (gipvit.mixup.MixPlan.table) -- the single-segment, single-window batch is mixed inside the
+        patchify pass (gv_patchify_mix / gv_patchify_nchw_mix); None issues exactly the default launches."""
         D, T, H = self.D, G.T, self.H
         cap = capture
+        if mix is not None and (len(G.segs) != 1 or len(windows[0]) != 1):
+            raise ValueError("mix: the supervised step's one window of one segment only")
         if cap is not None:
             assert not G.save and len(G.segs) == 1, "capture: forward-only single-crop groups"
         tok0 = self.depth - len(cap.tokens) if cap is not None else self.depth        # first block whose normed tokens are captured
@@ -476,9 +480,9 @@ class VitRunner:
             if src.dtype == f32:
                 if fill is not None:
                     raise ValueError("fill= works on uint8 tiles: not with float32 NCHW input")
-                ops.patchify_nchw(src, wins, sg.crop, out=sg.patches)
+                ops.patchify_nchw(src, wins, sg.crop, out=sg.patches, mix=mix)
             else:
-                ops.patchify(src, wins, sg.crop, mean, std, out=sg.patches, fill=fill)
+                ops.patchify(src, wins, sg.crop, mean, std, out=sg.patches, fill=fill, mix=mix)
             if sg.pos is None:
                 pos = pos_full
             else:   # interpolate_pos_encoding: row 0 = cls pos, rows 1.. = M @ pos[1:]
@@ -1198,17 +1202,26 @@ class DinoEngine:
 # supervised single-crop step (reference train.py:1044-1078; BASELINE config 1)
 # --------------------------------------------------------------------------- #
 class SupervisedEngine:
-    """ViT + Linear head, softmax -> LabelSmoothingCE (the reference's actual loss path)."""
+    """ViT + Linear head, softmax -> LabelSmoothingCE (the reference's actual loss path); with a mix plan (gipvit.mixup) the batch
+    is mixed inside the patchify pass and the loss is SoftTargetCE / BCE on the mixup target (train.py:832-842, 1037-1040)."""
 
     def __init__(self, arch="vit_tiny", img_size=64, num_classes=2, batch=8, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999),
                  eps=1e-8, smoothing=0.1, clip_grad: float = 0.0, mean=MEAN_RON, std=STD_RON, device="cuda:0", reducer=None,
                  opt: str = "adamw", momentum: float = 0.9, train_backbone: bool = True, model_ema_decay: Optional[float] = None,
-                 precision: str = "bf16", clip_mode: str = "norm"):
+                 precision: str = "bf16", clip_mode: str = "norm", loss: str = "lsce", bce_target_thresh: Optional[float] = None):
         """``precision``: "bf16" (the training path: bf16 GEMM / attention operands, f32 accumulation and residual stream) or
         "fp32" (the reference's default arithmetic: every operand f32, csrc/f32path.hip -- the mode the 1e-4 parity gates
-        of SURVEY 8d are stated for; an order of magnitude slower, kept for verification)."""
+        of SURVEY 8d are stated for; an order of magnitude slower, kept for verification).
+        ``loss`` (train.py:832-842): "lsce" LabelSmoothingCrossEntropy (gv_softmax_lsce, the default path), "soft_ce" timm
+        SoftTargetCrossEntropy or "bce" timm BinaryCrossEntropy (``bce_target_thresh``: its target_threshold) on the mixup
+        target of the step's ``mix`` plan (gv_softmax_mix_loss); ``smoothing`` goes into that target."""
         if precision not in ("bf16", "fp32"):
             raise ValueError(f"precision {precision!r}: 'bf16' or 'fp32'")
+        if loss not in ("lsce", "soft_ce", "bce"):
+            raise ValueError(f"loss {loss!r}: 'lsce', 'soft_ce' or 'bce' (train.py:832-842)")
+        if bce_target_thresh is not None and loss != "bce":
+            raise ValueError("bce_target_thresh goes with loss='bce' (timm BinaryCrossEntropy's target_threshold)")
+        self.loss_kind, self.bce_target_thresh = loss, bce_target_thresh
         if clip_mode not in ("norm", "value", "agc"):
             raise ValueError(f"clip_mode {clip_mode!r}: 'norm', 'value' or 'agc' (train.py:1072-1077)")
         if clip_mode == "value" and opt == "lamb":
@@ -1309,12 +1322,26 @@ class SupervisedEngine:
         ops.small_matmul(self.feats, W.f("head.weight"), self.logits, B, C, D, sam=D, sak=1, sbk=1, sbn=D, bias=W.f("head.bias"))
         return self.logits, self.feats
 
-    def forward_backward(self, tiles_u8, target, fill=None):
+    def forward_backward(self, tiles_u8, target, fill=None, mix=None):
+        """``mix``: this step's gipvit.mixup.MixPlan (on the device) or None.  With a plan the batch is mixed inside the patchify
+        pass and the loss takes the plan's partner / lam (train.py:1037-1040); ``self.prob`` is the softmax of the MIXED batch."""
         B, C, D, W = self.B, self.C, self.D, self.W
+        if mix is not None and self.loss_kind == "lsce":
+            raise ValueError("mix= needs loss='soft_ce' or 'bce': label-smoothing cross-entropy takes hard labels (train.py:832-842)")
         self.arena.g.zero_()
-        self.forward(tiles_u8, fill=fill)
-        ops.softmax_lsce(self.logits, target.view(-1), self.loss, self.dlogits, self.prob, B, C, self.smoothing,
-                         loss_scale=self.scaler.scale if self.scaler is not None else None)
+        if mix is None:
+            self.forward(tiles_u8, fill=fill)
+        else:
+            input_form(tiles_u8, B, None, (("fill", fill),))
+            self.vit.forward(W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats, fill=fill, mix=mix.table)
+            ops.small_matmul(self.feats, W.f("head.weight"), self.logits, B, C, D, sam=D, sak=1, sbk=1, sbn=D, bias=W.f("head.bias"))
+        loss_scale = self.scaler.scale if self.scaler is not None else None
+        if self.loss_kind == "lsce":
+            ops.softmax_lsce(self.logits, target.view(-1), self.loss, self.dlogits, self.prob, B, C, self.smoothing, loss_scale=loss_scale)
+        else:
+            ops.softmax_mix_loss(self.logits, target.view(-1), self.loss, self.dlogits, self.prob, B, C, self.smoothing, self.loss_kind,
+                                 partner=None if mix is None else mix.partner, lam=None if mix is None else mix.lam,
+                                 threshold=self.bce_target_thresh, loss_scale=loss_scale)
         # head backward: dW = dlogits^T f, db = colsum(dlogits), df = dlogits W
         ops.small_matmul(self.dlogits, self.feats, W.g("head.weight"), C, D, B, sam=1, sak=C, sbk=D, sbn=1, accumulate=True)
         ops.small_matmul(self.ones, self.dlogits, W.g("head.bias").view(1, C), 1, C, B, sam=0, sak=1, sbk=C, sbn=1, accumulate=True)
@@ -1365,9 +1392,9 @@ class SupervisedEngine:
         if scaled:
             self.scaler.update(self.gnorm_sq)
 
-    def step(self, tiles_u8, target, lr=None, fill=None):
+    def step(self, tiles_u8, target, lr=None, fill=None, mix=None):
         assert target.dtype == torch.int64
-        self.forward_backward(tiles_u8, target, fill=fill)
+        self.forward_backward(tiles_u8, target, fill=fill, mix=mix)
         self.optimizer_step(lr)
         return self.loss
 

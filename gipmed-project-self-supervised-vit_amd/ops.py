@@ -54,10 +54,21 @@ def C_sizeof_augment_params() -> int:
     return ctypes.sizeof(L.gv_augment_params)
 
 
+def _mix_table(mix: torch.Tensor, n_tiles: int, windows) -> int:
+    """Pointer of a device mix table: uint8 [n_tiles * sizeof(gv_mix_row)] (gipvit.mixup.MixPlan.table)."""
+    import ctypes
+    if not (mix.is_cuda and mix.dtype == torch.uint8 and mix.is_contiguous() and mix.numel() == n_tiles * ctypes.sizeof(L.gv_mix_row)):
+        raise ValueError(f"mix: expected a contiguous uint8 device tensor of {n_tiles} gv_mix_row records, got {mix.dtype} {tuple(mix.shape)} on {mix.device}")
+    if len(windows) != 1:
+        raise ValueError("mix: the batch is mixed as a whole -- one crop window only")
+    return mix.data_ptr()
+
+
 def patchify(tiles_u8: torch.Tensor, windows: Sequence[Sequence[int]], crop: int, mean, std,
-             out: Optional[torch.Tensor] = None, fill: Optional[torch.Tensor] = None) -> torch.Tensor:
+             out: Optional[torch.Tensor] = None, fill: Optional[torch.Tensor] = None, mix: Optional[torch.Tensor] = None) -> torch.Tensor:
     """tiles_u8 [n_tiles, H, W, 3] u8 NHWC; windows [(y0, x0)] of side ``crop``.
-    Returns bf16 patches [(len(windows) * n_tiles) * (crop/16)^2, 768], images crop-major."""
+    Returns bf16 patches [(len(windows) * n_tiles) * (crop/16)^2, 768], images crop-major.
+    ``mix``: a device mix table (gipvit.mixup) -- the batch is mixed in the same pass (gv_patchify_mix), one window only."""
     _chk(tiles_u8, torch.uint8, "tiles")
     assert tiles_u8.dim() == 4 and tiles_u8.shape[-1] == 3 and tiles_u8.is_contiguous()
     n_tiles, H, W, _ = tiles_u8.shape
@@ -75,14 +86,19 @@ def patchify(tiles_u8: torch.Tensor, windows: Sequence[Sequence[int]], crop: int
     if fill is not None:        # f32 [n_tiles, 8] device: normalised fill boxes (Cutout after Normalize, MeanPixelRegularization)
         assert fill.is_cuda and fill.dtype == f32 and fill.shape == (n_tiles, 8) and fill.is_contiguous()
         a.fill = fill.data_ptr()
+    if mix is not None:
+        L.call("gv_patchify_mix" + _sfx(out), L.gv_patchify_mix_args(a, _mix_table(mix, n_tiles, windows)), _stream())
+        return out
     L.call("gv_patchify" + _sfx(out), a, _stream())
     return out
 
 
-def patchify_nchw(images_f32: torch.Tensor, windows: Sequence[Sequence[int]], crop: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def patchify_nchw(images_f32: torch.Tensor, windows: Sequence[Sequence[int]], crop: int, out: Optional[torch.Tensor] = None,
+                  mix: Optional[torch.Tensor] = None) -> torch.Tensor:
     """images_f32 [n_tiles, 3, H, W] f32 NCHW, already normalised (any N / C / H strides, W stride 1); windows [(y0, x0)] of
     side ``crop``.  Returns patches [(len(windows) * n_tiles) * (crop/16)^2, 768] in the build's 16-bit format (the value
-    rounded, no mean / std), or exact f32 rows when ``out`` is f32; images crop-major as ``patchify``."""
+    rounded, no mean / std), or exact f32 rows when ``out`` is f32; images crop-major as ``patchify``.
+    ``mix``: a device mix table (gipvit.mixup): gv_patchify_nchw_mix, one window only."""
     _chk(images_f32, f32, "images")
     if images_f32.dim() != 4 or images_f32.shape[1] != 3 or images_f32.stride(-1) != 1:
         raise ValueError(f"images: expected float32 [n, 3, H, W] with W stride 1, got shape {tuple(images_f32.shape)} "
@@ -101,6 +117,9 @@ def patchify_nchw(images_f32: torch.Tensor, windows: Sequence[Sequence[int]], cr
     a.n_win, a.crop = len(windows), crop
     for i, (y, x) in enumerate(windows):
         a.win_y[i], a.win_x[i] = int(y), int(x)
+    if mix is not None:
+        L.call("gv_patchify_nchw_mix" + sfx, L.gv_patchify_nchw_mix_args(a, _mix_table(mix, n_tiles, windows)), _stream())
+        return out
     L.call("gv_patchify_nchw" + sfx, a, _stream())
     return out
 
@@ -408,6 +427,22 @@ def softmax_lsce(logits, target, loss, dlogits, prob, B: int, C: int, smoothing:
     a = L.gv_softmax_lsce_args(logits.data_ptr(), target.data_ptr(), loss.data_ptr(), dlogits.data_ptr(), _p(prob), B, C, smoothing,
                                _p(loss_scale))
     L.call("gv_softmax_lsce", a, _stream())
+
+
+def softmax_mix_loss(logits, target, loss, dlogits, prob, B: int, C: int, smoothing: float, kind: str, partner=None, lam=None,
+                     threshold: Optional[float] = None, loss_scale=None):
+    """softmax -> timm SoftTargetCrossEntropy (``kind`` "soft_ce") or BinaryCrossEntropy ("bce") on the mixup target built
+    from ``target`` i64 [B], ``partner`` i32 [B] (None: no mixing) and ``lam`` f32 [B] (None: 1); see gv_softmax_mix_loss."""
+    kinds = {"soft_ce": L.MIX_LOSS_SOFT_CE, "bce": L.MIX_LOSS_BCE}
+    if kind not in kinds:
+        raise ValueError(f"kind {kind!r}: 'soft_ce' or 'bce'")
+    for t, dt, nm in ((partner, torch.int32, "partner"), (lam, f32, "lam")):
+        if t is not None and (t.dtype != dt or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f"{nm}: expected a contiguous {dt} tensor of {B} elements, got {t.dtype} {tuple(t.shape)}")
+    a = L.gv_softmax_mix_loss_args(logits.data_ptr(), target.data_ptr(), _p(partner), _p(lam), loss.data_ptr(), dlogits.data_ptr(), _p(prob),
+                                   B, C, smoothing, kinds[kind], int(threshold is not None), 0.0 if threshold is None else float(threshold),
+                                   _p(loss_scale))
+    L.call("gv_softmax_mix_loss", a, _stream())
 
 
 def gather_cls(x, y, n_img: int, N: int, D: int):

@@ -91,6 +91,38 @@ typedef struct {
 } gv_patchify_nchw_args;
 int gv_patchify_nchw(const gv_patchify_nchw_args* a, void* stream);
 
+/* ---- mixup / cutmix inside the patchify pass (reference train.py:752-771 builds timm's Mixup, 1037-1040 applies it to
+ * the batch: `input, target = mixup_fn(input, target)`).  One row of the device mix table per image i of the batch:
+ * partner index j, the weights (BOTH rounded on the host from the double the sampler drew: the kernel never computes
+ * 1 - lam), a box [yl, yh) x [xl, xh) in window coordinates and a mode.  With n(t, y, x, c) the value the unmixed
+ * kernel writes for tile t:
+ *   GV_MIX_COPY   n(i)                                  the row is bit-identical to the unmixed kernel's; j is not read
+ *   GV_MIX_BLEND  n(i) * lam + n(j) * one_minus_lam     (mixup) each product and the sum rounded separately, no FMA,
+ *                                                       then rounded once to the 16-bit format (kept f32 for _f32)
+ *   GV_MIX_PASTE  n(j) inside the box, n(i) outside     (cutmix)
+ * Sources are always the ORIGINAL tiles (timm mixes from x.flip(0) / copies), nothing is mixed in place.  A row whose
+ * partner is outside [0, n_tiles) or whose mode is unknown is treated as GV_MIX_COPY. */
+enum { GV_MIX_COPY = 0, GV_MIX_BLEND = 1, GV_MIX_PASTE = 2 };
+typedef struct {
+    int32_t partner, mode;
+    float lam, one_minus_lam;
+    int32_t yl, yh, xl, xh;
+} gv_mix_row;
+/* gv_patchify with a mix table: one window only (n_win == 1, the supervised step's top-left img_size window); `fill`
+ * is applied per SOURCE tile, as the unmixed kernel applies it. */
+typedef struct {
+    gv_patchify_args p;
+    const gv_mix_row* mix;        /* device [p.n_tiles], 4-byte aligned */
+} gv_patchify_mix_args;
+int gv_patchify_mix(const gv_patchify_mix_args* a, void* stream);
+/* gv_patchify_nchw with a mix table (n_win == 1): blend is x[i] * lam + x[j] * one_minus_lam with the same separate
+ * roundings -- bit-identical to torch's x.mul(lam).add(x.flip(0).mul(1 - lam)) followed by .to(16-bit). */
+typedef struct {
+    gv_patchify_nchw_args p;
+    const gv_mix_row* mix;        /* device [p.n_tiles], 4-byte aligned */
+} gv_patchify_nchw_mix_args;
+int gv_patchify_nchw_mix(const gv_patchify_nchw_mix_args* a, void* stream);
+
 /* ---- random-resized crops of the tiles (DINO multi-crop input stage; absent from the
  * reference, whose tiles are augmented on the CPU by transformations.py:103-209 -- SURVEY 8f rank 1).
  * For crop n: box (y0, x0, h, w) of tile `tile` is resampled to out_size x out_size with
@@ -514,6 +546,27 @@ typedef struct {
 } gv_softmax_lsce_args;
 int gv_softmax_lsce(const gv_softmax_lsce_args* a, void* stream);
 
+/* ---- supervised head loss on mixed / soft targets (train.py:832-842: timm SoftTargetCrossEntropy or BinaryCrossEntropy
+ * once mixup / cutmix is active or --bce-loss is given; :1046 softmax first, so the loss sees the SOFT-MAXED output p).
+ * The dense target of timm's mixup_target is built in registers, never in memory:
+ *     off = smoothing / C;  on = 1 - smoothing + off
+ *     t[b, c] = lam[b] * (c == y[b] ? on : off) + (1 - lam[b]) * (c == y[partner[b]] ? on : off)
+ *     has_threshold:  t = t > threshold ? 1 : 0                                        (GV_MIX_LOSS_BCE only)
+ *   GV_MIX_LOSS_SOFT_CE  loss = mean_b sum_c -t * log_softmax(p)
+ *   GV_MIX_LOSS_BCE      loss = mean_{b,c} binary_cross_entropy_with_logits(p, t)
+ * logits f32 [B, C] (C <= 64), target i64 [B]; loss scalar; dlogits f32 [B, C] = d loss / d logits (through both the
+ * softmax and the loss).  partner NULL: no mixing (timm's one-hot-with-smoothing branch); lam NULL: 1.  A partner
+ * outside [0, B) counts as the row itself. */
+enum { GV_MIX_LOSS_SOFT_CE = 0, GV_MIX_LOSS_BCE = 1 };
+typedef struct {
+    const float* logits; const int64_t* target; const int32_t* partner; const float* lam;
+    float* loss; float* dlogits; float* prob;
+    int32_t B, C; float smoothing;
+    int32_t kind, has_threshold; float threshold;
+    const float* loss_scale; /* optional DEVICE scalar: dlogits is multiplied by it (fp16 loss scaling); the loss itself is not */
+} gv_softmax_mix_loss_args;
+int gv_softmax_mix_loss(const gv_softmax_mix_loss_args* a, void* stream);
+
 /* ---- gather / scatter of CLS rows: y[i,:] = x[i*N, :] (f32 -> bf16) -------*/
 typedef struct { const float* x; void* y; int32_t n_img, N, D; } gv_gather_cls_args;
 int gv_gather_cls(const gv_gather_cls_args* a, void* stream);
@@ -647,6 +700,8 @@ int gv_layernorm_fwd_f32(const gv_layernorm_fwd_args* a, void* stream);
 int gv_layernorm_bwd_f32(const gv_layernorm_bwd_args* a, void* stream);
 int gv_patchify_f32(const gv_patchify_args* a, void* stream);
 int gv_patchify_nchw_f32(const gv_patchify_nchw_args* a, void* stream);    /* exact copy into f32 patch rows */
+int gv_patchify_mix_f32(const gv_patchify_mix_args* a, void* stream);
+int gv_patchify_nchw_mix_f32(const gv_patchify_nchw_mix_args* a, void* stream);
 int gv_tokens_bwd_f32(const gv_tokens_bwd_args* a, void* stream);
 /* DINO head: zn / dz (l2norm), the weight-normalised last-layer matrix, and the student-logit gradient as f32 */
 int gv_l2norm_fwd_f32(const gv_l2norm_fwd_args* a, void* stream);

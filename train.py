@@ -8,7 +8,8 @@ ViT path only.
 
 What it keeps from the reference (file:line = /root/reference/train.py):
   * the whole CLI surface (83-393, table in gipvit/cli_spec.py) + ``-c FILE`` YAML defaults (396-410);
-  * step order (1044-1078): forward -> softmax -> LabelSmoothingCE -> backward -> clip -> optimizer -> model EMA;
+  * step order (1037-1078): mixup / cutmix -> forward -> softmax -> LabelSmoothingCE (SoftTargetCE / BCE under mixup or --bce-loss,
+    828-846) -> backward -> clip -> optimizer -> model EMA;
   * lr = lr_base * global_batch / 256 (569-581), cosine/step schedule with warm-up (881-887);
   * the ``Train: ep [i/n] Loss .. Time .. rate/s LR .. Data ..`` log line (1096-1111);
   * the epoch loop (905-977): train -> slide-level ``validate`` (933, 1146-1345) -> EMA validate (943-955) ->
@@ -184,7 +185,53 @@ def check_supported(args, log=_logger.warning):
         raise SystemExit("--extract-attention writes <slide>_attention.pt next to the features: it needs --extract_features")
     if args.supervised and args.dino:
         raise SystemExit("--supervised (fine-tune with labels, train.py:715-717) and --dino (self-supervised) exclude each other")
+    # mixup / cutmix / BCE (train.py:752-771, 828-846): the supervised step's batch, target and loss
+    given = [f for f, on in (("--mixup", args.mixup), ("--cutmix", args.cutmix), ("--cutmix-minmax", args.cutmix_minmax is not None),
+                             ("--mixup-prob", args.mixup_prob != 1.0), ("--mixup-switch-prob", args.mixup_switch_prob != 0.5),
+                             ("--mixup-mode", args.mixup_mode != "batch"), ("--mixup-off-epoch", args.mixup_off_epoch),
+                             ("--bce-loss", args.bce_loss), ("--bce-target-thresh", args.bce_target_thresh is not None)) if on]
+    if args.dino and given:
+        raise SystemExit(f"{' '.join(given)} with --dino: mixup / cutmix and the soft-target / BCE losses belong to the supervised step "
+                         "(train.py:752-771, 828-846); the DINO loss takes no labels")
+    if args.mixup < 0 or args.cutmix < 0:
+        raise SystemExit(f"--mixup {args.mixup} --cutmix {args.cutmix}: the Beta distribution's alpha must be >= 0 (0 = off)")
+    if args.mixup_mode not in ("batch", "pair", "elem"):
+        raise SystemExit(f"--mixup-mode {args.mixup_mode}: 'batch', 'pair' or 'elem' (train.py:275-276)")
+    if args.cutmix_minmax is not None:
+        mm = list(args.cutmix_minmax)
+        if len(mm) != 2 or not (0.0 < mm[0] < mm[1] <= 1.0):
+            raise SystemExit(f"--cutmix-minmax {mm}: two values in (0, 1], strictly ascending (min and max side of the box as a share of the image)")
+    if not 0.0 <= args.mixup_prob <= 1.0 or not 0.0 <= args.mixup_switch_prob <= 1.0:
+        raise SystemExit("--mixup-prob / --mixup-switch-prob are probabilities: 0 <= p <= 1")
+    if mix_active(args) and args.batch_size % 2:
+        raise SystemExit(f"--batch-size {args.batch_size} with mixup / cutmix: image i is mixed with image B - 1 - i, the batch size must be even")
+    if args.bce_loss and not mix_active(args) and not args.smoothing:
+        log("--bce-loss with --smoothing 0 and no mixup: the reference selects plain cross-entropy there (train.py:838-844); so does this build")
     return img
+
+
+def mix_active(args) -> bool:
+    """train.py:755."""
+    return args.mixup > 0 or args.cutmix > 0.0 or args.cutmix_minmax is not None
+
+
+def loss_kind(args) -> str:
+    """The training loss train.py:832-844 selects, as SupervisedEngine's ``loss``: mixing active -> BinaryCrossEntropy with --bce-loss,
+    else SoftTargetCrossEntropy (smoothing goes into the target); not active -> BinaryCrossEntropy with --bce-loss and a non-zero
+    --smoothing, else LabelSmoothingCrossEntropy (smoothing 0: cross-entropy)."""
+    if mix_active(args):
+        return "bce" if args.bce_loss else "soft_ce"
+    return "bce" if (args.bce_loss and args.smoothing) else "lsce"
+
+
+def build_mix_sampler(args, img_size: int, rank: int = 0):
+    """timm Mixup's draws from the flags (train.py:755-771), or None when mixing is off.  Seeded per rank like the other host streams."""
+    if not mix_active(args):
+        return None
+    from gipvit.mixup import MixSampler
+    return MixSampler(mixup_alpha=args.mixup, cutmix_alpha=args.cutmix, cutmix_minmax=args.cutmix_minmax, prob=args.mixup_prob,
+                      switch_prob=args.mixup_switch_prob, mode=args.mixup_mode, batch=args.batch_size, img_size=img_size,
+                      seed=args.seed + 101 * rank + 23)
 
 
 def amp_is_f16(args) -> bool:
@@ -369,7 +416,8 @@ def main(argv=None, transform=None):
         eng = SupervisedEngine(arch=arch, img_size=img, num_classes=nc, batch=B, lr=lr, weight_decay=args.weight_decay, betas=betas, eps=eps,
                                smoothing=args.smoothing, clip_grad=args.clip_grad or 0.0, mean=mean, std=std, device=dev, reducer=reducer,
                                opt=opt, momentum=args.momentum,
-                               train_backbone=not args.no_grad, model_ema_decay=ema_decay, precision=args.precision, clip_mode=args.clip_mode)
+                               train_backbone=not args.no_grad, model_ema_decay=ema_decay, precision=args.precision, clip_mode=args.clip_mode,
+                               loss=loss_kind(args), bce_target_thresh=args.bce_target_thresh if loss_kind(args) == "bce" else None)
         st = (M.load_encoder_checkpoint(args.initial_checkpoint, arch, img, nc) if args.initial_checkpoint
               else M.init_vit_state(arch, img, nc, seed=args.seed))
         eng.load_state(st)
@@ -433,6 +481,11 @@ def main(argv=None, transform=None):
         from gipvit.multicrop import MultiCropSampler
         sampler = MultiCropSampler(B, tile, 2, args.local_crops_number, tuple(args.global_crops_scale), tuple(args.local_crops_scale),
                                    seed=args.seed + rank)
+    # mixup / cutmix (train.py:752-771, 1037-1040): the draws are the host's, the mixed batch is made inside the patchify pass
+    mix_sampler = None if args.dino else build_mix_sampler(args, img, rank)
+    if mix_sampler is not None and primary:
+        _logger.info("mixup / cutmix on the device: mixup %.3g cutmix %.3g minmax %s prob %.3g switch %.3g mode %s, loss %s", args.mixup, args.cutmix,
+                     args.cutmix_minmax, args.mixup_prob, args.mixup_switch_prob, args.mixup_mode, loss_kind(args))
     view_sampler = None
     if args.view_augment:
         from gipvit.multicrop import ViewAugmentSampler
@@ -450,7 +503,8 @@ def main(argv=None, transform=None):
             ex["drop_path_rng"] = drop_sampler.state_dict()     # a resumed run continues the mask stream
         # ... and the other host-side draw streams (--drop step seeds, random-resized-crop boxes, view augmentation), as JSON
         # strings of numpy's bit-generator state: plain str, loads with weights_only=True
-        streams = {"drop": drop_rng, "crops": getattr(sampler, "rng", None), "views": getattr(view_sampler, "rng", None)}
+        streams = {"drop": drop_rng, "crops": getattr(sampler, "rng", None), "views": getattr(view_sampler, "rng", None),
+                   "mix": getattr(mix_sampler, "rng", None)}
         ex["host_rng"] = {k: json.dumps(g.bit_generator.state) for k, g in streams.items() if g is not None}
         if eng.scaler is not None:
             ex["amp_scaler"] = eng.scaler.state_dict()          # timm CheckpointSaver(amp_scaler=loss_scaler) key, train.py:585-602
@@ -476,7 +530,8 @@ def main(argv=None, transform=None):
         import numpy as np
         drop_rng = np.random.default_rng(args.seed + 7919 * rank + 11)
     if args.resume and isinstance(ck.get("host_rng"), dict):     # continue the draw streams where the saved run left them
-        for k, g in (("drop", drop_rng), ("crops", getattr(sampler, "rng", None)), ("views", getattr(view_sampler, "rng", None))):
+        for k, g in (("drop", drop_rng), ("crops", getattr(sampler, "rng", None)), ("views", getattr(view_sampler, "rng", None)),
+                     ("mix", getattr(mix_sampler, "rng", None))):
             if g is not None and k in ck["host_rng"]:
                 g.bit_generator.state = json.loads(ck["host_rng"][k])
     cur_lr = lr
@@ -488,6 +543,8 @@ def main(argv=None, transform=None):
         last_idx = updates_per_epoch - 1
         if args.dino:
             eng.train_last_layer = epoch >= args.freeze_last_layer
+        if mix_sampler is not None and args.mixup_off_epoch and epoch >= args.mixup_off_epoch:
+            mix_sampler.enabled = False                # train.py:1005-1009: no mixing from this epoch on; the loss stays the soft-target one
         for batch_idx, mb in (enumerate(loader) if not args.extract_features else ()):      # train.py:906
             data, target = mb["Data"], mb["Target"]
             fill = None
@@ -507,7 +564,7 @@ def main(argv=None, transform=None):
                 loss_t = eng.step(data, boxes=sampler.sample(dev) if sampler is not None else None, fill=fill if sampler is None else None,
                                   views=view_sampler.sample(dev) if view_sampler is not None else None, **sch)
             else:
-                loss_t = eng.step(data, target, lr=cur_lr, fill=fill)
+                loss_t = eng.step(data, target, lr=cur_lr, fill=fill, mix=mix_sampler.sample(dev) if mix_sampler is not None else None)
                 probs.append(eng.prob[:, 1].clone() if eng.C > 1 else eng.prob[:, 0].clone()); targets.append(target.view(-1).clone())
             torch.cuda.synchronize()                  # train.py:1083
             batch_time.update(time.time() - end)
