@@ -135,6 +135,8 @@ gv_adamw_ema_args = _struct("gv_adamw_ema_args", [
     ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32), ("bias_corr1", f32), ("bias_corr2", f32),
     ("grad_scale", f32), ("clip_norm", f32), ("gnorm_sq", vp), ("teacher_momentum", f32), ("hyper", vp), ("mode", i32), ("clip_value", f32),
     ("loss_scale", vp)])
+gv_adamw_ema_ranges_args = _struct("gv_adamw_ema_ranges_args", gv_adamw_ema_args._fields_ + [
+    ("blocks", vp), ("n_blocks", i32), ("ranges", vp), ("n_ranges", i32)])
 gv_loss_scale_update_args = _struct("gv_loss_scale_update_args", [
     ("state", vp), ("gnorm_sq", vp), ("growth_factor", f32), ("backoff_factor", f32), ("growth_interval", i32)])
 u32 = C.c_uint32
@@ -145,7 +147,7 @@ gv_agc_args = _struct("gv_agc_args", [("p", vp), ("grad", vp), ("units", vp), ("
 gv_lamb_args = _struct("gv_lamb_args", [
     ("p", vp), ("grad", vp), ("m", vp), ("v", vp), ("p_bf16", vp), ("teacher", vp), ("teacher_bf16", vp), ("blocks", vp), ("n_blocks", i32),
     ("stats", vp), ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32), ("bias_corr1", f32), ("bias_corr2", f32),
-    ("grad_scale", f32), ("clip_norm", f32), ("max_grad_norm", f32), ("gnorm_sq", vp), ("teacher_momentum", f32), ("phase", i32)])
+    ("grad_scale", f32), ("clip_norm", f32), ("max_grad_norm", f32), ("gnorm_sq", vp), ("teacher_momentum", f32), ("phase", i32), ("lr_scale", vp)])
 
 # entry point -> argument struct (every `int gv_*(const args*, void* stream)` of the header)
 ENTRY_POINTS = {
@@ -160,7 +162,7 @@ ENTRY_POINTS = {
     "gv_patchify_mix": gv_patchify_mix_args, "gv_patchify_nchw_mix": gv_patchify_nchw_mix_args, "gv_softmax_mix_loss": gv_softmax_mix_loss_args,
     "gv_patchify_mix_f32": gv_patchify_mix_args, "gv_patchify_nchw_mix_f32": gv_patchify_nchw_mix_args,
     "gv_gather_cls": gv_gather_cls_args, "gv_cast_bf16": gv_cast_bf16_args, "gv_store_f32": gv_store_f32_args, "gv_sumsq": gv_sumsq_args,
-    "gv_adamw_ema": gv_adamw_ema_args, "gv_loss_scale_update": gv_loss_scale_update_args, "gv_lamb": gv_lamb_args, "gv_agc": gv_agc_args, "gv_dropout": gv_dropout_args, "gv_dropout_add": gv_dropout_add_args,
+    "gv_adamw_ema": gv_adamw_ema_args, "gv_adamw_ema_ranges": gv_adamw_ema_ranges_args, "gv_loss_scale_update": gv_loss_scale_update_args, "gv_lamb": gv_lamb_args, "gv_agc": gv_agc_args, "gv_dropout": gv_dropout_args, "gv_dropout_add": gv_dropout_add_args,
     # fp32 operand mode: the same structs with every bf16 buffer read / written as f32
     "gv_linear_f32": gv_linear_args, "gv_attention_fwd_f32": gv_attention_fwd_args, "gv_attention_bwd_f32": gv_attention_bwd_args,
     "gv_attention_probs_f32": gv_attention_probs_args,

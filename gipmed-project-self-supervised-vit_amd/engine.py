@@ -31,6 +31,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .layer_decay import LayerDecayPlan
 
 bf16, f32 = ops.bf16, torch.float32      # ops.bf16: the 16-bit dtype of the loaded library build (float16 under GIPVIT_ACT_FORMAT=f16)
 
@@ -1208,13 +1209,18 @@ class SupervisedEngine:
     def __init__(self, arch="vit_tiny", img_size=64, num_classes=2, batch=8, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999),
                  eps=1e-8, smoothing=0.1, clip_grad: float = 0.0, mean=MEAN_RON, std=STD_RON, device="cuda:0", reducer=None,
                  opt: str = "adamw", momentum: float = 0.9, train_backbone: bool = True, model_ema_decay: Optional[float] = None,
-                 precision: str = "bf16", clip_mode: str = "norm", loss: str = "lsce", bce_target_thresh: Optional[float] = None):
+                 precision: str = "bf16", clip_mode: str = "norm", loss: str = "lsce", bce_target_thresh: Optional[float] = None,
+                 layer_decay: Optional[float] = None):
         """``precision``: "bf16" (the training path: bf16 GEMM / attention operands, f32 accumulation and residual stream) or
         "fp32" (the reference's default arithmetic: every operand f32, csrc/f32path.hip -- the mode the 1e-4 parity gates
         of SURVEY 8d are stated for; an order of magnitude slower, kept for verification).
         ``loss`` (train.py:832-842): "lsce" LabelSmoothingCrossEntropy (gv_softmax_lsce, the default path), "soft_ce" timm
         SoftTargetCrossEntropy or "bce" timm BinaryCrossEntropy (``bce_target_thresh``: its target_threshold) on the mixup
-        target of the step's ``mix`` plan (gv_softmax_mix_loss); ``smoothing`` goes into that target."""
+        target of the step's ``mix`` plan (gv_softmax_mix_loss); ``smoothing`` goes into that target.
+        ``layer_decay`` (train.py:175 --layer-decay -> timm param_groups_layer_decay, restated in gipvit.layer_decay): None = one
+        rate for every layer, the two-launch optimizer pass.  A number (1.0 included) gives layer ``id`` the rate
+        ``lr * layer_decay ** (depth + 2 - id)`` and makes ``optimizer_step`` ONE gv_adamw_ema_ranges launch over a range table
+        (adamw / adam / sgd) or hands gv_lamb a per-tensor rate; ``layer_scales`` / ``mean_lr`` show the result."""
         if precision not in ("bf16", "fp32"):
             raise ValueError(f"precision {precision!r}: 'bf16' or 'fp32'")
         if loss not in ("lsce", "soft_ce", "bce"):
@@ -1283,6 +1289,26 @@ class SupervisedEngine:
             self._lamb_stats = torch.zeros(2 * len(self._lamb_names), dtype=f32, device=dev)
             self.lamb_max_grad_norm = 1.0          # timm Lamb default
         self.train_backbone = train_backbone      # False = --no-grad head-only fine-tune (train.py:497-503)
+        self.layer_decay = layer_decay
+        if layer_decay is not None:
+            # built once for both settings of train_backbone (the driver's model object may flip it after construction):
+            # the whole arena, and the classifier's two tensors alone (the optimizer never sees a frozen parameter)
+            a, depth = self.arena, ARCHS[arch]["depth"]
+            plans = {True: LayerDecayPlan(a, depth, layer_decay), False: LayerDecayPlan(a, depth, layer_decay, names=("head.weight", "head.bias"))}
+            self._ld = {k: (pl, pl.block_table().to(dev), pl.range_rows().to(dev)) for k, pl in plans.items()}
+            if opt == "lamb":
+                self._lamb_lr_scale = torch.tensor([plans[True].scales[n] for n in self._lamb_names], dtype=f32).to(dev)
+
+    @property
+    def layer_scales(self) -> Optional[Dict[str, float]]:
+        """--layer-decay: name -> rate scale of every parameter the optimizer steps (None without the flag)."""
+        return None if self.layer_decay is None else dict(self._ld[bool(self.train_backbone)][0].scales)
+
+    def mean_lr(self, lr: float) -> float:
+        """The rate the reference logs for a scheduled rate ``lr``: the mean over the optimizer's parameter groups (train.py:1088-1089,
+        959-965) -- with --layer-decay ``lr`` times the mean scale of the (layer, decay) groups that hold a trainable parameter,
+        else ``lr`` itself."""
+        return lr if self.layer_decay is None else self._ld[bool(self.train_backbone)][0].mean_lr(lr)
 
     def load_state(self, state: Dict[str, torch.Tensor], ema_state: Optional[Dict[str, torch.Tensor]] = None):
         self.arena.load(state)
@@ -1377,7 +1403,15 @@ class SupervisedEngine:
             for phase in (0, 1):
                 for tab, wd in zip(self._lamb_tabs, (self.wd, 0.0)):
                     if tab.shape[0]:
-                        ops.lamb(a.p, a.g, a.m, a.v, a.pb, a.t, a.tb, tab, self._lamb_stats, self.gnorm_sq, phase=phase, weight_decay=wd, **kl)
+                        ops.lamb(a.p, a.g, a.m, a.v, a.pb, a.t, a.tb, tab, self._lamb_stats, self.gnorm_sq, phase=phase, weight_decay=wd,
+                                 lr_scale=self._lamb_lr_scale if self.layer_decay is not None else None, **kl)
+            return
+        if self.layer_decay is not None:
+            # --layer-decay: every (layer, decay | no-decay) range at its own rate, one launch (gv_adamw_ema_ranges)
+            _, blocks, rows = self._ld[bool(self.train_backbone)]
+            ops.adamw_ema_ranges(a.p, a.g, a.m, a.v, a.pb, a.t, a.tb, a.n, blocks, rows, weight_decay=self.wd, **kw)
+            if scaled:
+                self.scaler.update(self.gnorm_sq)
             return
         if self.train_backbone:
             ranges = [(0, a.n_decay, self.wd), (a.n_decay, a.n, 0.0)]

@@ -144,7 +144,7 @@ class _Head:
 
 class VitModel:
     """The object ``create_model`` returns: the attributes and methods the reference driver uses on timm's
-    ``VisionTransformer`` (``num_classes``, ``head``, ``no_weight_decay()``, ``set_grad_checkpointing()``, ``parameters()``,
+    ``VisionTransformer`` (``num_classes``, ``head``, ``no_weight_decay()``, ``group_matcher()``, ``set_grad_checkpointing()``, ``parameters()``,
     ``state_dict()`` / ``load_state_dict()``, ``train()`` / ``eval()``, ``model(input)``), backed by a ``SupervisedEngine``
     (the hot path itself: HIP kernels behind the C ABI, explicit backward -- there is no ``nn.Module`` and no autograd)."""
 
@@ -165,6 +165,13 @@ class VitModel:
 
     def no_weight_decay(self):
         return {"pos_embed", "cls_token"}               # vit.pyc@L208-211
+
+    def group_matcher(self, coarse: bool = False):
+        """timm ``VisionTransformer.group_matcher`` -- what ``--layer-decay`` (train.py:175 -> create_optimizer_v2 ->
+        param_groups_layer_decay) groups the parameters by; restated from timm's published source, which is not importable
+        here and unpinned in the reference (gipvit.layer_decay)."""
+        from .layer_decay import group_matcher
+        return group_matcher(coarse)
 
     def set_grad_checkpointing(self, enable: bool = True):
         # the explicit backward keeps every block's activations resident (4 GB at B = 64 on a 288-GB part): nothing to do

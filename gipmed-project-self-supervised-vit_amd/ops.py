@@ -476,6 +476,32 @@ def adamw_ema(p, grad, m, v, p_bf16, teacher, teacher_bf16, n: int, *, lr, beta1
     L.call("gv_adamw_ema", a, _stream())
 
 
+def range_block_table(ranges, chunk: int = 1 << 12) -> torch.Tensor:
+    """Block table of gv_adamw_ema_ranges for ranges = [(lo, hi), ...] (element ranges of the flat buffers, multiples of 4, in
+    range-id order): int32 [n_blocks, 3] = (range, lo, hi), rows of at most ``chunk`` elements that never cross a range -- one
+    workgroup's work, so a 768-element range and a 1.77 M-element one load the chip alike (as lamb_block_table)."""
+    assert chunk > 0 and chunk % 4 == 0
+    return lamb_block_table(ranges, chunk)
+
+
+def adamw_ema_ranges(p, grad, m, v, p_bf16, teacher, teacher_bf16, n: int, blocks, ranges, *, lr, beta1, beta2, eps, weight_decay, step: int,
+                     grad_scale=1.0, clip_norm=0.0, gnorm_sq=None, teacher_momentum=0.0, hyper=None, mode=0, clip_value=0.0, loss_scale=None):
+    """gv_adamw_ema over a range table in ONE launch: ``blocks`` device int32 [n_blocks, 3] = (range, lo, hi) (range_block_table),
+    ``ranges`` device f32 [n_ranges, 2] = (lr_scale, wd_multiplier); range r steps at ``lr * lr_scale[r]`` with weight decay
+    ``weight_decay * wd_multiplier[r]``.  Everything else as adamw_ema."""
+    if not (blocks.dtype == torch.int32 and blocks.is_contiguous() and blocks.dim() == 2 and blocks.shape[1] == 3):
+        raise TypeError("blocks: contiguous int32 [n_blocks, 3]")
+    if not (ranges.dtype == f32 and ranges.is_contiguous() and ranges.dim() == 2 and ranges.shape[1] == 2):
+        raise TypeError("ranges: contiguous float32 [n_ranges, 2]")
+    if blocks.device != p.device or ranges.device != p.device:
+        raise TypeError("blocks / ranges must live on the device of the buffers")
+    a = L.gv_adamw_ema_ranges_args(p.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p_bf16), _p(teacher), _p(teacher_bf16), n,
+                                   lr, beta1, beta2, eps, weight_decay, 1.0 - beta1 ** step, 1.0 - beta2 ** step,
+                                   grad_scale, clip_norm, _p(gnorm_sq), teacher_momentum, _p(hyper), mode, clip_value, _p(loss_scale),
+                                   blocks.data_ptr(), blocks.shape[0], ranges.data_ptr(), ranges.shape[0])
+    L.call("gv_adamw_ema_ranges", a, _stream())
+
+
 class LossScaler:
     """torch.cuda.amp.GradScaler as timm's NativeScaler drives it (reference train.py:585-602, 1061-1070), kept on the device:
     ``state`` = f32 [S, consecutive finite steps, skipped steps, applied steps].  The loss kernels multiply their gradient by S, gv_adamw_ema divides
@@ -518,12 +544,14 @@ def lamb_block_table(tensors, chunk: int = 1 << 16) -> torch.Tensor:
 
 
 def lamb(p, grad, m, v, p_bf16, teacher, teacher_bf16, blocks, stats, gnorm_sq, *, phase: int, lr, beta1, beta2, eps, weight_decay, step: int,
-         grad_scale=1.0, clip_norm=0.0, max_grad_norm=1.0, teacher_momentum=0.0):
-    """One phase of LAMB over the tensors of ``blocks`` (device int32 [n, 3], offsets relative to the buffers passed); see gv_lamb."""
+         grad_scale=1.0, clip_norm=0.0, max_grad_norm=1.0, teacher_momentum=0.0, lr_scale=None):
+    """One phase of LAMB over the tensors of ``blocks`` (device int32 [n, 3], offsets relative to the buffers passed); see gv_lamb.
+    ``lr_scale``: optional device f32 [n_tensors], tensor t steps at ``lr * lr_scale[t]`` (--layer-decay)."""
+    assert lr_scale is None or (lr_scale.dtype == f32 and lr_scale.is_contiguous() and lr_scale.device == p.device)
     assert blocks.dtype == torch.int32 and blocks.is_contiguous() and stats.dtype == f32
     a = L.gv_lamb_args(p.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p_bf16), _p(teacher), _p(teacher_bf16), blocks.data_ptr(),
                        blocks.shape[0], stats.data_ptr(), lr, beta1, beta2, eps, weight_decay, 1.0 - beta1 ** step, 1.0 - beta2 ** step,
-                       grad_scale, clip_norm, max_grad_norm, gnorm_sq.data_ptr(), teacher_momentum, phase)
+                       grad_scale, clip_norm, max_grad_norm, gnorm_sq.data_ptr(), teacher_momentum, phase, _p(lr_scale))
     L.call("gv_lamb", a, _stream())
 
 

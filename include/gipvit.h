@@ -623,6 +623,37 @@ typedef struct {
 } gv_adamw_ema_args;
 int gv_adamw_ema(const gv_adamw_ema_args* a, void* stream);
 
+/* ---- the same pass over a RANGE TABLE: per-range learning-rate scale and weight-decay multiplier in ONE launch
+ * (`--layer-decay`, reference train.py:175 -> optimizer_kwargs -> timm create_optimizer_v2 -> param_groups_layer_decay: one
+ * parameter group per (layer, decay | no-decay), each at lr * lr_scale, the scheduler multiplying every group's rate by its
+ * lr_scale -- SURVEY Appendix B).  Every field gv_adamw_ema_args carries keeps its meaning; range r is stepped with
+ *     lr_r = lr * ranges[r][0]  (formed once, in f32; `lr` is hyper[GV_HYP_LR] when hyper is given)
+ *     wd_r = weight_decay * ranges[r][1]          (weight_decay after the hyper[GV_HYP_WD] multiplication)
+ * and the global-norm / value clip, the loss-scaled skip on a non-finite *gnorm_sq (p, m, v untouched in every range, the
+ * EMA copy still moves), the applied-step bias corrections, the EMA copy and both 16-bit refreshes are gv_adamw_ema's:
+ * both kernels call one per-element device function, so with lr_scale = 1 the results are bit-identical to gv_adamw_ema
+ * calls over the same ranges.  mode 0 / 1 / 2 only: a frozen range is simply left out of the table.
+ *   blocks: device int32 [n_blocks][3] = {range, lo, hi}: elements [lo, hi) of the buffers, all of range `range`, taken by
+ *           one workgroup -- rows of bounded length that never cross a range (the ranges differ in size by three orders
+ *           of magnitude), lo / hi multiples of 4, 0 <= lo < hi <= n; a row outside [0, n) or naming no range is skipped;
+ *   ranges: device f32 [n_ranges][2] = {lr_scale, wd_multiplier}.
+ * Elements no row covers are not touched at all (no 16-bit refresh, no EMA).                                          */
+typedef struct {
+    float* p; const float* grad; float* m; float* v; void* p_bf16;
+    float* teacher; void* teacher_bf16;
+    int64_t n;                   /* length of the buffers in elements: the bound every table row is checked against */
+    float lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2;
+    float grad_scale, clip_norm; const float* gnorm_sq;
+    float teacher_momentum;
+    const float* hyper;
+    int32_t mode;                /* 0 AdamW, 1 Adam + L2, 2 SGD Nesterov */
+    float clip_value;
+    const float* loss_scale;
+    const int32_t* blocks; int32_t n_blocks;
+    const float* ranges; int32_t n_ranges;
+} gv_adamw_ema_ranges_args;
+int gv_adamw_ema_ranges(const gv_adamw_ema_ranges_args* a, void* stream);
+
 /* ---- GradScaler.update() (torch.cuda.amp.GradScaler: init_scale 65536, growth_factor 2, backoff_factor 0.5, growth_interval
  * 2000): state[0] = S, state[1] = number of consecutive finite steps, state[2] = number of skipped steps so far (for the log),
  * state[3] = number of applied optimizer steps.
@@ -683,6 +714,9 @@ typedef struct {
     float grad_scale, clip_norm, max_grad_norm; const float* gnorm_sq;     /* gnorm_sq: sum of squares of the raw gradient */
     float teacher_momentum;
     int32_t phase;
+    /* optional: device f32 [n_tensors], tensor t is stepped at lr * lr_scale[t] in phase 1 (`--layer-decay`; the trust ratio and
+     * both clips do not depend on the rate).  NULL = every tensor at lr                                                */
+    const float* lr_scale;
 } gv_lamb_args;
 int gv_lamb(const gv_lamb_args* a, void* stream);
 

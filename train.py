@@ -155,6 +155,13 @@ def check_supported(args, log=_logger.warning):
     if args.dino and args.opt.lower() != "adamw":
         raise SystemExit(f"--dino --opt {args.opt}: the DINO step is AdamW with the recipe's weight-decay schedule (paper; the frozen-last-layer and "
                          "teacher-EMA ranges are fused into that pass); pass --opt adamw")
+    if args.layer_decay is not None:
+        # train.py:175 -> timm param_groups_layer_decay: every layer below the classifier at layer_decay times the rate of the one above
+        if not args.layer_decay > 0:
+            raise SystemExit(f"--layer-decay {args.layer_decay}: the per-layer rate scale is layer_decay ** k, it must be > 0")
+        if args.dino:
+            raise SystemExit("--dino --layer-decay is not built: the DINO step keeps its recipe (one rate for the student, the frozen-last-layer and "
+                             "teacher-EMA ranges fused into its pass); --layer-decay is the supervised fine-tuning knob")
     if args.sched.lower() not in SUPPORTED_SCHEDS:
         raise SystemExit(f"--sched {args.sched}: this build steps the learning rate by {' / '.join(SUPPORTED_SCHEDS)} (+ linear warm-up); timm's other "
                          "create_scheduler_v2 choices (reference train.py:180, 881-887) are not built and a constant rate is not substituted")
@@ -417,7 +424,8 @@ def main(argv=None, transform=None):
                                smoothing=args.smoothing, clip_grad=args.clip_grad or 0.0, mean=mean, std=std, device=dev, reducer=reducer,
                                opt=opt, momentum=args.momentum,
                                train_backbone=not args.no_grad, model_ema_decay=ema_decay, precision=args.precision, clip_mode=args.clip_mode,
-                               loss=loss_kind(args), bce_target_thresh=args.bce_target_thresh if loss_kind(args) == "bce" else None)
+                               loss=loss_kind(args), bce_target_thresh=args.bce_target_thresh if loss_kind(args) == "bce" else None,
+                               layer_decay=args.layer_decay)
         st = (M.load_encoder_checkpoint(args.initial_checkpoint, arch, img, nc) if args.initial_checkpoint
               else M.init_vit_state(arch, img, nc, seed=args.seed))
         eng.load_state(st)
@@ -535,6 +543,9 @@ def main(argv=None, transform=None):
             if g is not None and k in ck["host_rng"]:
                 g.bit_generator.state = json.loads(ck["host_rng"][k])
     cur_lr = lr
+    # the reference logs the MEAN rate over the optimizer's parameter groups (train.py:1088-1089, 959-965): with --layer-decay
+    # that is cur_lr x the mean group scale, without it cur_lr itself
+    logged_lr = eng.mean_lr if hasattr(eng, "mean_lr") else (lambda v: v)
     # ---- epoch loop (train.py:905-977) / step loop (988-1143)
     for epoch in range(start_epoch, args.epochs):
         batch_time, data_time, losses = Meter(), Meter(), Meter()
@@ -579,7 +590,7 @@ def main(argv=None, transform=None):
                     _logger.info("Train: {} [{:>4d}/{} ({:>3.0f}%)]  Loss: {:#.4g} ({:#.3g})  Time: {:.3f}s, {:>7.2f}/s  ({:.3f}s, {:>7.2f}/s)  "
                                  "LR: {:.3e}  Data: {:.3f} ({:.3f})".format(
                                      epoch, batch_idx, updates_per_epoch, 100.0 * batch_idx / max(last_idx, 1), losses.val, losses.avg,
-                                     batch_time.val, B * world / batch_time.val, batch_time.avg, B * world / batch_time.avg, cur_lr,
+                                     batch_time.val, B * world / batch_time.val, batch_time.avg, B * world / batch_time.avg, logged_lr(cur_lr),
                                      data_time.val, data_time.avg))
                 if saver is not None and args.recovery_interval and (batch_idx + 1) % args.recovery_interval == 0:
                     saver.save_recovery(epoch, batch_idx, eng.arena.state_dict(), extra=extra_state())
@@ -606,7 +617,7 @@ def main(argv=None, transform=None):
             break
         if primary:
             row = OrderedDict(epoch=epoch, **{"train_" + k: v for k, v in train_metrics.items()}, **{"eval_" + k: v for k, v in eval_metrics.items()},
-                              lr=cur_lr)
+                              lr=logged_lr(cur_lr))
             fn = os.path.join(output_dir, "summary.csv")
             new = not os.path.exists(fn)
             with open(fn, "a") as f:
