@@ -2,7 +2,7 @@
 
 The product path has NO fallback: if the shared library is missing or a symbol
 is absent, importing this module raises.  Field order / types mirror the header
-one to one; ``tests/test_abi.py`` checks every declared symbol is exported.
+one to one; ``tests/test_host.py`` checks every declared symbol is exported.
 """
 from __future__ import annotations
 

@@ -48,7 +48,6 @@ PAD = 64                              # arena offsets are multiples of 64 elemen
 def _empty(shape, dt, device):
     """torch.empty, or NaN / 0xFF-poisoned memory when GIPVIT_POISON=1 (debug: any read of a
     buffer before it was written then shows up as NaN in the loss / gradients)."""
-    import os
     t = torch.empty(shape, dtype=dt, device=device)
     if os.environ.get("GIPVIT_POISON"):
         if dt.is_floating_point:
@@ -323,8 +322,8 @@ class VitGroup:
             self.dxn = e((T, D), act)
             self.dqkv = e((T, 3 * D), act)
             self.do = e((T, D), act)
-            # grouped weight gradients (one launch per block, queued on the side stream while the NEXT block runs): the dY
-            # buffers alternate between two sets by block parity, so a block's set stays untouched until its group has run
+            # a block's weight gradients are one side-stream item that runs while the NEXT block's dX chain does: the dY
+            # buffers alternate between two sets by block parity, so a block's set stays untouched until that item has run
             self.gb3, self.gb4 = e((T, D), act), e((T, D), act)
             self.dh_b, self.dqkv_b = e((T, 4 * D), act), e((T, 3 * D), act)
 
@@ -420,7 +419,7 @@ class VitRunner:
         """``sw``: the switches of the engine that owns this runner (read from the environment when not given)."""
         a = ARCHS[arch]
         self.arch, self.D, self.depth, self.H, self.img_size = arch, a["embed_dim"], a["depth"], a["num_heads"], img_size
-        self.fp32 = fp32    # fp32 operand mode: one f32 kernel per op (no fused Linear + LayerNorm, no grouped dW)
+        self.fp32 = fp32    # fp32 operand mode: one f32 kernel per op (no fused Linear + LayerNorm, no grouped dW launch)
         self.scale = 64 ** -0.5
         self.sw = sw = EngineSwitches.from_env() if sw is None else sw
         # full-row Linear + LayerNorm kernels (csrc/panel.hip) exist for the ViT-S width; GIPVIT_FUSED_LN=0 keeps the
@@ -428,7 +427,8 @@ class VitRunner:
         self.fused = self.D == 384 and not fp32 and sw.fused_ln
         # the four weight-gradient products of a block as ONE split-K launch (gv_linear_dw_group): a quarter of the slab
         # traffic and four times longer k-loops than four launches (ViT-S: 165 us per block at 950 TFLOP/s against
-        # 4 x (51 + 7) us).  GIPVIT_GROUP_DW=0 keeps one launch per product for A/B runs.
+        # 4 x (51 + 7) us).  GIPVIT_GROUP_DW=0 (and the fp32 operand mode) runs the same schedule with four gv_linear
+        # launches in the block's side-stream item instead of the one, for A/B runs.
         self.group_dw = not fp32 and sw.group_dw
         # Only the CLS row of the last block's output feeds the head (vit.pyc@L248-253: forward returns x[:, 0]), so that block's
         # attention projection, MLP and residual adds for the other tokens -- and their whole backward except the K / V path --
@@ -437,8 +437,7 @@ class VitRunner:
         self.cls_last = sw.cls_only_last
         # forward-only passes (teacher, inference) run the MLP as one launch; GIPVIT_FUSED_MLP=0 keeps fc1 / fc2 apart (A/B runs)
         self.fused_mlp = sw.fused_mlp
-        self.partials = _empty((L.LN_PARTIAL_BLOCKS, 3, self.D), f32, device)
-        self.partials_ring = [self.partials] + [_empty((L.LN_PARTIAL_BLOCKS, 3, self.D), f32, device) for _ in range(2)]
+        self.partials_ring = [_empty((L.LN_PARTIAL_BLOCKS, 3, self.D), f32, device) for _ in range(3)]
         self.cs_ws = _empty((64 * 4 * self.D,), f32, device)
         self.one = torch.ones(1, dtype=f32, device=device)
         # split-K slabs per stream: the weight gradients' (on the side stream, or inline when there is none) and those of the
@@ -503,6 +502,29 @@ class VitRunner:
         # D = 384 (ViT-S): proj / fc2 run as full-row products with the residual add AND the LayerNorm that reads the new
         # row next fused into the epilogue (gv_linear_ln_fwd) -- only block 0's norm1 is a stand-alone pass
         fused = self.fused and dp is None
+
+        def norm_args(i, k):
+            """Block i's norm1 / norm2 (k = 1 / 2) as the arguments of the launch that writes the row it reads; all None past the last block."""
+            if i == self.depth:
+                return dict(gamma=None, beta=None, y=None, mean=None, rstd=None)
+            n, s = f"blocks.{i}.norm{k}.", G.slot(i)
+            return dict(gamma=W.f(n + "weight"), beta=W.f(n + "bias"), y=(G.xn1, G.xn2)[k - 1][s], mean=G.stats[s][2 * k - 2], rstd=G.stats[s][2 * k - 1])
+
+        def residual(i, site, a, name, K, resid, out, row_scale, ln):
+            """out = resid + row_scale * dropout(a W^T + bias), the residual add behind block i's ``name`` (attn.proj: dropout site 1,
+            mlp.fc2: site 3), then the LayerNorm ``ln`` of the new row (None: it is not computed here)."""
+            w, bias = W.w(f"blocks.{i}.{name}.weight"), W.f(f"blocks.{i}.{name}.bias")
+            if fused:
+                ops.linear_ln_fwd(a, w, out, T, K, bias=bias, resid=resid, row_scale=row_scale, **ln)
+                return
+            if dp:
+                ops.linear(a, w, G.tmp, T, D, K, epilogue=E.EPI_BIAS, bias=bias)
+                ops.dropout_add(G.tmp, resid, out, T, D, dseed(i, site), dp[0], row_scale=row_scale)
+            else:
+                ops.linear(a, w, out, T, D, K, epilogue=E.EPI_BIAS | E.EPI_RESID, bias=bias, resid=resid, row_scale=row_scale)
+            if ln is not None:
+                ops.layernorm_fwd(out, ln["gamma"], ln["beta"], T, D, y=ln["y"], mean=ln["mean"], rstd=ln["rstd"])
+
         for i in range(self.depth):
             b, s = f"blocks.{i}.", G.slot(i)
             xa, xb, xc = G.xbuf(2 * i), G.xbuf(2 * i + 1), G.xbuf(2 * i + 2)
@@ -526,47 +548,21 @@ class VitRunner:
             if cls_tail and i == self.depth - 1:
                 self._last_block_tail_fwd(W, G, i, xa, on_side)
                 break
-            if fused:
-                ops.linear_ln_fwd(G.o[s], W.w(b + "attn.proj.weight"), xb, T, D, bias=W.f(b + "attn.proj.bias"), resid=xa,
-                                  gamma=W.f(b + "norm2.weight"), beta=W.f(b + "norm2.bias"), y=G.xn2[s], mean=st[2], rstd=st[3], row_scale=rs_a)
-            else:
-                if dp:
-                    ops.linear(G.o[s], W.w(b + "attn.proj.weight"), G.tmp, T, D, D, epilogue=E.EPI_BIAS, bias=W.f(b + "attn.proj.bias"))
-                    ops.dropout_add(G.tmp, xa, xb, T, D, dseed(i, 1), dp[0], row_scale=rs_a)
-                else:
-                    ops.linear(G.o[s], W.w(b + "attn.proj.weight"), xb, T, D, D, epilogue=E.EPI_BIAS | E.EPI_RESID,
-                               bias=W.f(b + "attn.proj.bias"), resid=xa, row_scale=rs_a)
-                ops.layernorm_fwd(xb, W.f(b + "norm2.weight"), W.f(b + "norm2.bias"), T, D, y=G.xn2[s], mean=st[2], rstd=st[3])
+            residual(i, 1, G.o[s], "attn.proj", D, xa, xb, rs_a, norm_args(i, 2))
+            # fused: the launch that ends the block also runs the NEXT block's norm1 on the row it has just written
+            ln_next = norm_args(i + 1, 1) if fused else None
             if fused and self.fused_mlp and not G.save:
                 # a pass that keeps no activations (the teacher, inference): fc1 -> GELU -> fc2 -> + residual -> the next norm1 in ONE
                 # launch (gv_mlp_ln_fwd); the [T, 4 D] activation never reaches HBM
-                nxt = i + 1 < self.depth
-                nb, ns = f"blocks.{i + 1}.", G.slot(i + 1)
                 ops.mlp_ln_fwd(G.xn2[s], W.w(b + "mlp.fc1.weight"), W.f(b + "mlp.fc1.bias"), W.w(b + "mlp.fc2.weight"), xc, T, D, 4 * D,
-                               bias2=W.f(b + "mlp.fc2.bias"), resid=xb, gamma=W.f(nb + "norm1.weight") if nxt else None,
-                               beta=W.f(nb + "norm1.bias") if nxt else None, y=G.xn1[ns] if nxt else None,
-                               mean=G.stats[ns][0] if nxt else None, rstd=G.stats[ns][1] if nxt else None, row_scale=rs_m)
-                if i >= tok0:
-                    capture_tokens(i, xc)
-                continue
-            ops.linear(G.xn2[s], W.w(b + "mlp.fc1.weight"), G.h[s], T, 4 * D, D,
-                       epilogue=E.EPI_BIAS | E.EPI_GELU | (E.EPI_SAVE_PRE if G.save else 0),   # a forward-only group keeps no pre-activation
-                       bias=W.f(b + "mlp.fc1.bias"), aux_out=G.hp[s] if G.save else None)
-            if dp:
-                ops.dropout(G.h[s], dseed(i, 2), dp[0], n=T * 4 * D)
-            if fused:
-                nxt = i + 1 < self.depth
-                nb, ns = f"blocks.{i + 1}.", G.slot(i + 1)
-                ops.linear_ln_fwd(G.h[s], W.w(b + "mlp.fc2.weight"), xc, T, 4 * D, bias=W.f(b + "mlp.fc2.bias"), resid=xb,
-                                  gamma=W.f(nb + "norm1.weight") if nxt else None, beta=W.f(nb + "norm1.bias") if nxt else None,
-                                  y=G.xn1[ns] if nxt else None, mean=G.stats[ns][0] if nxt else None, rstd=G.stats[ns][1] if nxt else None,
-                                  row_scale=rs_m)
-            elif dp:
-                ops.linear(G.h[s], W.w(b + "mlp.fc2.weight"), G.tmp, T, D, 4 * D, epilogue=E.EPI_BIAS, bias=W.f(b + "mlp.fc2.bias"))
-                ops.dropout_add(G.tmp, xb, xc, T, D, dseed(i, 3), dp[0], row_scale=rs_m)
+                               bias2=W.f(b + "mlp.fc2.bias"), resid=xb, row_scale=rs_m, **ln_next)
             else:
-                ops.linear(G.h[s], W.w(b + "mlp.fc2.weight"), xc, T, D, 4 * D, epilogue=E.EPI_BIAS | E.EPI_RESID,
-                           bias=W.f(b + "mlp.fc2.bias"), resid=xb, row_scale=rs_m)
+                ops.linear(G.xn2[s], W.w(b + "mlp.fc1.weight"), G.h[s], T, 4 * D, D,
+                           epilogue=E.EPI_BIAS | E.EPI_GELU | (E.EPI_SAVE_PRE if G.save else 0),   # a forward-only group keeps no pre-activation
+                           bias=W.f(b + "mlp.fc1.bias"), aux_out=G.hp[s] if G.save else None)
+                if dp:
+                    ops.dropout(G.h[s], dseed(i, 2), dp[0], n=T * 4 * D)
+                residual(i, 3, G.h[s], "mlp.fc2", 4 * D, xb, xc, rs_m, ln_next)
             if i >= tok0:
                 capture_tokens(i, xc)
         xl = G.xbuf(2 * self.depth)
@@ -611,11 +607,8 @@ class VitRunner:
             G.alloc_cls()
             G.do.zero_()
         else:
-            (G.gb3 if (self.group_dw and ((self.depth - 1) & 1)) else G.gb).zero_()
+            (G.gb3 if (self.depth - 1) & 1 else G.gb).zero_()      # the last block's MLP-half dY (backward: sets[parity][0])
         G.prepared = True
-
-    def _fin3(self, dgamma, dbeta, dbias):
-        ops.ln_finalize(self.partials, L.LN_PARTIAL_BLOCKS, self.D, dgamma, dbeta, dbias)
 
     # ---- backward from d(CLS features) bf16 [G.n_img, D]; gradients ACCUMULATE into the arena
     def backward(self, W: Weights, G: VitGroup, dfeat: torch.Tensor, on_block_done=None):
@@ -624,7 +617,6 @@ class VitRunner:
         D, T, H = self.D, G.T, self.H
         E = L
         ACC = E.EPI_ACCUM
-        grouped = self.group_dw
         # --drop: the gradient entering a dropout site carries that site's mask (regenerated from the step seed); the bias gradients
         # of attn.proj / mlp.fc2 are then column sums of the MASKED gradient, not LayerNorm backward's third sum
         dp = G.dropout
@@ -635,7 +627,7 @@ class VitRunner:
             ops.dropout(gb, dseed(layer, site), dp[0], n=T * D)
             ops.colsum(gb, T, D, self.cs_ws, bias_grad, accumulate=True)
         sets = ((G.gb, G.gb2, G.dh, G.dqkv), (G.gb3, G.gb4, G.dh_b, G.dqkv_b))      # per block parity: dY of the MLP / attention half, dh, dqkv
-        gb_first = sets[(self.depth - 1) & 1][0] if grouped else G.gb
+        gb_first = sets[(self.depth - 1) & 1][0]
         cls_tail = self._cls_tail(G)          # the last block ran its projection / MLP on the CLS rows only (forward): so does its backward
         if not G.prepared:
             self.prepare_backward(G)
@@ -643,17 +635,19 @@ class VitRunner:
         xl = G.x[2 * self.depth]
         # stochastic depth: the bf16 gradient handed to a branch carries that branch's row factor (rs[i, 0] attention, rs[i, 1] MLP)
         rs = G.rs
+        ring = self.partials_ring
         for sg in G.segs:
             # (the final norm touches the CLS rows only, one per image: the per-image factors are its row factors)
             im = slice(sg.img0, sg.img0 + sg.n_img)
             if cls_tail:
-                ops.layernorm_bwd(dfeat[im], G.c_xc[im], sg.fstats[0], sg.fstats[1], W.f("norm.weight"), G.c_g[im], G.c_gb[im], self.partials,
+                ops.layernorm_bwd(dfeat[im], G.c_xc[im], sg.fstats[0], sg.fstats[1], W.f("norm.weight"), G.c_g[im], G.c_gb[im], ring[0],
                                   sg.n_img, D, g_init=True, gb_scale=None if rs is None else G.drop_img[self.depth - 1, 1, im])
             else:
                 ops.layernorm_bwd(dfeat[im], sg.rows(xl), sg.fstats[0], sg.fstats[1], W.f("norm.weight"), sg.rows(G.g),
-                                  sg.rows(gb_first), self.partials, sg.n_img, D, x_stride=sg.N * D, g_stride=sg.N * D, gb_stride=sg.N * D, g_init=True,
+                                  sg.rows(gb_first), ring[0], sg.n_img, D, x_stride=sg.N * D, g_stride=sg.N * D, gb_stride=sg.N * D, g_init=True,
                                   gb_scale=None if rs is None else G.drop_img[self.depth - 1, 1, im])
-            self._fin3(W.g("norm.weight"), W.g("norm.bias"), None if dp else W.g(f"blocks.{self.depth - 1}.mlp.fc2.bias"))
+            ops.ln_finalize(ring[0], L.LN_PARTIAL_BLOCKS, D, W.g("norm.weight"), W.g("norm.bias"),
+                            None if dp else W.g(f"blocks.{self.depth - 1}.mlp.fc2.bias"))
         # The weight-gradient GEMMs are off the critical path (nothing in backward consumes dW):
         # they run on a side stream beside the dX chain, so their tiles fill the tail of every
         # main-stream kernel (a 345 x 3-tile GEMM occupies 2.02 rounds of the 512 workgroup slots).
@@ -661,15 +655,10 @@ class VitRunner:
         sx = SideStream(self.side if xl.is_cuda else None, self._events)
         join = sx.join
 
-        def dw(A, Bm, Cg, M, N, colsum_a=None):
-            """dW (+)= A^T Bm on the side stream once main's work so far is done; returns the event that marks its end."""
-            return sx.run(lambda: ops.linear(A, Bm, Cg, M, N, T, trans_a=True, trans_b=True, epilogue=ACC, colsum_a=colsum_a,
-                                             workspace=self.ws_side))
-
         # LayerNorm backward leaves per-block column sums in a partials buffer; folding them into the gamma / beta /
         # bias gradients (ln_finalize) is parameter-gradient work too, so it also goes to the side stream.  Three
         # partials buffers rotate; one is rewritten only after the finalize that read it (three calls ago) has run.
-        ring, fin_ev, ring_i, last_fin = self.partials_ring, [None, None, None], 0, None
+        fin_ev, ring_i, last_fin = [None, None, None], 0, None
 
         def ln_bwd(dy, x, mean, rstd, gamma, gb, d0, d1, d2, dx_of=None, gb_scale=None, rows=None, g=None):
             """LayerNorm backward into the residual gradient.  ``dx_of = (dY, W, K)``: the dX product that produces ``dy``
@@ -695,13 +684,22 @@ class VitRunner:
                 # there, so a data-parallel all-reduce queues behind the dW products and main never waits
                 sx.then(lambda: on_block_done(i))
 
+        def block_dw(probs):
+            """The block's four weight gradients dW (+)= dY^T X (bias gradient: the column sums of dY), one side-stream item."""
+            if self.group_dw:
+                ops.linear_dw_group(probs, T, self.ws_side)
+                return
+            for dY, X, dW, cs in probs:
+                ops.linear(dY, X, dW, dY.shape[1], X.shape[1], T, trans_a=True, trans_b=True, epilogue=ACC, colsum_a=cs, workspace=self.ws_side)
+
         done_grp = [None, None]
-        for i in reversed(range(self.depth) if grouped else ()):
+        for i in reversed(range(self.depth)):
             b, st = f"blocks.{i}.", G.stats[i]
             par = i & 1
             gb_mlp, gb_att, dh, dqkv = sets[par]
             gb_next = sets[par ^ 1][0]                    # dY of block i - 1's MLP half
-            join(done_grp[par])                           # block i + 2's group read this parity's buffers
+            segs = [(sg.n_img, sg.N, sg.lse[i]) for sg in G.segs]
+            join(done_grp[par])                           # block i + 2's weight gradients read this parity's buffers
             if cls_tail and i == self.depth - 1:
                 # ---- last block, CLS rows only (forward: _last_block_tail_fwd): MLP and projection backward over n_img rows; the
                 # attention backward and the qkv product's dX + norm1 backward then run over all tokens as in every block, with
@@ -715,20 +713,19 @@ class VitRunner:
                 G.scatter_cls(G.c_do, G.do)           # (G.do was zeroed by prepare_backward)
                 G.scatter_cls(G.c_g, G.g)                 # (G.g was zeroed above)
                 # dO is zero behind every image's CLS row: the attention backward skips the other queries (their dQ rows come out zero)
-                ops.attention_bwd_varlen(G.qkv[i], G.o[i], G.do, dqkv, [(sg.n_img, sg.N, sg.lse[i]) for sg in G.segs], H, self.scale,
-                                         q_limit=1 if self.sw.cls_qlimit else 0)
+                ops.attention_bwd_varlen(G.qkv[i], G.o[i], G.do, dqkv, segs, H, self.scale, q_limit=1 if self.sw.cls_qlimit else 0)
                 ln_bwd(G.dxn, G.x[2 * i], st[0], st[1], W.f(b + "norm1.weight"), gb_next,
                        W.g(b + "norm1.weight"), W.g(b + "norm1.bias"), W.g(f"blocks.{i - 1}.mlp.fc2.bias") if i > 0 else None,
                        dx_of=(dqkv, W.w(b + "attn.qkv.weight"), 3 * D), gb_scale=None if (rs is None or i == 0) else rs[i - 1, 1])
 
-                def last_block_dw():
+                def tail_dw():
                     # three weight gradients reduce over the n CLS rows, the qkv one over all tokens
                     ops.linear(G.c_gb, G.c_h, W.g(b + "mlp.fc2.weight"), D, 4 * D, n, trans_a=True, trans_b=True, epilogue=ACC, workspace=self.ws_side)
                     ops.linear(G.c_dh, G.c_xn2, W.g(b + "mlp.fc1.weight"), 4 * D, D, n, trans_a=True, trans_b=True, epilogue=ACC,
                                colsum_a=W.g(b + "mlp.fc1.bias"), workspace=self.ws_side)
                     ops.linear(G.c_gb_att, G.c_o, W.g(b + "attn.proj.weight"), D, D, n, trans_a=True, trans_b=True, epilogue=ACC, workspace=self.ws_side)
                     ops.linear_dw_group([(dqkv, G.xn1[i], W.g(b + "attn.qkv.weight"), W.g(b + "attn.qkv.bias"))], T, self.ws_side)
-                done_grp[par] = sx.run(last_block_dw)
+                done_grp[par] = sx.run(tail_dw)
                 report(i)
                 continue
             if dp:
@@ -742,53 +739,20 @@ class VitRunner:
             if dp:
                 drop_branch_grad(gb_att, i, 1, W.g(b + "attn.proj.bias"))
             ops.linear(gb_att, W.w(b + "attn.proj.weight"), G.do, T, D, D, trans_b=True)
-            ops.attention_bwd_varlen(G.qkv[i], G.o[i], G.do, dqkv, [(sg.n_img, sg.N, sg.lse[i]) for sg in G.segs], H, self.scale)
+            ops.attention_bwd_varlen(G.qkv[i], G.o[i], G.do, dqkv, segs, H, self.scale)
             # the block's four dY operands are final once the attention backward has run: its weight gradients go to the side stream
             # BEFORE the last kernel of the block's dX chain (which only reads dqkv), one kernel earlier than the chain's end
             probs = [(gb_mlp, G.h[i], W.g(b + "mlp.fc2.weight"), None),
                      (dh, G.xn2[i], W.g(b + "mlp.fc1.weight"), W.g(b + "mlp.fc1.bias")),
                      (gb_att, G.o[i], W.g(b + "attn.proj.weight"), None),
                      (dqkv, G.xn1[i], W.g(b + "attn.qkv.weight"), W.g(b + "attn.qkv.bias"))]
-            done_grp[par] = sx.run(lambda: ops.linear_dw_group(probs, T, self.ws_side))
-            join(done_grp[par ^ 1])                       # block i + 1's group read gb_next (its MLP-half dY)
+            done_grp[par] = sx.run(lambda: block_dw(probs))
+            join(done_grp[par ^ 1])                       # block i + 1's weight gradients read gb_next (its MLP-half dY)
             ln_bwd(G.dxn, G.x[2 * i], st[0], st[1], W.f(b + "norm1.weight"), gb_next,
                    W.g(b + "norm1.weight"), W.g(b + "norm1.bias"), W.g(f"blocks.{i - 1}.mlp.fc2.bias") if (i > 0 and not dp) else None,
                    dx_of=(dqkv, W.w(b + "attn.qkv.weight"), 3 * D), gb_scale=None if (rs is None or i == 0) else rs[i - 1, 1])
             report(i)
-        join(done_grp[0]); join(done_grp[1])
-
-        gbs = (G.gb, G.gb2)              # gb: dY of the MLP half, gb2: dY of the attention half
-        done_fc1 = done_qkv = done_fc2 = done_proj = None
-        for i in reversed(range(self.depth) if not grouped else ()):
-            b, st = f"blocks.{i}.", G.stats[i]
-            # MLP
-            join(done_fc1)               # last block's dW_fc1 read dh
-            if dp:
-                drop_branch_grad(gbs[0], i, 3, W.g(b + "mlp.fc2.bias"))
-            ops.linear(gbs[0], W.w(b + "mlp.fc2.weight"), G.dh, T, 4 * D, D, trans_b=True, epilogue=E.EPI_DGELU, aux_in=G.hp[i])
-            if dp:
-                ops.dropout(G.dh, dseed(i, 2), dp[0], n=T * 4 * D)
-            done_fc2 = dw(gbs[0], G.h[i], W.g(b + "mlp.fc2.weight"), D, 4 * D)
-            done_fc1 = dw(G.dh, G.xn2[i], W.g(b + "mlp.fc1.weight"), 4 * D, D, colsum_a=W.g(b + "mlp.fc1.bias"))
-            join(done_proj)              # last block's dW_proj read gb2
-            ln_bwd(G.dxn, G.x[2 * i + 1], st[2], st[3], W.f(b + "norm2.weight"), gbs[1],
-                   W.g(b + "norm2.weight"), W.g(b + "norm2.bias"), None if dp else W.g(b + "attn.proj.bias"),
-                   dx_of=(G.dh, W.w(b + "mlp.fc1.weight"), 4 * D), gb_scale=None if rs is None else rs[i, 0])
-            if dp:
-                drop_branch_grad(gbs[1], i, 1, W.g(b + "attn.proj.bias"))
-            # attention
-            ops.linear(gbs[1], W.w(b + "attn.proj.weight"), G.do, T, D, D, trans_b=True)
-            done_proj = dw(gbs[1], G.o[i], W.g(b + "attn.proj.weight"), D, D)
-            join(done_qkv)               # last block's dW_qkv read dqkv
-            for sg in G.segs:
-                ops.attention_bwd(sg.rows(G.qkv[i]), sg.rows(G.o[i]), sg.rows(G.do), sg.lse[i], sg.n_img, sg.N, H, self.scale, dqkv=sg.rows(G.dqkv))
-            done_qkv = dw(G.dqkv, G.xn1[i], W.g(b + "attn.qkv.weight"), 3 * D, D, colsum_a=W.g(b + "attn.qkv.bias"))
-            join(done_fc2)               # this block's dW_fc2 read gb
-            ln_bwd(G.dxn, G.x[2 * i], st[0], st[1], W.f(b + "norm1.weight"), gbs[0],
-                   W.g(b + "norm1.weight"), W.g(b + "norm1.bias"), W.g(f"blocks.{i - 1}.mlp.fc2.bias") if (i > 0 and not dp) else None,
-                   dx_of=(G.dqkv, W.w(b + "attn.qkv.weight"), 3 * D), gb_scale=None if (rs is None or i == 0) else rs[i - 1, 1])
-            report(i)
-        join(done_qkv)          # every dW product is in (the side stream runs them in order); ws_side is free again
+        join(done_grp[0]); join(done_grp[1])    # every dW product is in (the side stream runs them in order); ws_side is free again
         join(last_fin)          # ... and the last finalize
         if dp:
             ops.dropout(G.g, dseed(0, 0), dp[0], n=T * D)                                 # pos_drop's mask on the token gradient
@@ -893,10 +857,58 @@ class NoReducer:
         pass
 
 
+def operand_mode(precision: str):
+    """``precision`` "bf16" | "fp32" -> (fp32 operand mode?, element type of the activation buffers)."""
+    if precision not in ("bf16", "fp32"):
+        raise ValueError(f"precision {precision!r}: 'bf16' or 'fp32'")
+    return precision == "fp32", (f32 if precision == "fp32" else bf16)
+
+
+def _prefixed(backbone: Dict[str, torch.Tensor], head: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The two state dicts of a DINO network under their arena names."""
+    st = {"backbone." + k: v for k, v in backbone.items()}
+    st.update({"head." + k: v for k, v in head.items()})
+    return st
+
+
+class TrainEngine:
+    """What the two training engines share: the precision / clip-mode arguments and the loss scaler, the gradients handed out,
+    and the clip / loss-scale part of the optimizer's arguments."""
+
+    def _set_modes(self, precision: str, clip_mode: str, clip_modes: Sequence[str], dev):
+        """-> (fp32, act) of ``operand_mode``; sets ``precision``, ``clip_mode`` (train.py:1072-1077) and ``scaler``."""
+        if clip_mode not in clip_modes:
+            raise ValueError(f"clip_mode {clip_mode!r}: one of {', '.join(clip_modes)} (train.py:1072-1077)")
+        fp32, act = operand_mode(precision)
+        self.precision, self.clip_mode = precision, clip_mode
+        # the float16 library build (--amp --amp-dtype float16) trains under dynamic loss scaling: torch's GradScaler on the device
+        # (via timm NativeScaler, reference train.py:585-602, 1061-1070)
+        self.scaler = ops.LossScaler(dev) if (L.ACT_FORMAT == "f16" and not fp32) else None
+        return fp32, act
+
+    def grads(self) -> Dict[str, torch.Tensor]:
+        """Copies of the parameter gradients of the last forward_backward.  Under float16 loss scaling the arena holds S x gradient:
+        the copies are divided by the scale in force (call before optimizer_step, whose scaler update may change S)."""
+        inv = None if self.scaler is None else 1.0 / self.scaler.state[0]
+        return {n: self.arena.view(self.arena.g, n).detach().clone() if inv is None else self.arena.view(self.arena.g, n).detach() * inv
+                for n in self.arena.specs}
+
+    def _clip_args(self) -> dict:
+        """The optimizer launches' clip_norm / gnorm_sq / clip_value / loss_scale arguments; queues the gradient's sum of squares
+        when they need it (under loss scaling it is also the finite check of GradScaler.step())."""
+        by_norm = self.clip > 0 and self.clip_mode == "norm"
+        scaled = self.scaler is not None
+        if by_norm or scaled:
+            ops.sumsq(self.arena.g, self.red_ws, self.gnorm_sq)
+        return dict(clip_norm=self.clip if by_norm else 0.0, gnorm_sq=self.gnorm_sq if (by_norm or scaled) else None,
+                    clip_value=self.clip if (self.clip > 0 and self.clip_mode == "value") else 0.0,
+                    loss_scale=self.scaler.scale if scaled else None)
+
+
 # --------------------------------------------------------------------------- #
 # one DINO multi-crop training step (paper Alg. 1; SURVEY rows D1-D5, S1)
 # --------------------------------------------------------------------------- #
-class DinoEngine:
+class DinoEngine(TrainEngine):
     def __init__(self, arch="vit_small", img_size=224, out_dim=65536, batch=64, tile=256, n_global=2, n_local=8,
                  gsize=224, lsize=96, hidden=2048, bottleneck=256, lr=5e-4, weight_decay=0.04, betas=(0.9, 0.999), eps=1e-8,
                  momentum_teacher=0.996, student_temp=0.1, teacher_temp=0.04, center_momentum=0.9, clip_grad: float = 0.0,
@@ -904,17 +916,8 @@ class DinoEngine:
         """``precision``: "bf16" (the training path) or "fp32" (every GEMM / attention operand, the head activations, the
         weight-normalised prototype matrix and the logit gradient in f32 -- the verification mode of SURVEY 8d's fp32 column).
         ``clip_mode``: "norm" (global norm, the reference default) or "value" (element-wise clamp), train.py:1072-1077."""
-        if clip_mode not in ("norm", "value"):
-            raise ValueError(f"clip_mode {clip_mode!r}: 'norm' or 'value'")
-        self.clip_mode = clip_mode
-        if precision not in ("bf16", "fp32"):
-            raise ValueError(f"precision {precision!r}: 'bf16' or 'fp32'")
-        fp32 = precision == "fp32"
-        act = f32 if fp32 else bf16
-        self.precision = precision
         dev = torch.device(device)
-        # the float16 library build (--amp --amp-dtype float16) trains under dynamic loss scaling: torch's GradScaler on the device
-        self.scaler = ops.LossScaler(dev) if (L.ACT_FORMAT == "f16" and not fp32) else None
+        fp32, act = self._set_modes(precision, clip_mode, ("norm", "value"), dev)
         self.dev, self.arch, self.B, self.tile = dev, arch, batch, tile
         D = ARCHS[arch]["embed_dim"]
         self.D, self.K, self.G, self.V = D, out_dim, n_global, n_global + n_local
@@ -959,24 +962,19 @@ class DinoEngine:
         # contiguous arena range of every block's weight-decayed matrices (arena order = backward order)
         self._block_range = {}
         for i in range(ARCHS[arch]["depth"]):
-            names = [n for n in self.arena.order if n.startswith(f"backbone.blocks.{i}.") and self.arena.off[n] < self.arena.n_decay]
-            self._block_range[i] = (min(self.arena.off[n] for n in names),
-                                    max(self.arena.off[n] + _round_up(math.prod(self.arena.specs[n]), PAD) for n in names))
+            spans = [self.arena.span(n) for n in self.arena.order if n.startswith(f"backbone.blocks.{i}.") and self.arena.off[n] < self.arena.n_decay]
+            self._block_range[i] = (min(lo for lo, _ in spans), max(hi for _, hi in spans))
 
     # ---- parameters ----------------------------------------------------------------
     def load_state(self, backbone: Dict[str, torch.Tensor], head: Dict[str, torch.Tensor]):
-        st = {"backbone." + k: v for k, v in backbone.items()}
-        st.update({"head." + k: v for k, v in head.items()})
-        self.arena.load(st)
+        self.arena.load(_prefixed(backbone, head))
         self.arena.t.copy_(self.arena.p)            # teacher starts as a copy of the student
         self.refresh_bf16()
 
     def load_teacher_state(self, backbone: Dict[str, torch.Tensor], head: Dict[str, torch.Tensor], center: Optional[torch.Tensor] = None):
         """Restore the EMA teacher (and the centre) of a saved run: without it a resumed run would restart the
         teacher from the student while the momentum schedule is already near 1."""
-        st = {"backbone." + k: v for k, v in backbone.items()}
-        st.update({"head." + k: v for k, v in head.items()})
-        self.arena.load(st, self.arena.t)
+        self.arena.load(_prefixed(backbone, head), self.arena.t)
         if center is not None:
             self.center.copy_(center.to(self.center.device, f32).view(-1))
         self.refresh_bf16()
@@ -996,13 +994,6 @@ class DinoEngine:
 
     def head_state_dict(self, teacher: bool = False):
         return self.arena.state_dict(self.arena.t if teacher else self.arena.p, "head.")
-
-    def grads(self) -> Dict[str, torch.Tensor]:
-        """Copies of the parameter gradients of the last forward_backward.  Under float16 loss scaling the arena holds S x gradient:
-        the copies are divided by the scale in force (call before optimizer_step, whose scaler update may change S)."""
-        inv = None if self.scaler is None else 1.0 / self.scaler.state[0]
-        return {n: self.arena.view(self.arena.g, n).detach().clone() if inv is None else self.arena.view(self.arena.g, n).detach() * inv
-                for n in self.arena.specs}
 
     # ---- the step --------------------------------------------------------------------
     def set_drop_path(self, per_img: Optional[torch.Tensor]):
@@ -1142,14 +1133,7 @@ class DinoEngine:
 
     def optimizer_step(self):
         a = self.arena
-        by_norm = self.clip > 0 and self.clip_mode == "norm"
-        scaled = self.scaler is not None
-        if by_norm or scaled:           # loss scaling: the sum of squares is also the finite check of GradScaler.step()
-            ops.sumsq(a.g, self.red_ws, self.gnorm_sq)
-        kw = dict(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, step=max(self.t, 1),
-                  clip_norm=self.clip if by_norm else 0.0, gnorm_sq=self.gnorm_sq if (by_norm or scaled) else None, hyper=self.hyper,
-                  clip_value=self.clip if (self.clip > 0 and self.clip_mode == "value") else 0.0,
-                  loss_scale=self.scaler.scale if scaled else None)
+        kw = dict(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, step=max(self.t, 1), hyper=self.hyper, **self._clip_args())
         lo = 0
         if not self.train_last_layer:
             # the head's last layer is frozen for the first epochs (DINO cancel_gradients_last_layer sets its grad to
@@ -1165,7 +1149,7 @@ class DinoEngine:
         if a.n > a.n_decay:   # biases / LN / pos / cls: same schedules, weight-decay multiplier 0
             sl = slice(a.n_decay, a.n)
             ops.adamw_ema(a.p[sl], a.g[sl], a.m[sl], a.v[sl], a.pb[sl], a.t[sl], a.tb[sl], a.n - a.n_decay, weight_decay=0.0, **kw)
-        if scaled:
+        if self.scaler is not None:
             self.scaler.update(self.gnorm_sq)
         self._refresh_wn()
         ops.center_update(self.center, self.center_sum, self.K, self.cm, 1.0 / (self.G * self.B * self.reducer.world * self._n_micro))
@@ -1202,7 +1186,7 @@ class DinoEngine:
 # --------------------------------------------------------------------------- #
 # supervised single-crop step (reference train.py:1044-1078; BASELINE config 1)
 # --------------------------------------------------------------------------- #
-class SupervisedEngine:
+class SupervisedEngine(TrainEngine):
     """ViT + Linear head, softmax -> LabelSmoothingCE (the reference's actual loss path); with a mix plan (gipvit.mixup) the batch
     is mixed inside the patchify pass and the loss is SoftTargetCE / BCE on the mixup target (train.py:832-842, 1037-1040)."""
 
@@ -1221,24 +1205,15 @@ class SupervisedEngine:
         rate for every layer, the two-launch optimizer pass.  A number (1.0 included) gives layer ``id`` the rate
         ``lr * layer_decay ** (depth + 2 - id)`` and makes ``optimizer_step`` ONE gv_adamw_ema_ranges launch over a range table
         (adamw / adam / sgd) or hands gv_lamb a per-tensor rate; ``layer_scales`` / ``mean_lr`` show the result."""
-        if precision not in ("bf16", "fp32"):
-            raise ValueError(f"precision {precision!r}: 'bf16' or 'fp32'")
         if loss not in ("lsce", "soft_ce", "bce"):
             raise ValueError(f"loss {loss!r}: 'lsce', 'soft_ce' or 'bce' (train.py:832-842)")
         if bce_target_thresh is not None and loss != "bce":
             raise ValueError("bce_target_thresh goes with loss='bce' (timm BinaryCrossEntropy's target_threshold)")
         self.loss_kind, self.bce_target_thresh = loss, bce_target_thresh
-        if clip_mode not in ("norm", "value", "agc"):
-            raise ValueError(f"clip_mode {clip_mode!r}: 'norm', 'value' or 'agc' (train.py:1072-1077)")
         if clip_mode == "value" and opt == "lamb":
             raise ValueError("--clip-mode value with --opt lamb is not built (Lamb's own global-norm clip needs the norm of the clamped gradient)")
-        self.clip_mode = clip_mode
-        fp32 = precision == "fp32"
-        act = f32 if fp32 else bf16
-        self.precision = precision
         dev = torch.device(device)
-        # float16 library build: dynamic loss scaling (torch GradScaler via timm NativeScaler, reference train.py:585-602, 1061-1070)
-        self.scaler = ops.LossScaler(dev) if (L.ACT_FORMAT == "f16" and not fp32) else None
+        fp32, act = self._set_modes(precision, clip_mode, ("norm", "value", "agc"), dev)
         if self.scaler is not None and (opt == "lamb" or clip_mode == "agc"):
             raise ValueError("float16 loss scaling is built for adamw / adam / sgd with --clip-mode norm | value; "
                              "--opt lamb and --clip-mode agc run with --amp-dtype bfloat16")
@@ -1332,19 +1307,13 @@ class SupervisedEngine:
         """--drop for the next training steps' forward / backward: probability and the step's 32-bit seed (evaluation: p = 0)."""
         self.grp.set_dropout(p, seed)
 
-    def grads(self):
-        """As DinoEngine.grads: the gradient itself, whatever the loss scale."""
-        inv = None if self.scaler is None else 1.0 / self.scaler.state[0]
-        return {n: self.arena.view(self.arena.g, n).detach().clone() if inv is None else self.arena.view(self.arena.g, n).detach() * inv
-                for n in self.arena.specs}
-
-    def forward(self, tiles_u8, ema: bool = False, fill=None):
+    def forward(self, tiles_u8, ema: bool = False, fill=None, mix=None):
         """Inference / features: returns (logits f32 [B,C], CLS features bf16 [B,D]); ``ema``: with the EMA weights.
         ``tiles_u8``: uint8 NHWC [B, H, W, 3] or float32 NCHW [B, 3, H, W] already normalised (engine.input_form); the
-        image is its top-left img_size window."""
+        image is its top-left img_size window.  ``mix``: a training step's gipvit.mixup.MixPlan (forward_backward)."""
         B, C, D, W = self.B, self.C, self.D, (self.Wema if ema else self.W)
         input_form(tiles_u8, B, None, (("fill", fill),))
-        self.vit.forward(W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats, fill=fill)
+        self.vit.forward(W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats, fill=fill, mix=None if mix is None else mix.table)
         ops.small_matmul(self.feats, W.f("head.weight"), self.logits, B, C, D, sam=D, sak=1, sbk=1, sbn=D, bias=W.f("head.bias"))
         return self.logits, self.feats
 
@@ -1355,12 +1324,7 @@ class SupervisedEngine:
         if mix is not None and self.loss_kind == "lsce":
             raise ValueError("mix= needs loss='soft_ce' or 'bce': label-smoothing cross-entropy takes hard labels (train.py:832-842)")
         self.arena.g.zero_()
-        if mix is None:
-            self.forward(tiles_u8, fill=fill)
-        else:
-            input_form(tiles_u8, B, None, (("fill", fill),))
-            self.vit.forward(W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats, fill=fill, mix=mix.table)
-            ops.small_matmul(self.feats, W.f("head.weight"), self.logits, B, C, D, sam=D, sak=1, sbk=1, sbn=D, bias=W.f("head.bias"))
+        self.forward(tiles_u8, fill=fill, mix=mix)
         loss_scale = self.scaler.scale if self.scaler is not None else None
         if self.loss_kind == "lsce":
             ops.softmax_lsce(self.logits, target.view(-1), self.loss, self.dlogits, self.prob, B, C, self.smoothing, loss_scale=loss_scale)
@@ -1380,18 +1344,10 @@ class SupervisedEngine:
     def optimizer_step(self, lr=None):
         a = self.arena
         self.t += 1
-        by_norm = self.clip > 0 and self.clip_mode == "norm"
         if self.clip > 0 and self.clip_mode == "agc":
             ops.agc(a.p, a.g, self._agc_units, self.clip, 1e-3, 1.0 / self.reducer.world)
-        scaled = self.scaler is not None
-        if by_norm or scaled:
-            ops.sumsq(a.g, self.red_ws, self.gnorm_sq)
         kw = dict(lr=self.lr if lr is None else lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, step=self.t,
-                  grad_scale=1.0 / self.reducer.world, clip_norm=self.clip if by_norm else 0.0,
-                  gnorm_sq=self.gnorm_sq if (by_norm or scaled) else None,
-                  mode=self.opt_mode, teacher_momentum=self.ema_decay or 0.0,
-                  clip_value=self.clip if (self.clip > 0 and self.clip_mode == "value") else 0.0,
-                  loss_scale=self.scaler.scale if scaled else None)
+                  grad_scale=1.0 / self.reducer.world, mode=self.opt_mode, teacher_momentum=self.ema_decay or 0.0, **self._clip_args())
         tt = (lambda sl: (a.t[sl], a.tb[sl])) if a.t is not None else (lambda sl: (None, None))
         if self.opt_mode < 0:
             if not self.train_backbone:
@@ -1399,7 +1355,7 @@ class SupervisedEngine:
             ops.sumsq(a.g, self.red_ws, self.gnorm_sq)              # Lamb clips by the global norm itself (max_grad_norm = 1)
             self._lamb_stats.zero_()
             kl = dict(lr=kw["lr"], beta1=kw["beta1"], beta2=kw["beta2"], eps=self.eps, step=self.t, grad_scale=kw["grad_scale"],
-                      clip_norm=self.clip if by_norm else 0.0, max_grad_norm=self.lamb_max_grad_norm, teacher_momentum=self.ema_decay or 0.0)
+                      clip_norm=kw["clip_norm"], max_grad_norm=self.lamb_max_grad_norm, teacher_momentum=self.ema_decay or 0.0)
             for phase in (0, 1):
                 for tab, wd in zip(self._lamb_tabs, (self.wd, 0.0)):
                     if tab.shape[0]:
@@ -1410,7 +1366,7 @@ class SupervisedEngine:
             # --layer-decay: every (layer, decay | no-decay) range at its own rate, one launch (gv_adamw_ema_ranges)
             _, blocks, rows = self._ld[bool(self.train_backbone)]
             ops.adamw_ema_ranges(a.p, a.g, a.m, a.v, a.pb, a.t, a.tb, a.n, blocks, rows, weight_decay=self.wd, **kw)
-            if scaled:
+            if self.scaler is not None:
                 self.scaler.update(self.gnorm_sq)
             return
         if self.train_backbone:
@@ -1423,7 +1379,7 @@ class SupervisedEngine:
         for lo, hi, wd in ranges:
             sl = slice(lo, hi)
             ops.adamw_ema(a.p[sl], a.g[sl], a.m[sl], a.v[sl], a.pb[sl], *tt(sl), hi - lo, weight_decay=wd, **kw)
-        if scaled:
+        if self.scaler is not None:
             self.scaler.update(self.gnorm_sq)
 
     def step(self, tiles_u8, target, lr=None, fill=None, mix=None):
@@ -1448,10 +1404,9 @@ class FeatureExtractor:
     def __init__(self, arch="vit_small", img_size=256, batch=256, num_classes=0, mean=MEAN_RON, std=STD_RON, device="cuda:0",
                  weights: Optional[Weights] = None, precision: str = "bf16"):
         """``precision``: as for the engines; with ``weights`` it follows the owning engine's mode."""
-        if precision not in ("bf16", "fp32"):
-            raise ValueError(f"precision {precision!r}: 'bf16' or 'fp32'")
-        fp32 = weights.fp32 if weights is not None else precision == "fp32"
-        act = f32 if fp32 else bf16
+        fp32, act = operand_mode(precision)
+        if weights is not None:
+            fp32, act = weights.fp32, (f32 if weights.fp32 else bf16)
         dev = torch.device(device)
         self.dev, self.arch, self.B, self.img, self.C = dev, arch, batch, img_size, num_classes
         self.D = ARCHS[arch]["embed_dim"]

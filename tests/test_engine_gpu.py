@@ -90,6 +90,47 @@ def test_dino_step_parity(dev, n_local):
         assert _rel(td[k], orc.tp[k]) < 1e-3, k
 
 
+_DW_REF = {}
+
+
+def _dw_reference(arch, K, n_local):
+    """Oracle, tiles and reference results of one shape, computed once for both ``group_dw`` settings."""
+    from oracle import step_oracle as so, vit_oracle as vo
+    key = (arch, K, n_local)
+    if key not in _DW_REF:
+        orc = so.DinoOracle(arch=arch, img_size=224, out_dim=K, seed=0, n_local=n_local)
+        tiles = vo.synth_tiles(2, 256, seed=1234)
+        _DW_REF[key] = (orc, tiles, orc.forward_backward(tiles))
+    return _DW_REF[key]
+
+
+@gpu
+@pytest.mark.parametrize("group_dw", [True, False])
+@pytest.mark.parametrize("arch,K,n_local", [("vit_tiny", 4096, 8), ("vit_tiny", 4096, 0), ("vit_small", 2048, 8)])
+def test_dino_parity_grouped_and_four_launch_dw(dev, arch, K, n_local, group_dw):
+    """One forward / backward against the oracle with a block's weight gradients as ONE grouped launch (the default) and as FOUR
+    gv_linear launches in the same side-stream item (``VitRunner.group_dw`` off: GIPVIT_GROUP_DW=0) -- the bf16 four-launch form
+    of the single backward loop.  ViT-T at test_dino_step_parity's shape (unfused; two segments: the varlen attention backward,
+    and one), ViT-S with the fused Linear + LayerNorm kernels; depth 12 alternates the two dY sets.  B = 2; gates of SURVEY 8d:
+    loss 1e-3, logits 2 %, per-parameter gradient 5 %, grad norm 1 %."""
+    from gipvit.engine import DinoEngine
+    orc, tiles, (loss_r, grads_r, s_out, t_out, _) = _dw_reference(arch, K, n_local)
+    eng = DinoEngine(arch=arch, img_size=224, out_dim=K, batch=2, n_local=n_local, device=dev)
+    eng.vit.group_dw = group_dw
+    eng.load_state(orc.p, orc.hp)
+    eng.set_hyper()
+    eng.forward_backward(tiles.to(dev))
+    torch.cuda.synchronize()
+    assert eng.vit.fused == (arch == "vit_small") and eng.vit._cls_tail(eng.g_stu) == group_dw
+    for got, ref, nm in ((eng.hb_t.logits, t_out, "teacher"), (eng.hb_s.logits, s_out, "student")):
+        err = float((got.cpu() - ref).abs().max())
+        assert err <= 2e-2 * float(ref.abs().max()), (nm, err, float(ref.abs().max()))
+    dl = abs(float(eng.loss) - float(loss_r))
+    worst, gn = _check_grads(eng.grads(), grads_r, skip=("head.last_layer.weight_g",))
+    print(f"[dw parity {arch} L{n_local} group_dw={group_dw}] |dloss| {dl:.2e}  worst grad {worst[0]:.2e} ({worst[1]})  grad-norm rel {gn:.2e}")
+    assert dl <= 1e-3, (float(eng.loss), float(loss_r))
+
+
 @gpu
 @pytest.mark.parametrize("arch,n_local,B,K", [("vit_small", 0, 8, 2048), ("vit_small", 8, 8, 2048), ("vit_base", 8, 8, 2048),
                                               ("vit_small", 8, 4, 65536)])
