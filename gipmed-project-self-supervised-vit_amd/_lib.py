@@ -148,6 +148,9 @@ gv_lamb_args = _struct("gv_lamb_args", [
     ("p", vp), ("grad", vp), ("m", vp), ("v", vp), ("p_bf16", vp), ("teacher", vp), ("teacher_bf16", vp), ("blocks", vp), ("n_blocks", i32),
     ("stats", vp), ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32), ("bias_corr1", f32), ("bias_corr2", f32),
     ("grad_scale", f32), ("clip_norm", f32), ("max_grad_norm", f32), ("gnorm_sq", vp), ("teacher_momentum", f32), ("phase", i32), ("lr_scale", vp)])
+gv_knn_vote_args = _struct("gv_knn_vote_args", [
+    ("q", vp), ("bank", vp), ("labels", vp), ("votes", vp), ("top_sim", vp), ("top_idx", vp), ("workspace", vp), ("workspace_bytes", i64),
+    ("Q", i32), ("Nb", i32), ("D", i32), ("k", i32), ("C", i32), ("n_split", i32), ("ldq", i64), ("ldb", i64), ("inv_temp", f32)])
 
 # entry point -> argument struct (every `int gv_*(const args*, void* stream)` of the header)
 ENTRY_POINTS = {
@@ -169,9 +172,10 @@ ENTRY_POINTS = {
     "gv_layernorm_fwd_f32": gv_layernorm_fwd_args, "gv_layernorm_bwd_f32": gv_layernorm_bwd_args, "gv_patchify_f32": gv_patchify_args, "gv_patchify_nchw_f32": gv_patchify_nchw_args,
     "gv_tokens_bwd_f32": gv_tokens_bwd_args, "gv_l2norm_fwd_f32": gv_l2norm_fwd_args, "gv_l2norm_bwd_f32": gv_l2norm_bwd_args,
     "gv_weightnorm_fwd_f32": gv_weightnorm_fwd_args, "gv_dino_loss_f32": gv_dino_loss_args,
+    "gv_knn_vote": gv_knn_vote_args,
 }
 PLAIN_SYMBOLS = ("gv_version", "gv_last_error", "gv_target", "gv_act_format", "gv_linear_workspace_bytes", "gv_workspace_bytes", "gv_linear_timing", "gv_linear_timing_read",
-                 "gv_linear_ln_blocks")
+                 "gv_linear_ln_blocks", "gv_knn_workspace_bytes")
 
 
 class gv_linear_timing_row(C.Structure):
@@ -212,6 +216,8 @@ def _load():
     lib.gv_linear_timing_read.restype = C.c_int
     lib.gv_linear_ln_blocks.argtypes = [C.c_int32]
     lib.gv_linear_ln_blocks.restype = C.c_int
+    lib.gv_knn_workspace_bytes.argtypes = [C.c_int32] * 4
+    lib.gv_knn_workspace_bytes.restype = C.c_int64
     return lib
 
 

@@ -1,0 +1,122 @@
+"""Weighted k-NN monitor on frozen teacher features: the training monitor DINO's recipe comes with (``knn_classifier`` of the
+paper's eval_knn), for ``--dino`` runs, whose encoder has no classifier head for ``validate()`` to score.
+
+A bank of L2-normalised CLS features with slide labels is built from the training-fold slides, every tile of the evaluation fold
+votes with its k most similar bank tiles, weighted exp(sim / temp) (``ops.knn_vote`` -> gv_knn_vote: the Nb x Q similarity
+matrix stays on chip).  Reported like ``validate()``: per-tile top-1, AUC per patch and AUC per slide (slide score = mean of its
+tile scores).  The features come from a forward-only ``engine.FeatureExtractor`` over the teacher backbone's live weights, so the
+bank is rebuilt at every evaluation.  A tile larger than the runner's image (256-px tiles, 224-px global crops) contributes its
+centred window."""
+from __future__ import annotations
+
+import logging
+from collections import OrderedDict
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import ops
+from .validate import _auc
+
+_logger = logging.getLogger("train")
+f32 = torch.float32
+
+
+def knn_metrics(votes: np.ndarray, labels: np.ndarray, slide_ids: np.ndarray) -> "OrderedDict[str, float]":
+    """votes [N, C] (>= 0), labels [N] in [0, C), slide_ids [N] (any hashable per tile; tiles of a slide share one) ->
+    OrderedDict(knn_top1 in percent, and for C > 1: knn_auc_per_patch, knn_auc_per_slide).  The predicted class is the arg-max
+    of the votes, the lowest class on a tie; the patch score is votes[:, 1] / votes.sum(1), the slide score the mean of its
+    patch scores, the slide label its first tile's."""
+    votes = np.asarray(votes, dtype=np.float64)
+    labels = np.asarray(labels).reshape(-1).astype(np.int64)
+    if votes.ndim != 2 or votes.shape[0] != labels.shape[0] or len(slide_ids) != labels.shape[0]:
+        raise ValueError(f"knn_metrics: votes {votes.shape}, labels {labels.shape} and {len(slide_ids)} slide ids do not match")
+    out = OrderedDict()
+    out["knn_top1"] = 100.0 * float((np.argmax(votes, axis=1) == labels).mean()) if len(labels) else float("nan")
+    if votes.shape[1] > 1 and len(labels):
+        tot = votes.sum(1)
+        score = np.divide(votes[:, 1], tot, out=np.zeros_like(tot), where=tot > 0)
+        out["knn_auc_per_patch"] = _auc(labels, score)
+        first, inv = {}, np.empty(len(labels), dtype=np.int64)
+        for i, s in enumerate(slide_ids):                      # slides in order of first appearance
+            inv[i] = first.setdefault(s if not isinstance(s, np.generic) else s.item(), len(first))
+        n = len(first)
+        mean = np.bincount(inv, weights=score, minlength=n) / np.bincount(inv, minlength=n)
+        out["knn_auc_per_slide"] = _auc(labels[np.unique(inv, return_index=True)[1]], mean)      # a slide's label: its first tile's
+    return out
+
+
+class KnnMonitor:
+    """``runner``: an ``engine.FeatureExtractor`` (``run(tiles) -> (features f32 [n, D], logits)``).  ``build_bank(loader)`` then
+    ``evaluate(loader)``; loaders are ``data.InferTiles`` / ``data.SyntheticSlides``."""
+
+    def __init__(self, runner, k: int = 20, temp: float = 0.07, num_classes: int = 2, primary: bool = True, log: Optional[logging.Logger] = None):
+        if not 1 <= k <= 64:
+            raise ValueError(f"KnnMonitor: k must be in 1..64 (got {k})")
+        if not temp > 0:
+            raise ValueError(f"KnnMonitor: temp must be > 0 (got {temp})")
+        if not 1 <= num_classes <= 32:
+            raise ValueError(f"KnnMonitor: num_classes must be in 1..32 (got {num_classes})")
+        self.runner, self.k, self.temp, self.C, self.primary, self.log = runner, k, temp, num_classes, primary, log or _logger
+        self.bank = self.bank_labels = None
+
+    def _window(self, data: torch.Tensor) -> torch.Tensor:
+        """The centred img x img window of larger uint8 tiles (a device slice copy); everything else goes to the runner as it is."""
+        img = self.runner.img
+        if data.dtype == torch.uint8 and data.dim() == 4 and data.shape[1] == data.shape[2] and data.shape[1] > img:
+            o = (data.shape[1] - img) // 2
+            return data[:, o:o + img, o:o + img, :].contiguous()
+        return data
+
+    def features(self, data: torch.Tensor) -> torch.Tensor:
+        """L2-normalised f32 [n, D] CLS features of one chunk of tiles, on the device."""
+        if data.dim() == 5:
+            data = data.squeeze(0)
+        data = self._window(data.to(self.runner.dev, non_blocking=True))
+        feats, _ = self.runner.run(data)
+        n, D = feats.shape
+        out = torch.empty_like(feats)
+        ops.l2norm_fwd(feats, out, torch.empty(n, dtype=f32, device=feats.device), n, D)
+        return out
+
+    def _collect(self, loader):
+        """-> (features f32 [N, D] device, labels int64 [N], slide ordinal int64 [N], slides left out) over the slides whose label
+        is inside [0, C)."""
+        if hasattr(loader, "reset_counter"):
+            loader.reset_counter()
+        feats, labels, slides, skipped, ordinal = [], [], [], 0, 0
+        for mb in loader:
+            y = int(mb["Label"].reshape(-1)[0])
+            if 0 <= y < self.C:
+                f = self.features(mb["Data"])
+                feats.append(f)
+                labels.append(np.full(f.shape[0], y, dtype=np.int64))
+                slides.append(np.full(f.shape[0], ordinal, dtype=np.int64))
+            if mb["Is Last Batch"]:
+                skipped += not 0 <= y < self.C
+                ordinal += 1
+        if not feats:
+            raise ValueError(f"KnnMonitor: no slide with a label in [0, {self.C}) in the loader")
+        return torch.cat(feats), np.concatenate(labels), np.concatenate(slides), skipped
+
+    def build_bank(self, loader) -> int:
+        feats, labels, slides, skipped = self._collect(loader)
+        self.bank = feats
+        self.bank_labels = torch.from_numpy(labels.astype(np.int32)).to(feats.device)
+        if self.primary:
+            self.log.info("k-NN monitor: bank of %d tiles from %d slides (%d slides left out: label outside [0, %d))",
+                          feats.shape[0], len(np.unique(slides)), skipped, self.C)
+        return feats.shape[0]
+
+    def evaluate(self, loader) -> "OrderedDict[str, float]":
+        if self.bank is None:
+            raise RuntimeError("KnnMonitor.evaluate: build_bank first")
+        feats, labels, slides, skipped = self._collect(loader)
+        k = min(self.k, self.bank.shape[0])
+        votes = ops.knn_vote(feats, self.bank, self.bank_labels, k, self.temp, self.C)
+        metrics = knn_metrics(votes.cpu().numpy(), labels, slides)           # (the copy synchronises)
+        if self.primary:
+            self.log.info("k-NN monitor: %d query tiles from %d slides (%d left out), k %d, temp %g: %s", feats.shape[0], len(np.unique(slides)),
+                          skipped, k, self.temp, "  ".join(f"{n} {v:.4f}" for n, v in metrics.items()))
+        return metrics

@@ -401,6 +401,40 @@ def l2norm_bwd(dy, y, inv_norm, dx, rows: int, C: int):
     L.call("gv_l2norm_bwd" + _sfx(y), L.gv_l2norm_bwd_args(dy.data_ptr(), y.data_ptr(), inv_norm.data_ptr(), dx.data_ptr(), rows, C), _stream())
 
 
+_knn_workspace: dict = {}        # device -> uint8 scratch of knn_vote, grown on demand and kept
+
+
+def knn_vote(q, bank, labels, k: int, temp: float, C: int, *, n_split: int = 0, want_topk: bool = False):
+    """Weighted k-NN vote (gv_knn_vote): q f32 [Q, D] and bank f32 [Nb, D], rows L2-normalised (row stride free, a multiple of 4;
+    unit column stride), labels int32 [Nb] -> votes f32 [Q, C] with votes[q, c] = sum over the k most similar bank rows of
+    exp(sim / temp) * [label == c]; with ``want_topk`` also (top_sim f32 [Q, k] non-increasing, top_idx int32 [Q, k]).
+    ``n_split``: 0 = the library chooses, > 0 forces that many bank splits (same result)."""
+    _chk(q, f32, "q"); _chk(bank, f32, "bank"); _chk(labels, torch.int32, "labels")
+    if q.dim() != 2 or bank.dim() != 2 or q.shape[1] != bank.shape[1] or q.stride(1) != 1 or bank.stride(1) != 1:
+        raise ValueError(f"knn_vote: expected q [Q, D] and bank [Nb, D] with unit column stride, got {tuple(q.shape)} strides {q.stride()} "
+                         f"and {tuple(bank.shape)} strides {bank.stride()}")
+    if bank.device != q.device or labels.device != q.device:
+        raise TypeError("knn_vote: q, bank and labels must live on one device")
+    if labels.dim() != 1 or labels.shape[0] != bank.shape[0] or not labels.is_contiguous():
+        raise ValueError(f"knn_vote: labels must be a contiguous int32 [{bank.shape[0]}], got {tuple(labels.shape)}")
+    if not temp > 0:
+        raise ValueError(f"knn_vote: temp must be > 0 (got {temp})")
+    (Q, D), Nb = q.shape, bank.shape[0]
+    need = L.lib.gv_knn_workspace_bytes(Q, Nb, k, n_split)
+    if need < 0:
+        raise L.GipvitError(f"gv_knn_workspace_bytes: {L.lib.gv_last_error().decode()}")
+    ws = _knn_workspace.get(q.device)
+    if ws is None or ws.numel() < need:
+        ws = _knn_workspace[q.device] = torch.empty(need, dtype=torch.uint8, device=q.device)
+    votes = torch.empty(Q, C, dtype=f32, device=q.device)
+    top_sim = torch.empty(Q, k, dtype=f32, device=q.device) if want_topk else None
+    top_idx = torch.empty(Q, k, dtype=torch.int32, device=q.device) if want_topk else None
+    a = L.gv_knn_vote_args(q.data_ptr(), bank.data_ptr(), labels.data_ptr(), votes.data_ptr(), _p(top_sim), _p(top_idx), ws.data_ptr(), ws.numel(),
+                           Q, Nb, D, k, C, n_split, q.stride(0), bank.stride(0), 1.0 / temp)
+    L.call("gv_knn_vote", a, _stream())
+    return (votes, top_sim, top_idx) if want_topk else votes
+
+
 def weightnorm_fwd(v, g, w, rows: int, C: int):
     L.call("gv_weightnorm_fwd" + _sfx(w), L.gv_weightnorm_fwd_args(v.data_ptr(), g.data_ptr(), w.data_ptr(), rows, C), _stream())
 

@@ -743,6 +743,35 @@ int gv_l2norm_bwd_f32(const gv_l2norm_bwd_args* a, void* stream);
 int gv_weightnorm_fwd_f32(const gv_weightnorm_fwd_args* a, void* stream);
 int gv_dino_loss_f32(const gv_dino_loss_args* a, void* stream);
 
+/* ---- weighted k-NN vote on frozen features: DINO's knn_classifier, the training monitor of a --dino run (gipvit/knn.py).
+ * For query row q and bank row b, both already L2-normalised (gv_l2norm_fwd_f32):
+ *     sim = q . b in f32;  the k largest sim over the whole bank;
+ *     votes[q, c] = sum over those k of exp(sim_j * inv_temp) * [labels[idx_j] == c].
+ * The Q x Nb similarity matrix is never written: one launch walks the bank in 128-row chunks on the f32 MFMA and keeps a sorted
+ * (sim, idx) list of length k per query on chip, per bank split; a second small launch merges the n_split lists and votes.
+ * f32 only (both library builds), no atomics: the result is the same run to run.
+ * Order, part of the contract: similarity descending and, among equal similarities, the smaller bank index first -- for every
+ * split count; top_sim is bitwise the same for every split count.  A label outside [0, C) votes for no class and is never used
+ * as an index.  Limits: Q >= 1, 1 <= k <= 64, k <= Nb, D a multiple of 4 and <= 1024, 1 <= C <= 32, ldq / ldb multiples of 4
+ * and >= D, q / bank 16-byte aligned, 0 <= n_split <= min(32, Nb), workspace_bytes >= gv_knn_workspace_bytes(Q, Nb, k, n_split). */
+typedef struct {
+    const float*   q;        /* f32 [Q, D], row stride ldq                                              */
+    const float*   bank;     /* f32 [Nb, D], row stride ldb                                             */
+    const int32_t* labels;   /* i32 [Nb]                                                                */
+    float*         votes;    /* f32 [Q, C]                                                              */
+    float*         top_sim;  /* f32 [Q, k], non-increasing; may be NULL                                 */
+    int32_t*       top_idx;  /* i32 [Q, k], bank rows of top_sim; may be NULL                           */
+    void*          workspace; int64_t workspace_bytes;   /* caller-owned scratch: the per-split lists   */
+    int32_t Q, Nb, D, k, C;
+    int32_t n_split;         /* 0: the library chooses (a workgroup per CU); > 0: that many bank splits */
+    int64_t ldq, ldb;        /* row strides in elements                                                 */
+    float   inv_temp;        /* 1 / temperature (DINO: 1 / 0.07)                                        */
+} gv_knn_vote_args;
+int gv_knn_vote(const gv_knn_vote_args* a, void* stream);
+/* scratch bytes of one gv_knn_vote call (n_split as in the call; 0 resolves as the call would); -1 with gv_last_error() set
+ * for arguments the call would refuse.  Touches no GPU.                                                                    */
+int64_t gv_knn_workspace_bytes(int32_t Q, int32_t Nb, int32_t k, int32_t n_split);
+
 #ifdef __cplusplus
 }
 #endif

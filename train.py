@@ -95,6 +95,13 @@ def build_parser():
     g.add_argument("--warmup-teacher-temp-epochs", type=int, default=0)
     g.add_argument("--weight-decay-end", type=float, default=0.4)
     g.add_argument("--freeze-last-layer", type=int, default=1, help="epochs during which the head's last layer is not updated")
+    g.add_argument("--knn-monitor", action="store_true", help="DINO: weighted k-NN classifier on the teacher's frozen features as the training "
+                   "monitor (bank = training-fold slides, queries = evaluation fold; gv_knn_vote): eval_knn_top1 / eval_knn_auc_per_patch / "
+                   "eval_knn_auc_per_slide in summary.csv, checkpoints chosen on --eval-metric among them")
+    g.add_argument("--knn-k", type=int, default=20, help="--knn-monitor: neighbours that vote (1..64)")
+    g.add_argument("--knn-temp", type=float, default=0.07, help="--knn-monitor: a neighbour votes with weight exp(similarity / temp)")
+    g.add_argument("--knn-bank-tiles", type=int, default=None, help="--knn-monitor: tiles per training slide in the bank (default: --num_tiles)")
+    g.add_argument("--knn-rate", type=int, default=1, help="--knn-monitor: evaluate every N epochs")
     g.add_argument("--tile-size", type=int, default=256)
     g.add_argument("--batches-per-epoch", type=int, default=100, help="synthetic source only")
     g.add_argument("--synthetic-slides", type=int, default=4, help="synthetic source only: slides of the inference set")
@@ -190,6 +197,25 @@ def check_supported(args, log=_logger.warning):
         raise SystemExit("--view-augment augments the crops that --dino --random-crops cuts on the device: pass both")
     if args.extract_attention and not args.extract_features:
         raise SystemExit("--extract-attention writes <slide>_attention.pt next to the features: it needs --extract_features")
+    if args.knn_monitor:
+        if not args.dino:
+            raise SystemExit("--knn-monitor scores the DINO teacher's frozen features: it needs --dino (a supervised run has validate())")
+        if not 1 <= args.knn_k <= 64:
+            raise SystemExit(f"--knn-k {args.knn_k}: the vote kernel keeps 1..64 neighbours per query (gv_knn_vote)")
+        if not args.knn_temp > 0:
+            raise SystemExit(f"--knn-temp {args.knn_temp}: the vote weight is exp(similarity / temp), temp must be > 0")
+        if args.knn_rate < 1:
+            raise SystemExit(f"--knn-rate {args.knn_rate}: evaluate every N >= 1 epochs")
+        if args.knn_bank_tiles is not None and args.knn_bank_tiles < 1:
+            raise SystemExit(f"--knn-bank-tiles {args.knn_bank_tiles}: tiles per training slide in the bank, >= 1")
+        if args.eval_metric == "loss":
+            raise SystemExit("--eval-metric loss with --knn-monitor: the monitor reports top1 / auc_per_patch / auc_per_slide (no loss); "
+                             "pick one of them")
+        if args.test_fold in (-1, "-1"):
+            raise SystemExit("--test_fold -1 with --knn-monitor: no evaluation fold is left to query the bank with")
+        if args.tile_size < args.global_crop_size:
+            raise SystemExit(f"--knn-monitor: the teacher sees {args.global_crop_size}-px images, the centred window of a {args.tile_size}-px "
+                             "tile (--tile-size) cannot be smaller than that")
     if args.supervised and args.dino:
         raise SystemExit("--supervised (fine-tune with labels, train.py:715-717) and --dino (self-supervised) exclude each other")
     # mixup / cutmix / BCE (train.py:752-771, 828-846): the supervised step's batch, target and loss
@@ -367,10 +393,17 @@ def main(argv=None, transform=None):
     if hook_format == "f32_nchw" and primary:
         _logger.info("transform hook returns float32 [3, H, W]: batches are float32 NCHW, patchified without the fused normalise")
     inf_loader = None
+    # --knn-monitor: the bank comes from the training fold, the queries from the evaluation fold; --extract_features runs alone
+    want_knn = bool(args.knn_monitor) and not args.extract_features
+    knn_bank_loader = knn_query_loader = None
+    bank_tiles = args.knn_bank_tiles or args.num_tiles
     if synthetic:
         source = D.SyntheticTiles(B, tile, args.batches_per_epoch, args.num_classes or 2, seed=args.seed + rank)
         if not args.no_validate and (not args.dino or args.extract_features):
             inf_loader = D.SyntheticSlides(args.synthetic_slides, min(args.num_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 99)
+        if want_knn:
+            knn_bank_loader = D.SyntheticSlides(args.synthetic_slides, min(bank_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 77)
+            knn_query_loader = D.SyntheticSlides(args.synthetic_slides, min(args.num_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 99)
     elif args.dataset.startswith("tiles:") or args.data_dir:
         root = args.dataset[6:] if args.dataset.startswith("tiles:") else args.data_dir
         slides = D.scan_slides(root, args.target)
@@ -380,7 +413,7 @@ def main(argv=None, transform=None):
         want_eval = not args.no_validate and (not args.dino or args.extract_features)
         no_val_fold = args.test_fold in (-1, "-1")
         train_slides = D.select_fold(slides, args.test_fold, True)
-        if args.supervised or (want_eval and not no_val_fold):
+        if args.supervised or want_knn or (want_eval and not no_val_fold):
             eval_slides = D.select_fold(slides, args.test_fold, False)       # raises when evaluation was asked for and no slide is in the fold
         else:
             eval_slides = []
@@ -398,6 +431,11 @@ def main(argv=None, transform=None):
         if want_eval:
             inf_loader = D.InferTiles(root, tile, args.tiles_per_iter, args.num_tiles, seed=args.seed, dataset_name=args.dataset,
                                       workers=args.workers, slides=eval_slides)
+        if want_knn:
+            knn_bank_loader = D.InferTiles(root, tile, args.tiles_per_iter, bank_tiles, seed=args.seed + 1, dataset_name=args.dataset,
+                                           workers=args.workers, slides=train_slides)
+            knn_query_loader = D.InferTiles(root, tile, args.tiles_per_iter, args.num_tiles, seed=args.seed, dataset_name=args.dataset,
+                                            workers=args.workers, slides=eval_slides)
     else:
         raise SystemExit(f"--dataset {args.dataset}: whole-slide datasets need openslide and are outside this build "
                          "(SURVEY section 2 #15); use 'synthetic' or 'tiles:<dir>' with pre-extracted tile_<i>.data files")
@@ -469,15 +507,25 @@ def main(argv=None, transform=None):
             if ema_decay is not None:
                 runner_ema = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.Wema)
 
+    monitor = None
+    knn_names = []
+    if want_knn:        # the teacher backbone at its own image size; larger tiles contribute their centred window (gipvit/knn.py)
+        from gipvit.knn import KnnMonitor
+        knn_runner = FeatureExtractor(arch, img, eval_B, 0, mean, std, dev, weights=Weights(eng.arena, "backbone.", teacher=True, fp32=args.precision == "fp32"))
+        monitor = KnnMonitor(knn_runner, k=args.knn_k, temp=args.knn_temp, num_classes=args.num_classes or 2, primary=primary)
+        knn_names = ["knn_top1"] + (["knn_auc_per_patch", "knn_auc_per_slide"] if monitor.C > 1 else [])
+
     # ---- output dir, args.yaml, saver (train.py:854-879)
     eval_metric = args.eval_metric                              # train.py:849
+    if monitor is not None and not eval_metric.startswith("knn_"):
+        eval_metric = "knn_" + eval_metric                      # the default 'top1' selects knn_top1
     decreasing = eval_metric == "loss"                          # train.py:866
     saver = output_dir = None
     if primary:
         exp = args.experiment or "-".join([time.strftime("%Y%m%d-%H%M%S"), args.model.replace("/", "_"), str(img)])
         output_dir = os.path.join(args.output or "./output/train", exp, args.subexperiment or "")
         os.makedirs(output_dir, exist_ok=True)
-        saver = CheckpointSaver(output_dir, args.model, vars(args), decreasing=decreasing or inf_loader is None or args.dino,
+        saver = CheckpointSaver(output_dir, args.model, vars(args), decreasing=(decreasing or inf_loader is None or args.dino) and monitor is None,
                                 max_history=args.checkpoint_hist)
         with open(os.path.join(output_dir, "args.yaml"), "w") as f:
             f.write(args_text)
@@ -611,13 +659,20 @@ def main(argv=None, transform=None):
             if runner_ema is not None and not args.extract_features:       # train.py:943-955: the EMA model's metrics win
                 eval_metrics = validate(runner_ema, inf_loader, smoothing=args.smoothing, log_interval=args.log_interval, primary=primary,
                                         log_suffix=" (EMA)")
+        knn_blank = []
+        if monitor is not None:
+            if (epoch + 1) % args.knn_rate == 0:                # the teacher moved: the bank is rebuilt at every evaluation
+                monitor.build_bank(knn_bank_loader)
+                eval_metrics.update(monitor.evaluate(knn_query_loader))
+            else:
+                knn_blank = knn_names                           # summary.csv keeps its columns, empty for this epoch
         if args.extract_features:
             if primary:
                 _logger.info(f"*** features of {int(eval_metrics.get('slides', 0))} slides written to {args.features_dir}")
             break
         if primary:
             row = OrderedDict(epoch=epoch, **{"train_" + k: v for k, v in train_metrics.items()}, **{"eval_" + k: v for k, v in eval_metrics.items()},
-                              lr=logged_lr(cur_lr))
+                              **{"eval_" + k: "" for k in knn_blank}, lr=logged_lr(cur_lr))
             fn = os.path.join(output_dir, "summary.csv")
             new = not os.path.exists(fn)
             with open(fn, "a") as f:
@@ -626,17 +681,19 @@ def main(argv=None, transform=None):
                     w.writeheader()
                 w.writerow(row)
             if run is not None:
-                run.log(dict(row))
+                run.log({k: v for k, v in row.items() if v != ""})
             optim = {"exp_avg": eng.arena.m, "exp_avg_sq": eng.arena.v, "step": eng.t}
             if eval_metrics:
                 if eval_metric not in eval_metrics:
-                    raise SystemExit(f"--eval-metric {eval_metric}: validate() reports {list(eval_metrics)}")
+                    raise SystemExit(f"--eval-metric {eval_metric}: {'the k-NN monitor' if monitor is not None else 'validate()'} reports {list(eval_metrics)}")
                 save_metric, name = eval_metrics[eval_metric], "eval " + eval_metric          # train.py:970-973
+            elif monitor is not None:
+                save_metric, name = None, "eval " + eval_metric                               # not evaluated this epoch (--knn-rate)
             else:
                 save_metric, name = train_metrics["loss"], "train loss"
             best, best_ep = saver.save_checkpoint(epoch, eng.arena.state_dict(), optim, metric=save_metric, extra=extra_state())
             _logger.info(f"*** epoch {epoch}: " + "  ".join(f"{k} {v:.4f}" for k, v in list(train_metrics.items()) + [("eval_" + k, v) for k, v in eval_metrics.items()])
-                         + f"  (best {name} {best:.4f} @ {best_ep})")
+                         + (f"  (best {name} {best:.4f} @ {best_ep})" if best is not None else f"  (no {name} yet)"))
     if world > 1:
         torch.distributed.destroy_process_group()
     return 0
