@@ -240,7 +240,12 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(gv_attention_fwd_args
     }
 }
 
-// dQ: query rows against all keys.  P = exp(scale S - lse), dP = dO V^T, dS = P (dP - delta), dQ = scale dS K
+// The backward renormalises P = exp(scale S - lse) by its own row sum: lse is an f32 (ulp 7.6e-6 at |lse| ~ 100), so P taken from
+// it alone carries the relative error of that rounding (1.4e-6 for lse = 96 + ln 2) into every gradient; the row sum of the
+// recomputed P is exp(that error), and dividing by it leaves the f32 rounding of the sum itself (~1e-7).
+__device__ __forceinline__ float attn_renorm(float rowsum) { return (rowsum > 0.f && rowsum < INFINITY) ? 1.f / rowsum : 1.f; }
+
+// dQ: query rows against all keys.  P = exp(scale S - lse) / rowsum, dP = dO V^T, dS = P (dP - delta), dQ = scale dS K
 __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(gv_attention_bwd_args a) {
     extern __shared__ float sm[];
     const int N = a.N, H = a.H, img = blockIdx.x / H, h = blockIdx.x % H, D3 = 3 * H * 64, D = H * 64;
@@ -278,12 +283,17 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(gv_attention_bwd_a
                     dp[c] = fmaf(gd, Vs[j * ALD + d], dp[c]);
                 }
         }
+        float psum = 0.f;
 #pragma unroll
         for (int c = 0; c < AMAXC; ++c)
             if (c < NC) {
-                const float pj = (c * 64 + lane < N) ? expf(s[c] * a.scale - lse) : 0.f;
-                Dw[w * NP + c * 64 + lane] = pj * (dp[c] - delta);
+                s[c] = (c * 64 + lane < N) ? expf(s[c] * a.scale - lse) : 0.f;
+                psum += s[c];
             }
+        const float rn = attn_renorm(wave_sum(psum));
+#pragma unroll
+        for (int c = 0; c < AMAXC; ++c)
+            if (c < NC) Dw[w * NP + c * 64 + lane] = s[c] * rn * (dp[c] - delta);
         __syncthreads();
         float dq = 0.f;
         for (int j = 0; j < N; ++j) dq = fmaf(Dw[w * NP + j], Ks[j * ALD + lane], dq);
@@ -304,6 +314,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_f32_kernel(gv_attention_bwd_
     float* Dw = Pw + 4 * NP;           // [4][NP] dS strip
     float* Kw = Dw + 4 * NP;           // [4][64]
     float* Vw = Kw + 4 * 64;           // [4][64]
+    float* Rn = Vw + 4 * 64;           // [NP] 1 / row sum of the recomputed P
     const float* base = (const float*)a.qkv + (long)img * N * D3 + h * 64;
     const float* dO = (const float*)a.d_o + (long)img * N * D + h * 64;
     const float* O = (const float*)a.o + (long)img * N * D + h * 64;
@@ -316,12 +327,39 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_f32_kernel(gv_attention_bwd_
         const float d = wave_sum(Gs[i * ALD + lane] * O[(long)i * D + lane]);
         if (lane == 0) Dl[i] = d;
     }
+    // row sums of P over ALL keys (this workgroup's 64 keys see only a slice of each row): wave w takes keys w, w + 4, ...,
+    // lane = query (+64, +128 ...); the four partial sums meet in the P strip, which the main loop does not use yet
+    {
+        float acc[AMAXC];
+#pragma unroll
+        for (int c = 0; c < AMAXC; ++c) acc[c] = 0.f;
+        for (int j = w; j < N; j += 4) {
+            const float* krow = base + (long)j * D3 + H * 64;
+            float s[AMAXC];
+#pragma unroll
+            for (int c = 0; c < AMAXC; ++c) s[c] = 0.f;
+            for (int d = 0; d < 64; ++d) {
+                const float kd = krow[d];
+#pragma unroll
+                for (int c = 0; c < AMAXC; ++c)
+                    if (c < NC) s[c] = fmaf(kd, Qs[min(c * 64 + lane, N - 1) * ALD + d], s[c]);
+            }
+#pragma unroll
+            for (int c = 0; c < AMAXC; ++c)
+                if (c < NC) acc[c] += expf(s[c] * a.scale - Ls[min(c * 64 + lane, N - 1)]);
+        }
+#pragma unroll
+        for (int c = 0; c < AMAXC; ++c)
+            if (c < NC) Pw[w * NP + c * 64 + lane] = acc[c];
+        __syncthreads();
+        for (int i = threadIdx.x; i < NP; i += 256) Rn[i] = attn_renorm(Pw[i] + Pw[NP + i] + Pw[2 * NP + i] + Pw[3 * NP + i]);
+    }
     for (int it = 0; it < 16; ++it) {
         const int j = blockIdx.y * 64 + it * 4 + w;
         const bool ok = j < N;
         Kw[w * 64 + lane] = ok ? base[(long)j * D3 + H * 64 + lane] : 0.f;
         Vw[w * 64 + lane] = ok ? base[(long)j * D3 + 2 * H * 64 + lane] : 0.f;
-        __syncthreads();               // (first pass: also publishes Dl)
+        __syncthreads();               // (first pass: also publishes Dl and Rn, and ends the row-sum pass's use of the P strip)
         float s[AMAXC], dp[AMAXC];
 #pragma unroll
         for (int c = 0; c < AMAXC; ++c) s[c] = dp[c] = 0.f;
@@ -339,7 +377,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_f32_kernel(gv_attention_bwd_
         for (int c = 0; c < AMAXC; ++c)
             if (c < NC) {
                 const int i = c * 64 + lane;
-                const float pi = i < N ? expf(s[c] * a.scale - Ls[i]) : 0.f;
+                const float pi = i < N ? expf(s[c] * a.scale - Ls[i]) * Rn[i] : 0.f;
                 Pw[w * NP + i] = pi;
                 Dw[w * NP + i] = i < N ? pi * (dp[c] - Dl[i]) : 0.f;
             }
@@ -452,7 +490,7 @@ extern "C" int gv_attention_bwd_f32(const gv_attention_bwd_args* a, void* stream
     GV_REQUIRE(gv_aligned(a->qkv, 16) && gv_aligned(a->o, 16) && gv_aligned(a->d_o, 16) && gv_aligned(a->dqkv, 16), GV_E_ALIGN,
                "gv_attention_bwd_f32: buffers must be 16-byte aligned");
     const int NP = ((a->N + 63) / 64) * 64;
-    const int lds_q = (2 * a->N * ALD + 4 * NP + 8 * 64) * 4, lds_kv = (2 * a->N * ALD + 2 * NP + 8 * NP + 8 * 64) * 4;
+    const int lds_q = (2 * a->N * ALD + 4 * NP + 8 * 64) * 4, lds_kv = (2 * a->N * ALD + 3 * NP + 8 * NP + 8 * 64) * 4;
     int rc = set_lds(attn_bwd_dq_f32_kernel, lds_q, "gv_attention_bwd_f32");
     if (rc != GV_OK) return rc;
     rc = set_lds(attn_bwd_dkv_f32_kernel, lds_kv, "gv_attention_bwd_f32");

@@ -457,20 +457,34 @@ def _attn_ref(qkv, n_img, N, H, scale):
 
 @pytest.mark.parametrize("N,H,n_img", [(197, 6, 5), (37, 6, 7), (17, 3, 9), (257, 6, 2), (65, 12, 3), (1, 3, 2), (224, 2, 1)])
 def test_attention_fwd_bwd(dev, N, H, n_img):
+    """bf16 forward / backward against fp32 torch; lse against fp64 logsumexp on the CPU within LSE_BOUND (4 x the kernel's measured
+    error, a quarter of what one counted pad key would shift it by: tests/test_attention_probes_host.py); o, lse and dqkv each have
+    sentinel-filled guard rows behind them."""
+    from test_attention_probes_host import LSE_BOUND
     o = ops()
     g = torch.Generator().manual_seed(N * 7 + H)
     qkv = torch.randn(n_img * N, 3 * H * 64, generator=g).to(dev).to(bf16)
     scale = 64 ** -0.5
-    out, lse = o.attention_fwd(qkv, n_img, N, H, scale)
+    T, G = n_img * N, 4
+    obuf = torch.full((T + G, H * 64), 7.0, dtype=bf16, device=dev)
+    lbuf = torch.full((n_img * H * N + G,), 7.0, dtype=f32, device=dev)
+    gbuf = torch.full((T + G, 3 * H * 64), 5.0, dtype=bf16, device=dev)
+    out, lse = o.attention_fwd(qkv, n_img, N, H, scale, o=obuf[:T], lse=lbuf[:n_img * H * N].view(n_img, H, N))
     x = qkv.float().requires_grad_(True)
     ref, ref_lse = _attn_ref(x, n_img, N, H, scale)
     close(out, ref, 2e-2, 2e-2, "attn o")        # bf16 P and bf16 output
     close(lse, ref_lse, 1e-3, 1e-3, "lse")
+    q64, k64 = (qkv.cpu().double().view(n_img, N, 3, H, 64)[:, :, i].transpose(1, 2) for i in range(2))
+    lse64 = torch.logsumexp(q64 @ k64.transpose(-1, -2) * scale, -1)
+    err = float((lse.cpu().double() - lse64).abs().max())
+    assert err <= LSE_BOUND, f"lse: max err {err:.4g} against fp64 logsumexp, bound {LSE_BOUND:.4g}"
     d_o = torch.randn(n_img * N, H * 64, generator=g).to(dev).to(bf16)
     ref.backward(d_o.float())
-    dqkv = o.attention_bwd(qkv, out, d_o, lse, n_img, N, H, scale)
+    dqkv = o.attention_bwd(qkv, out, d_o, lse, n_img, N, H, scale, dqkv=gbuf[:T])
     scale_ref = float(x.grad.abs().max())
     close(dqkv, x.grad, 3e-2, 2e-2 * max(scale_ref, 1.0), "dqkv")
+    assert float(obuf[T:].float().min()) == 7.0 == float(obuf[T:].float().max()) and float(lbuf[n_img * H * N:].min()) == 7.0 == float(lbuf[n_img * H * N:].max())
+    assert float(gbuf[T:].float().min()) == 5.0 == float(gbuf[T:].float().max())
 
 
 def test_attention_softmax_spike(dev):
