@@ -43,6 +43,11 @@ gv_mix_row = _struct("gv_mix_row", [("partner", i32), ("mode", i32), ("lam", f32
                                     ("yl", i32), ("yh", i32), ("xl", i32), ("xh", i32)])
 gv_patchify_mix_args = _struct("gv_patchify_mix_args", [("p", gv_patchify_args), ("mix", vp)])
 gv_patchify_nchw_mix_args = _struct("gv_patchify_nchw_mix_args", [("p", gv_patchify_nchw_args), ("mix", vp)])
+# one row of the device erase table (gipvit.erasing packs them) and the two patchify calls that take one (mix may be NULL)
+GV_ERASE_MAX_BOXES = 8
+gv_erase_row = _struct("gv_erase_row", [("mode", i32), ("n_box", i32), ("box", (i32 * 4) * GV_ERASE_MAX_BOXES), ("value", (f32 * 3) * GV_ERASE_MAX_BOXES)])
+gv_patchify_erase_args = _struct("gv_patchify_erase_args", [("p", gv_patchify_args), ("mix", vp), ("erase", vp), ("seed", C.c_uint32)])
+gv_patchify_nchw_erase_args = _struct("gv_patchify_nchw_erase_args", [("p", gv_patchify_nchw_args), ("mix", vp), ("erase", vp), ("seed", C.c_uint32)])
 MIX_LOSS_SOFT_CE, MIX_LOSS_BCE = 0, 1
 gv_augment_params = _struct("gv_augment_params", [
     ("n_color", i32), ("order", i32 * 4), ("bf", f32), ("cf", f32), ("sf", f32), ("hue", i32), ("blur", i32), ("kc", f32), ("ks", f32),
@@ -164,6 +169,8 @@ ENTRY_POINTS = {
     "gv_dino_loss": gv_dino_loss_args, "gv_center_update": gv_center_update_args, "gv_softmax_lsce": gv_softmax_lsce_args,
     "gv_patchify_mix": gv_patchify_mix_args, "gv_patchify_nchw_mix": gv_patchify_nchw_mix_args, "gv_softmax_mix_loss": gv_softmax_mix_loss_args,
     "gv_patchify_mix_f32": gv_patchify_mix_args, "gv_patchify_nchw_mix_f32": gv_patchify_nchw_mix_args,
+    "gv_patchify_erase": gv_patchify_erase_args, "gv_patchify_nchw_erase": gv_patchify_nchw_erase_args,
+    "gv_patchify_erase_f32": gv_patchify_erase_args, "gv_patchify_nchw_erase_f32": gv_patchify_nchw_erase_args,
     "gv_gather_cls": gv_gather_cls_args, "gv_cast_bf16": gv_cast_bf16_args, "gv_store_f32": gv_store_f32_args, "gv_sumsq": gv_sumsq_args,
     "gv_adamw_ema": gv_adamw_ema_args, "gv_adamw_ema_ranges": gv_adamw_ema_ranges_args, "gv_loss_scale_update": gv_loss_scale_update_args, "gv_lamb": gv_lamb_args, "gv_agc": gv_agc_args, "gv_dropout": gv_dropout_args, "gv_dropout_add": gv_dropout_add_args,
     # fp32 operand mode: the same structs with every bf16 buffer read / written as f32

@@ -80,8 +80,73 @@ template <bool F32OUT> __device__ __forceinline__ void store_run(void* patches, 
     }
 }
 
-template <bool F32OUT>      // fp32 parity mode: f32 patch rows (f32path.hip)
-__global__ __launch_bounds__(256) void patchify_kernel(gv_patchify_args a, int P, int side, norm_consts k) {
+// ---- random erasing (gv_erase_row): the part the u8 and the NCHW kernels share.  The table and the step's seed travel as one
+// kernel argument; the instantiations without ERASE never look at it.
+struct erase_in { const gv_erase_row* tab; uint32_t seed; };
+// A row as the kernels use it: anything that is not a well-formed value / noise row has no boxes.
+struct erase_desc { const gv_erase_row* r; int mode, nb; };
+__device__ __forceinline__ erase_desc load_erase(const gv_erase_row* tab, int img) {
+    const gv_erase_row* r = tab + img;
+    const int mode = r->mode, nb = r->n_box;
+    const bool ok = (mode == GV_ERASE_VALUE || mode == GV_ERASE_NOISE) && nb >= 0 && nb <= GV_ERASE_MAX_BOXES;
+    return erase_desc{r, ok ? mode : GV_ERASE_OFF, ok ? nb : 0};
+}
+// bit i set: pixel wx + i (i < N <= 16) of window row wy lies in box b.  The pixels of a run all lie in the window, so the box
+// is clamped to it by construction.
+template <int N> __device__ __forceinline__ unsigned erase_bits(const gv_erase_row* r, int b, int wy, int wx) {
+    const int yl = r->box[b][0], yh = r->box[b][1], xl = r->box[b][2], xh = r->box[b][3];
+    if (wy < yl || wy >= yh) return 0u;
+    const int lo = max(xl, wx), hi = min(xh, wx + N);
+    if (hi <= lo) return 0u;
+    return ((1u << (hi - wx)) - 1u) & ~((1u << (lo - wx)) - 1u);
+}
+template <int N> __device__ __forceinline__ unsigned erase_mask(const erase_desc& e, int wy, int wx) {
+    unsigned m = 0u;
+    for (int b = 0; b < e.nb; ++b) m |= erase_bits<N>(e.r, b, wy, wx);
+    return m;
+}
+__device__ __forceinline__ uint32_t fmix32(uint32_t h) {      // murmur3 finaliser, as drop_keep (rowops.hip)
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+    return h;
+}
+// z(idx): Box-Muller on two hashes of the pixel's index, f32 with the accurate logf / cosf / sqrtf (gipvit.h)
+__device__ __forceinline__ float erase_noise(uint32_t seed, uint32_t idx) {
+    const uint32_t h1 = fmix32(seed + 0x9E3779B9u * (idx + 1u));
+    const uint32_t h2 = fmix32(h1 + 0x6D2B79F5u);
+    const float u1 = (float)((h1 >> 8) + 1u) * 0x1p-24f;
+    const float u2 = (float)(h2 >> 8) * 0x1p-24f;
+    return sqrtf(-2.0f * logf(u1)) * cosf(6.2831853f * u2);
+}
+// The erased pixels (bits of `mask`) of NC channels c0 .. of one run: v[j][i] = channel c0 + j, pixel wx + i of window row wy.
+template <int NC, int N>
+__device__ __forceinline__ void erase_apply(const erase_desc& e, uint32_t seed, int img, int c0, int S, int wy, int wx, unsigned mask, float (&v)[NC][N]) {
+    if (e.mode == GV_ERASE_NOISE) {
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            const uint32_t idx = (((uint32_t)img * 3u + (uint32_t)(c0 + j)) * (uint32_t)S + (uint32_t)wy) * (uint32_t)S + (uint32_t)wx;
+#pragma unroll
+            for (int i = 0; i < N; ++i)
+                if ((mask >> i) & 1u) v[j][i] = erase_noise(seed, idx + (uint32_t)i);
+        }
+    } else {
+        for (int b = 0; b < e.nb; ++b) {        // in order: a later box overwrites an earlier one
+            const unsigned bits = erase_bits<N>(e.r, b, wy, wx);
+            if (!bits) continue;
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                const float val = e.r->value[b][c0 + j];
+#pragma unroll
+                for (int i = 0; i < N; ++i)
+                    if ((bits >> i) & 1u) v[j][i] = val;
+            }
+        }
+    }
+}
+
+// ERASE (gv_patchify_erase without a mix table, n_win == 1): the run's erased pixels are overwritten after normalise + fill; a
+// run wholly inside erased boxes reads nothing.
+template <bool F32OUT, bool ERASE = false>      // F32OUT: fp32 parity mode, f32 patch rows (f32path.hip)
+__global__ __launch_bounds__(256) void patchify_kernel(gv_patchify_args a, int P, int side, norm_consts k, erase_in er) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     const long total = (long)a.n_img * P * 16;
     if (t >= total) return;
@@ -93,7 +158,15 @@ __global__ __launch_bounds__(256) void patchify_kernel(gv_patchify_args a, int P
     const int prow = patch / side, pcol = patch - prow * side;
     const int y = a.win_y[win] + prow * 16 + py, x = a.win_x[win] + pcol * 16;
     float px[3][16];
-    norm_run(a, k, tile, y, x, px);
+    if constexpr (ERASE) {
+        const int wy = prow * 16 + py, wx = pcol * 16;       // window coordinates: the boxes' frame
+        const erase_desc e = load_erase(er.tab, img);
+        const unsigned em = erase_mask<16>(e, wy, wx);
+        if (em != 0xFFFFu) norm_run(a, k, tile, y, x, px);
+        if (em) erase_apply<3, 16>(e, er.seed, img, 0, a.crop, wy, wx, em, px);
+    } else {
+        norm_run(a, k, tile, y, x, px);
+    }
     store_run<F32OUT>(a.patches, ip, py, px);
 }
 
@@ -117,8 +190,9 @@ __device__ __forceinline__ mix_desc load_mix(const gv_mix_row* mix, int img, int
 // ---- patchify_mix: patchify with timm's Mixup applied to the batch inside the same pass (gv_patchify_mix_args).  Same
 // thread mapping and store pattern as patchify_kernel; the only new traffic is the partner tile's 48 bytes per thread, read
 // by blend rows and by the threads of a paste row whose run meets the box (a run wholly inside it skips its own tile instead).
-template <bool F32OUT>
-__global__ __launch_bounds__(256) void patchify_mix_kernel(gv_patchify_args a, const gv_mix_row* mix, int P, int side, norm_consts k) {
+// ERASE: as in patchify_kernel, after the mixing; a run wholly inside erased boxes reads neither source.
+template <bool F32OUT, bool ERASE = false>
+__global__ __launch_bounds__(256) void patchify_mix_kernel(gv_patchify_args a, const gv_mix_row* mix, int P, int side, norm_consts k, erase_in er) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     const long total = (long)a.n_img * P * 16;
     if (t >= total) return;
@@ -135,16 +209,27 @@ __global__ __launch_bounds__(256) void patchify_mix_kernel(gv_patchify_args a, c
     const bool whole = meets && wx >= m.xl && wx + 16 <= m.xh;
     const bool blend = m.mode == GV_MIX_BLEND;
     float px[3][16];
-    norm_run(a, k, whole ? m.partner : img, y, x, px);
-    if (blend || (meets && !whole)) {
-        float pj[3][16];
-        norm_run(a, k, m.partner, y, x, pj);
+    erase_desc e{nullptr, GV_ERASE_OFF, 0};
+    unsigned em = 0u;
+    if constexpr (ERASE) {
+        e = load_erase(er.tab, img);
+        em = erase_mask<16>(e, wy, wx);
+    }
+    if (!ERASE || em != 0xFFFFu) {
+        norm_run(a, k, whole ? m.partner : img, y, x, px);
+        if (blend || (meets && !whole)) {
+            float pj[3][16];
+            norm_run(a, k, m.partner, y, x, pj);
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const bool in = wx + i >= m.xl && wx + i < m.xh;
+            for (int i = 0; i < 16; ++i) {
+                const bool in = wx + i >= m.xl && wx + i < m.xh;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) px[c][i] = blend ? mix_blend(px[c][i], pj[c][i], m.lam, m.oml) : (in ? pj[c][i] : px[c][i]);
+                for (int c = 0; c < 3; ++c) px[c][i] = blend ? mix_blend(px[c][i], pj[c][i], m.lam, m.oml) : (in ? pj[c][i] : px[c][i]);
+            }
         }
+    }
+    if constexpr (ERASE) {
+        if (em) erase_apply<3, 16>(e, er.seed, img, 0, a.crop, wy, wx, em, px);
     }
     store_run<F32OUT>(a.patches, ip, py, px);
 }
@@ -228,8 +313,11 @@ __device__ __forceinline__ int paste_mask4(const mix_desc& m, int wy, int wx) {
 
 // MIX (gv_patchify_nchw_mix, n_win == 1): phase 1 takes each 4-pixel item from the image, from its partner or from both, as
 // the image's mix row says; everything else is the plain kernel.
-template <typename OT, bool MIX>
-__global__ __launch_bounds__(256) void patchify_nchw_kernel(gv_patchify_nchw_args a, int side, int n_chunk, const gv_mix_row* mix) {
+// ERASE (gv_patchify_nchw_erase, n_win == 1): the image's erase row is the workgroup's; a strip that meets none of its boxes runs
+// the loop of the kernel without it, in one that does an item wholly inside erased boxes loads nothing and the erased pixels are
+// overwritten after the combine.
+template <typename OT, bool MIX, bool ERASE = false>
+__global__ __launch_bounds__(256) void patchify_nchw_kernel(gv_patchify_nchw_args a, int side, int n_chunk, const gv_mix_row* mix, erase_in er) {
     constexpr int V = 16 / (int)sizeof(OT);                       // elements per 16-B store
     // items per lane and round: MIX holds two sources per item, so half as many keep the loads in flight (and the registers,
     // hence the workgroups per CU that overlap one strip's loads with another's stores) where the plain kernel has them
@@ -250,8 +338,19 @@ __global__ __launch_bounds__(256) void patchify_nchw_kernel(gv_patchify_nchw_arg
         m = load_mix(mix, img, a.n_tiles);
         if (m.mode != GV_MIX_COPY) pdelta = (long)(m.partner - tile) * a.stride_n;
     }
+    erase_desc e{nullptr, GV_ERASE_OFF, 0};
+    if constexpr (ERASE) {
+        e = load_erase(er.tab, img);
+        bool hit = false;                                           // does a box meet this strip's 16 rows x np * 16 columns?
+        for (int b = 0; b < e.nb; ++b) {
+            const int* bx = e.r->box[b];
+            hit |= bx[0] < prow * 16 + 16 && bx[1] > prow * 16 && bx[2] < (p0 + np) * 16 && bx[3] > p0 * 16 && bx[0] < bx[1] && bx[2] < bx[3];
+        }
+        if (!hit) e.nb = 0;
+    }
     for (int b0 = threadIdx.x; b0 < n_items; b0 += 256 * U) {
         f32x4 v[U];
+        unsigned em[ERASE ? U : 1];                                 // ERASE: which of the item's 4 pixels are erased
         // MIX: w = the partner's 4 pixels, pm = which of the 4 a paste row takes from it.  Every load of the batch of items is
         // issued before the first value is used (the combine waits for the second loop), as in the plain kernel.
         f32x4 w[MIX ? U : 1];
@@ -262,14 +361,20 @@ __global__ __launch_bounds__(256) void patchify_nchw_kernel(gv_patchify_nchw_arg
             if (it < n_items) {
                 const int seg = it / q, g = it - seg * q;
                 const float* src = base + (long)(seg >> 4) * a.stride_c + (long)(seg & 15) * a.stride_h + g * 4;
+                bool live = true;                                   // false: all 4 pixels are erased, nothing is read
+                if constexpr (ERASE) {
+                    em[u] = erase_mask<4>(e, prow * 16 + (seg & 15), p0 * 16 + g * 4);
+                    live = em[u] != 15u;
+                }
                 if constexpr (!MIX) {
-                    v[u] = nchw_load4(src);
+                    if constexpr (ERASE) v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (live) v[u] = nchw_load4(src);
                 } else {
                     pm[u] = paste_mask4(m, prow * 16 + (seg & 15), p0 * 16 + g * 4);
                     const bool blend = m.mode == GV_MIX_BLEND;
                     v[u] = w[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (blend || pm[u] != 15) v[u] = nchw_load4(src);
-                    if (blend || pm[u] != 0) w[u] = nchw_load4(src + pdelta);
+                    if (live && (blend || pm[u] != 15)) v[u] = nchw_load4(src);
+                    if (live && (blend || pm[u] != 0)) w[u] = nchw_load4(src + pdelta);
                 }
             }
         }
@@ -285,6 +390,13 @@ __global__ __launch_bounds__(256) void patchify_nchw_kernel(gv_patchify_nchw_arg
                     } else {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) v[u][i] = ((pm[u] >> i) & 1) ? w[u][i] : v[u][i];
+                    }
+                }
+                if constexpr (ERASE) {
+                    if (em[u]) {
+                        float t[1][4] = {{v[u][0], v[u][1], v[u][2], v[u][3]}};
+                        erase_apply<1, 4>(e, er.seed, img, seg >> 4, a.crop, prow * 16 + (seg & 15), p0 * 16 + g * 4, em[u], t);
+                        v[u] = f32x4{t[0][0], t[0][1], t[0][2], t[0][3]};
                     }
                 }
                 OT* d = img_lds + seg * ROW + g * 4;
@@ -329,8 +441,21 @@ extern "C" int gv_crop_resize(const gv_crop_resize_args* a, void* stream) {
     return GV_OK;
 }
 
-// mix == nullptr: gv_patchify; else gv_patchify_mix (has_mix says which was called: a NULL table is then an error)
-template <bool F32OUT> static int patchify_launch(const gv_patchify_args* a, void* stream, const gv_mix_row* mix = nullptr, bool has_mix = false) {
+// What an entry point with an erase table adds to the checks of the plain / mix launch (`crop` is validated by the caller first).
+static int erase_check(const char* name, const gv_mix_row* mix, const erase_in* er, int n_win, int n_img, int crop) {
+    GV_REQUIRE(er->tab, GV_E_NULL, "%s: null erase table", name);
+    GV_REQUIRE(gv_aligned(er->tab, 4), GV_E_ALIGN, "%s: the erase table must be 4-byte aligned", name);
+    GV_REQUIRE(gv_aligned(mix, 4), GV_E_ALIGN, "%s: the mix table must be 4-byte aligned", name);
+    GV_REQUIRE(n_win == 1, GV_E_SHAPE, "%s: n_win=%d, one window only (the boxes are in the window's coordinates)", name, n_win);
+    GV_REQUIRE((long)n_img * 3 * crop * crop < (1L << 32), GV_E_SHAPE,
+               "%s: n_img * 3 * crop^2 = %ld, the noise generator's pixel index needs < 2^32", name, (long)n_img * 3 * crop * crop);
+    return GV_OK;
+}
+
+// mix == nullptr: gv_patchify; else gv_patchify_mix (has_mix says which was called: a NULL table is then an error).  er: the call
+// is gv_patchify_erase, with or without a mix table.
+template <bool F32OUT> static int patchify_launch(const gv_patchify_args* a, void* stream, const gv_mix_row* mix = nullptr, bool has_mix = false,
+                                                  const erase_in* er = nullptr) {
     GV_REQUIRE(a && a->tiles && a->patches, GV_E_NULL, "gv_patchify: null pointer");
     if (has_mix) {
         GV_REQUIRE(mix, GV_E_NULL, "gv_patchify_mix: null mix table");
@@ -351,14 +476,33 @@ template <bool F32OUT> static int patchify_launch(const gv_patchify_args* a, voi
     const float o0 = -a->mean[0] / a->std[0], o1 = -a->mean[1] / a->std[1], o2 = -a->mean[2] / a->std[2];
     const norm_consts k{s0, s1, s2, o0, o1, o2};
     const dim3 grid((unsigned)((total + 255) / 256));
+    if (er) {
+        if (const int rc = erase_check("gv_patchify_erase", mix, er, a->n_win, a->n_img, a->crop)) return rc;
+        if (mix)
+            hipLaunchKernelGGL((patchify_mix_kernel<F32OUT, true>), grid, dim3(256), 0, (hipStream_t)stream, *a, mix, P, side, k, *er);
+        else
+            hipLaunchKernelGGL((patchify_kernel<F32OUT, true>), grid, dim3(256), 0, (hipStream_t)stream, *a, P, side, k, *er);
+        GV_LAUNCH_CHECK("gv_patchify_erase");
+        return GV_OK;
+    }
     if (has_mix) {
-        hipLaunchKernelGGL(patchify_mix_kernel<F32OUT>, grid, dim3(256), 0, (hipStream_t)stream, *a, mix, P, side, k);
+        hipLaunchKernelGGL((patchify_mix_kernel<F32OUT, false>), grid, dim3(256), 0, (hipStream_t)stream, *a, mix, P, side, k, erase_in{nullptr, 0u});
         GV_LAUNCH_CHECK("gv_patchify_mix");
         return GV_OK;
     }
-    hipLaunchKernelGGL(patchify_kernel<F32OUT>, grid, dim3(256), 0, (hipStream_t)stream, *a, P, side, k);
+    hipLaunchKernelGGL((patchify_kernel<F32OUT, false>), grid, dim3(256), 0, (hipStream_t)stream, *a, P, side, k, erase_in{nullptr, 0u});
     GV_LAUNCH_CHECK("gv_patchify");
     return GV_OK;
+}
+extern "C" int gv_patchify_erase(const gv_patchify_erase_args* a, void* stream) {
+    GV_REQUIRE(a, GV_E_NULL, "gv_patchify_erase: null pointer");
+    const erase_in er{a->erase, a->seed};
+    return patchify_launch<false>(&a->p, stream, a->mix, false, &er);
+}
+extern "C" int gv_patchify_erase_f32(const gv_patchify_erase_args* a, void* stream) {
+    GV_REQUIRE(a, GV_E_NULL, "gv_patchify_erase_f32: null pointer");
+    const erase_in er{a->erase, a->seed};
+    return patchify_launch<true>(&a->p, stream, a->mix, false, &er);
 }
 extern "C" int gv_patchify(const gv_patchify_args* a, void* stream) { return patchify_launch<false>(a, stream); }
 extern "C" int gv_patchify_f32(const gv_patchify_args* a, void* stream) { return patchify_launch<true>(a, stream); }
@@ -372,7 +516,7 @@ extern "C" int gv_patchify_mix_f32(const gv_patchify_mix_args* a, void* stream) 
 }
 
 template <typename OT> static int patchify_nchw_launch(const gv_patchify_nchw_args* a, void* stream, const char* name,
-                                                       const gv_mix_row* mix = nullptr, bool has_mix = false) {
+                                                       const gv_mix_row* mix = nullptr, bool has_mix = false, const erase_in* er = nullptr) {
     GV_REQUIRE(a && a->images && a->patches, GV_E_NULL, "%s: null pointer", name);
     if (has_mix) {
         GV_REQUIRE(mix, GV_E_NULL, "%s: null mix table", name);
@@ -392,12 +536,31 @@ template <typename OT> static int patchify_nchw_launch(const gv_patchify_nchw_ar
     const int side = a->crop / 16, n_chunk = (side + NCHW_MAXP - 1) / NCHW_MAXP;
     const long blocks = (long)a->n_img * side * n_chunk;
     GV_REQUIRE(blocks < (1L << 31), GV_E_SHAPE, "%s: %ld workgroups exceed the grid", name, blocks);
-    if (has_mix)
-        hipLaunchKernelGGL((patchify_nchw_kernel<OT, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *a, side, n_chunk, mix);
-    else
-        hipLaunchKernelGGL((patchify_nchw_kernel<OT, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *a, side, n_chunk, mix);
+    const dim3 grid((unsigned)blocks);
+    const erase_in none{nullptr, 0u};
+    if (er) {
+        if (const int rc = erase_check(name, mix, er, a->n_win, a->n_img, a->crop)) return rc;
+        if (mix)
+            hipLaunchKernelGGL((patchify_nchw_kernel<OT, true, true>), grid, dim3(256), 0, (hipStream_t)stream, *a, side, n_chunk, mix, *er);
+        else
+            hipLaunchKernelGGL((patchify_nchw_kernel<OT, false, true>), grid, dim3(256), 0, (hipStream_t)stream, *a, side, n_chunk, mix, *er);
+    } else if (has_mix) {
+        hipLaunchKernelGGL((patchify_nchw_kernel<OT, true, false>), grid, dim3(256), 0, (hipStream_t)stream, *a, side, n_chunk, mix, none);
+    } else {
+        hipLaunchKernelGGL((patchify_nchw_kernel<OT, false, false>), grid, dim3(256), 0, (hipStream_t)stream, *a, side, n_chunk, mix, none);
+    }
     GV_LAUNCH_CHECK(name);
     return GV_OK;
+}
+extern "C" int gv_patchify_nchw_erase(const gv_patchify_nchw_erase_args* a, void* stream) {
+    GV_REQUIRE(a, GV_E_NULL, "gv_patchify_nchw_erase: null pointer");
+    const erase_in er{a->erase, a->seed};
+    return patchify_nchw_launch<bf16>(&a->p, stream, "gv_patchify_nchw_erase", a->mix, false, &er);
+}
+extern "C" int gv_patchify_nchw_erase_f32(const gv_patchify_nchw_erase_args* a, void* stream) {
+    GV_REQUIRE(a, GV_E_NULL, "gv_patchify_nchw_erase_f32: null pointer");
+    const erase_in er{a->erase, a->seed};
+    return patchify_nchw_launch<float>(&a->p, stream, "gv_patchify_nchw_erase_f32", a->mix, false, &er);
 }
 extern "C" int gv_patchify_nchw_mix(const gv_patchify_nchw_mix_args* a, void* stream) {
     GV_REQUIRE(a, GV_E_NULL, "gv_patchify_nchw_mix: null pointer");

@@ -451,7 +451,7 @@ class VitRunner:
 
     # ---- forward: tiles -> CLS features written into feats[row_off + seg.img0 ...]
     def forward(self, W: Weights, G: VitGroup, tiles_u8, windows, mean, std, feats, row_off: int = 0, fill=None, on_side: bool = False,
-                capture: Optional[Capture] = None, mix: Optional[torch.Tensor] = None):
+                capture: Optional[Capture] = None, mix: Optional[torch.Tensor] = None, erase=None):
         """windows: one list of (y0, x0) crop origins per segment; tiles_u8: one NHWC u8 tensor for all
         segments, or one per segment (pre-cut crops: each with the single window (0, 0)).  A float32 NCHW source (already
         normalised, engine.input_form) goes through gv_patchify_nchw instead, without mean / std.  ``fill``: per-tile normalised
@@ -459,11 +459,16 @@ class VitRunner:
         ``on_side``: the call is queued on the side stream (the teacher beside the student): its split-K products take that
         stream's scratch.  ``capture``: extra outputs of a forward-only pass (``Capture``); None issues exactly the default launches.
         ``mix``: a device mix table (gipvit.mixup.MixPlan.table) -- the single-segment, single-window batch is mixed inside the
-        patchify pass (gv_patchify_mix / gv_patchify_nchw_mix); None issues exactly the default launches."""
+        patchify pass (gv_patchify_mix / gv_patchify_nchw_mix); None issues exactly the default launches.
+        ``erase``: (device erase table, seed) of a gipvit.erasing.ErasePlan -- random erasing in that same pass, after ``fill`` and
+        ``mix`` (gv_patchify_erase / gv_patchify_nchw_erase); None issues exactly the default launches."""
         D, T, H = self.D, G.T, self.H
         cap = capture
         if mix is not None and (len(G.segs) != 1 or len(windows[0]) != 1):
             raise ValueError("mix: the supervised step's one window of one segment only")
+        if erase is not None and (len(G.segs) != 1 or len(windows[0]) != 1):
+            raise ValueError("erase: the supervised step's one window of one segment only")
+        ekw = {} if erase is None else {"erase": erase}        # the keyword exists for a step with a plan only
         if cap is not None:
             assert not G.save and len(G.segs) == 1, "capture: forward-only single-crop groups"
         tok0 = self.depth - len(cap.tokens) if cap is not None else self.depth        # first block whose normed tokens are captured
@@ -480,9 +485,9 @@ class VitRunner:
             if src.dtype == f32:
                 if fill is not None:
                     raise ValueError("fill= works on uint8 tiles: not with float32 NCHW input")
-                ops.patchify_nchw(src, wins, sg.crop, out=sg.patches, mix=mix)
+                ops.patchify_nchw(src, wins, sg.crop, out=sg.patches, mix=mix, **ekw)
             else:
-                ops.patchify(src, wins, sg.crop, mean, std, out=sg.patches, fill=fill, mix=mix)
+                ops.patchify(src, wins, sg.crop, mean, std, out=sg.patches, fill=fill, mix=mix, **ekw)
             if sg.pos is None:
                 pos = pos_full
             else:   # interpolate_pos_encoding: row 0 = cls pos, rows 1.. = M @ pos[1:]
@@ -1310,21 +1315,28 @@ class SupervisedEngine(TrainEngine):
     def forward(self, tiles_u8, ema: bool = False, fill=None, mix=None):
         """Inference / features: returns (logits f32 [B,C], CLS features bf16 [B,D]); ``ema``: with the EMA weights.
         ``tiles_u8``: uint8 NHWC [B, H, W, 3] or float32 NCHW [B, 3, H, W] already normalised (engine.input_form); the
-        image is its top-left img_size window.  ``mix``: a training step's gipvit.mixup.MixPlan (forward_backward)."""
+        image is its top-left img_size window.  ``mix``: a training step's gipvit.mixup.MixPlan (forward_backward).  Never
+        erases: random erasing belongs to the training step alone."""
+        return self._forward(tiles_u8, ema, fill, mix, None)
+
+    def _forward(self, tiles_u8, ema, fill, mix, erase):
         B, C, D, W = self.B, self.C, self.D, (self.Wema if ema else self.W)
         input_form(tiles_u8, B, None, (("fill", fill),))
-        self.vit.forward(W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats, fill=fill, mix=None if mix is None else mix.table)
+        ekw = {} if erase is None else {"erase": (erase.table, erase.seed)}
+        self.vit.forward(W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats, fill=fill, mix=None if mix is None else mix.table, **ekw)
         ops.small_matmul(self.feats, W.f("head.weight"), self.logits, B, C, D, sam=D, sak=1, sbk=1, sbn=D, bias=W.f("head.bias"))
         return self.logits, self.feats
 
-    def forward_backward(self, tiles_u8, target, fill=None, mix=None):
+    def forward_backward(self, tiles_u8, target, fill=None, mix=None, erase=None):
         """``mix``: this step's gipvit.mixup.MixPlan (on the device) or None.  With a plan the batch is mixed inside the patchify
-        pass and the loss takes the plan's partner / lam (train.py:1037-1040); ``self.prob`` is the softmax of the MIXED batch."""
+        pass and the loss takes the plan's partner / lam (train.py:1037-1040); ``self.prob`` is the softmax of the MIXED batch.
+        ``erase``: this step's gipvit.erasing.ErasePlan (on the device) or None: random erasing of the normalised batch inside the
+        same pass, after ``fill`` and ``mix`` (timm's prefetcher order); the labels and every loss are unchanged by it."""
         B, C, D, W = self.B, self.C, self.D, self.W
         if mix is not None and self.loss_kind == "lsce":
             raise ValueError("mix= needs loss='soft_ce' or 'bce': label-smoothing cross-entropy takes hard labels (train.py:832-842)")
         self.arena.g.zero_()
-        self.forward(tiles_u8, fill=fill, mix=mix)
+        self._forward(tiles_u8, False, fill, mix, erase)
         loss_scale = self.scaler.scale if self.scaler is not None else None
         if self.loss_kind == "lsce":
             ops.softmax_lsce(self.logits, target.view(-1), self.loss, self.dlogits, self.prob, B, C, self.smoothing, loss_scale=loss_scale)
@@ -1382,9 +1394,9 @@ class SupervisedEngine(TrainEngine):
         if self.scaler is not None:
             self.scaler.update(self.gnorm_sq)
 
-    def step(self, tiles_u8, target, lr=None, fill=None, mix=None):
+    def step(self, tiles_u8, target, lr=None, fill=None, mix=None, erase=None):
         assert target.dtype == torch.int64
-        self.forward_backward(tiles_u8, target, fill=fill, mix=mix)
+        self.forward_backward(tiles_u8, target, fill=fill, mix=mix, erase=erase)
         self.optimizer_step(lr)
         return self.loss
 

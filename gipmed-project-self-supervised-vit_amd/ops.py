@@ -64,11 +64,27 @@ def _mix_table(mix: torch.Tensor, n_tiles: int, windows) -> int:
     return mix.data_ptr()
 
 
+def _erase_table(erase, n_tiles: int, windows):
+    """(pointer, seed) of ``erase`` = (device erase table: uint8 [n_tiles * sizeof(gv_erase_row)], the step's 32-bit seed) --
+    gipvit.erasing.ErasePlan's ``table`` and ``seed``."""
+    import ctypes
+    tab, seed = erase
+    if not (tab.is_cuda and tab.dtype == torch.uint8 and tab.is_contiguous() and tab.numel() == n_tiles * ctypes.sizeof(L.gv_erase_row)):
+        raise ValueError(f"erase: expected a contiguous uint8 device tensor of {n_tiles} gv_erase_row records, got {tab.dtype} {tuple(tab.shape)} on {tab.device}")
+    if len(windows) != 1:
+        raise ValueError("erase: the boxes are in the window's coordinates -- one crop window only")
+    if not 0 <= int(seed) < (1 << 32):
+        raise ValueError(f"erase: the seed is one 32-bit value, got {seed}")
+    return tab.data_ptr(), int(seed)
+
+
 def patchify(tiles_u8: torch.Tensor, windows: Sequence[Sequence[int]], crop: int, mean, std,
-             out: Optional[torch.Tensor] = None, fill: Optional[torch.Tensor] = None, mix: Optional[torch.Tensor] = None) -> torch.Tensor:
+             out: Optional[torch.Tensor] = None, fill: Optional[torch.Tensor] = None, mix: Optional[torch.Tensor] = None, erase=None) -> torch.Tensor:
     """tiles_u8 [n_tiles, H, W, 3] u8 NHWC; windows [(y0, x0)] of side ``crop``.
     Returns bf16 patches [(len(windows) * n_tiles) * (crop/16)^2, 768], images crop-major.
-    ``mix``: a device mix table (gipvit.mixup) -- the batch is mixed in the same pass (gv_patchify_mix), one window only."""
+    ``mix``: a device mix table (gipvit.mixup) -- the batch is mixed in the same pass (gv_patchify_mix), one window only.
+    ``erase``: (device erase table, seed) of a gipvit.erasing.ErasePlan -- random erasing in the same pass, after ``fill`` and
+    ``mix`` (gv_patchify_erase), one window only."""
     _chk(tiles_u8, torch.uint8, "tiles")
     assert tiles_u8.dim() == 4 and tiles_u8.shape[-1] == 3 and tiles_u8.is_contiguous()
     n_tiles, H, W, _ = tiles_u8.shape
@@ -86,6 +102,10 @@ def patchify(tiles_u8: torch.Tensor, windows: Sequence[Sequence[int]], crop: int
     if fill is not None:        # f32 [n_tiles, 8] device: normalised fill boxes (Cutout after Normalize, MeanPixelRegularization)
         assert fill.is_cuda and fill.dtype == f32 and fill.shape == (n_tiles, 8) and fill.is_contiguous()
         a.fill = fill.data_ptr()
+    if erase is not None:
+        L.call("gv_patchify_erase" + _sfx(out), L.gv_patchify_erase_args(a, None if mix is None else _mix_table(mix, n_tiles, windows),
+                                                                         *_erase_table(erase, n_tiles, windows)), _stream())
+        return out
     if mix is not None:
         L.call("gv_patchify_mix" + _sfx(out), L.gv_patchify_mix_args(a, _mix_table(mix, n_tiles, windows)), _stream())
         return out
@@ -94,11 +114,12 @@ def patchify(tiles_u8: torch.Tensor, windows: Sequence[Sequence[int]], crop: int
 
 
 def patchify_nchw(images_f32: torch.Tensor, windows: Sequence[Sequence[int]], crop: int, out: Optional[torch.Tensor] = None,
-                  mix: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  mix: Optional[torch.Tensor] = None, erase=None) -> torch.Tensor:
     """images_f32 [n_tiles, 3, H, W] f32 NCHW, already normalised (any N / C / H strides, W stride 1); windows [(y0, x0)] of
     side ``crop``.  Returns patches [(len(windows) * n_tiles) * (crop/16)^2, 768] in the build's 16-bit format (the value
     rounded, no mean / std), or exact f32 rows when ``out`` is f32; images crop-major as ``patchify``.
-    ``mix``: a device mix table (gipvit.mixup): gv_patchify_nchw_mix, one window only."""
+    ``mix``: a device mix table (gipvit.mixup): gv_patchify_nchw_mix, one window only.
+    ``erase``: (device erase table, seed) of a gipvit.erasing.ErasePlan: gv_patchify_nchw_erase, after ``mix``, one window only."""
     _chk(images_f32, f32, "images")
     if images_f32.dim() != 4 or images_f32.shape[1] != 3 or images_f32.stride(-1) != 1:
         raise ValueError(f"images: expected float32 [n, 3, H, W] with W stride 1, got shape {tuple(images_f32.shape)} "
@@ -117,6 +138,10 @@ def patchify_nchw(images_f32: torch.Tensor, windows: Sequence[Sequence[int]], cr
     a.n_win, a.crop = len(windows), crop
     for i, (y, x) in enumerate(windows):
         a.win_y[i], a.win_x[i] = int(y), int(x)
+    if erase is not None:
+        L.call("gv_patchify_nchw_erase" + sfx, L.gv_patchify_nchw_erase_args(a, None if mix is None else _mix_table(mix, n_tiles, windows),
+                                                                             *_erase_table(erase, n_tiles, windows)), _stream())
+        return out
     if mix is not None:
         L.call("gv_patchify_nchw_mix" + sfx, L.gv_patchify_nchw_mix_args(a, _mix_table(mix, n_tiles, windows)), _stream())
         return out

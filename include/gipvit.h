@@ -123,6 +123,47 @@ typedef struct {
 } gv_patchify_nchw_mix_args;
 int gv_patchify_nchw_mix(const gv_patchify_nchw_mix_args* a, void* stream);
 
+/* ---- random erasing inside the patchify pass (--reprob / --remode / --recount: timm's RandomErasing as its PrefetchLoader
+ * builds it -- the reference's timm_train.py:621-624 passes the flags to timm's loader, its train.py:788-791 has the same
+ * call commented out).  One row of the device erase table per image i of the batch: up to GV_ERASE_MAX_BOXES boxes
+ * [yl, yh) x [xl, xh) in window coordinates (clamped to the window), applied in order on the NORMALISED values the
+ * network sees, after the mix table and after `fill`, so an erased pixel depends on no source pixel:
+ *   GV_ERASE_OFF    the row is bit-identical to the kernel without the table
+ *   GV_ERASE_VALUE  pixels of box b take value[b][c] (timm mode 'const': zeros; 'rand': one N(0,1) draw per box and
+ *                   channel, made on the host); a later box overwrites an earlier one
+ *   GV_ERASE_NOISE  pixels of every box take z(i, c, y, x) (timm mode 'pixel'), a counter-based N(0,1) deviate keyed by the
+ *                   pixel, not by the box or the launch geometry -- the u8 and the NCHW kernel, both output widths and
+ *                   gipvit.erasing.noise_reference agree.  With S = crop, idx = ((i * 3 + c) * S + y) * S + x as uint32 and
+ *                   fmix32 the murmur3 finaliser of gv_dropout:
+ *                       h1 = fmix32(seed + 0x9E3779B9 * (idx + 1));   h2 = fmix32(h1 + 0x6D2B79F5)
+ *                       u1 = ((h1 >> 8) + 1) * 2^-24;                 u2 = (h2 >> 8) * 2^-24
+ *                       z  = sqrtf(-2 * logf(u1)) * cosf(6.2831853f * u2)       (f32, the accurate library functions)
+ * In every mode the value is rounded once to the 16-bit format (kept f32 for _f32).  A row with an unknown mode or n_box
+ * outside 0 .. GV_ERASE_MAX_BOXES is treated as GV_ERASE_OFF.  A 16-pixel run (u8) or 4-pixel item (NCHW) wholly inside
+ * erased boxes loads nothing, neither from its image nor from its mix partner. */
+enum { GV_ERASE_OFF = 0, GV_ERASE_VALUE = 1, GV_ERASE_NOISE = 2 };
+#define GV_ERASE_MAX_BOXES 8
+typedef struct {
+    int32_t mode, n_box;
+    int32_t box[GV_ERASE_MAX_BOXES][4];   /* {yl, yh, xl, xh} */
+    float value[GV_ERASE_MAX_BOXES][3];   /* GV_ERASE_VALUE: normalised value per box and channel */
+} gv_erase_row;
+/* gv_patchify / gv_patchify_mix with an erase table: one window only (n_win == 1); n_img * 3 * crop^2 < 2^32. */
+typedef struct {
+    gv_patchify_args p;
+    const gv_mix_row* mix;        /* device [p.n_tiles], 4-byte aligned, or NULL: no mixing */
+    const gv_erase_row* erase;    /* device [p.n_tiles], 4-byte aligned */
+    uint32_t seed;                /* GV_ERASE_NOISE: one value per step */
+} gv_patchify_erase_args;
+int gv_patchify_erase(const gv_patchify_erase_args* a, void* stream);
+typedef struct {
+    gv_patchify_nchw_args p;
+    const gv_mix_row* mix;        /* device [p.n_tiles], 4-byte aligned, or NULL: no mixing */
+    const gv_erase_row* erase;    /* device [p.n_tiles], 4-byte aligned */
+    uint32_t seed;
+} gv_patchify_nchw_erase_args;
+int gv_patchify_nchw_erase(const gv_patchify_nchw_erase_args* a, void* stream);
+
 /* ---- random-resized crops of the tiles (DINO multi-crop input stage; absent from the
  * reference, whose tiles are augmented on the CPU by transformations.py:103-209 -- SURVEY 8f rank 1).
  * For crop n: box (y0, x0, h, w) of tile `tile` is resampled to out_size x out_size with
@@ -736,6 +777,8 @@ int gv_patchify_f32(const gv_patchify_args* a, void* stream);
 int gv_patchify_nchw_f32(const gv_patchify_nchw_args* a, void* stream);    /* exact copy into f32 patch rows */
 int gv_patchify_mix_f32(const gv_patchify_mix_args* a, void* stream);
 int gv_patchify_nchw_mix_f32(const gv_patchify_nchw_mix_args* a, void* stream);
+int gv_patchify_erase_f32(const gv_patchify_erase_args* a, void* stream);
+int gv_patchify_nchw_erase_f32(const gv_patchify_nchw_erase_args* a, void* stream);
 int gv_tokens_bwd_f32(const gv_tokens_bwd_args* a, void* stream);
 /* DINO head: zn / dz (l2norm), the weight-normalised last-layer matrix, and the student-logit gradient as f32 */
 int gv_l2norm_fwd_f32(const gv_l2norm_fwd_args* a, void* stream);

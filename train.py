@@ -240,6 +240,17 @@ def check_supported(args, log=_logger.warning):
         raise SystemExit(f"--batch-size {args.batch_size} with mixup / cutmix: image i is mixed with image B - 1 - i, the batch size must be even")
     if args.bce_loss and not mix_active(args) and not args.smoothing:
         log("--bce-loss with --smoothing 0 and no mixup: the reference selects plain cross-entropy there (train.py:838-844); so does this build")
+    # random erasing (timm_train.py:621-624 -> timm's loader; train.py:788-791 has the call commented out): the supervised step's batch
+    given = [f for f, on in (("--reprob", args.reprob), ("--remode", args.remode != "pixel"), ("--recount", args.recount != 1)) if on]
+    if args.dino and given:
+        raise SystemExit(f"{' '.join(given)} with --dino: random erasing belongs to the supervised step (timm's loader applies it to the "
+                         "labelled batch); the DINO crops have their own augmentation (--view-augment)")
+    if not 0.0 <= args.reprob <= 1.0:
+        raise SystemExit(f"--reprob {args.reprob} is a probability: 0 <= p <= 1 (0 = off)")
+    if args.remode not in ("pixel", "rand", "const"):
+        raise SystemExit(f"--remode {args.remode}: 'pixel' (per-pixel noise), 'rand' (one random colour per box) or 'const' (zeros)")
+    if not 1 <= args.recount <= 8:
+        raise SystemExit(f"--recount {args.recount}: 1 .. 8 boxes per image (the erase table's row holds GV_ERASE_MAX_BOXES = 8)")
     return img
 
 
@@ -265,6 +276,15 @@ def build_mix_sampler(args, img_size: int, rank: int = 0):
     return MixSampler(mixup_alpha=args.mixup, cutmix_alpha=args.cutmix, cutmix_minmax=args.cutmix_minmax, prob=args.mixup_prob,
                       switch_prob=args.mixup_switch_prob, mode=args.mixup_mode, batch=args.batch_size, img_size=img_size,
                       seed=args.seed + 101 * rank + 23)
+
+
+def build_erase_sampler(args, img_size: int, rank: int = 0):
+    """timm RandomErasing's draws from --reprob / --remode / --recount, or None at --reprob 0.  Seeded per rank like the other host streams."""
+    if not args.reprob > 0:
+        return None
+    from gipvit.erasing import EraseSampler
+    return EraseSampler(prob=args.reprob, mode=args.remode, count=args.recount, batch=args.batch_size, img_size=img_size,
+                        seed=args.seed + 211 * rank + 37)
 
 
 def amp_is_f16(args) -> bool:
@@ -542,6 +562,11 @@ def main(argv=None, transform=None):
     if mix_sampler is not None and primary:
         _logger.info("mixup / cutmix on the device: mixup %.3g cutmix %.3g minmax %s prob %.3g switch %.3g mode %s, loss %s", args.mixup, args.cutmix,
                      args.cutmix_minmax, args.mixup_prob, args.mixup_switch_prob, args.mixup_mode, loss_kind(args))
+    # random erasing (--reprob / --remode / --recount): boxes drawn on the host, erased inside the same patchify pass, after the mixing
+    erase_sampler = None if args.dino else build_erase_sampler(args, img, rank)
+    if erase_sampler is not None and primary:
+        _logger.info("random erasing on the device: reprob %.3g remode %s recount %d (training steps only, after mixup / cutmix)",
+                     args.reprob, args.remode, args.recount)
     view_sampler = None
     if args.view_augment:
         from gipvit.multicrop import ViewAugmentSampler
@@ -560,7 +585,7 @@ def main(argv=None, transform=None):
         # ... and the other host-side draw streams (--drop step seeds, random-resized-crop boxes, view augmentation), as JSON
         # strings of numpy's bit-generator state: plain str, loads with weights_only=True
         streams = {"drop": drop_rng, "crops": getattr(sampler, "rng", None), "views": getattr(view_sampler, "rng", None),
-                   "mix": getattr(mix_sampler, "rng", None)}
+                   "mix": getattr(mix_sampler, "rng", None), "erase": getattr(erase_sampler, "rng", None)}
         ex["host_rng"] = {k: json.dumps(g.bit_generator.state) for k, g in streams.items() if g is not None}
         if eng.scaler is not None:
             ex["amp_scaler"] = eng.scaler.state_dict()          # timm CheckpointSaver(amp_scaler=loss_scaler) key, train.py:585-602
@@ -587,7 +612,7 @@ def main(argv=None, transform=None):
         drop_rng = np.random.default_rng(args.seed + 7919 * rank + 11)
     if args.resume and isinstance(ck.get("host_rng"), dict):     # continue the draw streams where the saved run left them
         for k, g in (("drop", drop_rng), ("crops", getattr(sampler, "rng", None)), ("views", getattr(view_sampler, "rng", None)),
-                     ("mix", getattr(mix_sampler, "rng", None))):
+                     ("mix", getattr(mix_sampler, "rng", None)), ("erase", getattr(erase_sampler, "rng", None))):
             if g is not None and k in ck["host_rng"]:
                 g.bit_generator.state = json.loads(ck["host_rng"][k])
     cur_lr = lr
@@ -623,7 +648,8 @@ def main(argv=None, transform=None):
                 loss_t = eng.step(data, boxes=sampler.sample(dev) if sampler is not None else None, fill=fill if sampler is None else None,
                                   views=view_sampler.sample(dev) if view_sampler is not None else None, **sch)
             else:
-                loss_t = eng.step(data, target, lr=cur_lr, fill=fill, mix=mix_sampler.sample(dev) if mix_sampler is not None else None)
+                ekw = {"erase": erase_sampler.sample(dev)} if erase_sampler is not None else {}
+                loss_t = eng.step(data, target, lr=cur_lr, fill=fill, mix=mix_sampler.sample(dev) if mix_sampler is not None else None, **ekw)
                 probs.append(eng.prob[:, 1].clone() if eng.C > 1 else eng.prob[:, 0].clone()); targets.append(target.view(-1).clone())
             torch.cuda.synchronize()                  # train.py:1083
             batch_time.update(time.time() - end)
