@@ -19,42 +19,7 @@
 
 namespace {
 
-__device__ __attribute__((aligned(256))) unsigned short attn_zero_page[128];
-
-__device__ __forceinline__ void glds16(const void* src, GV_LDS char* dst) {
-    __builtin_amdgcn_global_load_lds((const GV_GLOBAL void*)src, (GV_LDS void*)dst, 16, 0, 0);
-}
-
-// stage rows [0, nrows_pad) of a [token][64] slice; rows >= nvalid are zero filled
-__device__ __forceinline__ void stage_rows(const bf16* __restrict__ gbase, long ld, int nvalid, int nrows_pad,
-                                           GV_LDS char* img, int wave, int nwaves, int lane) {
-    const int pieces = nrows_pad >> 3;
-    for (int piece = wave; piece < pieces; piece += nwaves) {
-        const int r = piece * 8 + (lane >> 3);
-        const int slot = lane & 7;
-        const int c = slot ^ (r & 7);
-        const bf16* src = r < nvalid ? gbase + (long)r * ld + c * 8 : (const bf16*)attn_zero_page + slot * 8;
-        glds16(src, img + __builtin_amdgcn_readfirstlane(piece * 1024));
-    }
-}
-
-__device__ __forceinline__ bf16x8 read_nat(GV_LDS char* img, int row, int chunk) {
-    return *(GV_LDS bf16x8*)(img + row * 128 + ((chunk ^ (row & 7)) << 4));
-}
-// transposed read: this lane addresses `row`, 16-column block dt, quarter p (0..3)
-__device__ __forceinline__ bf16x4 read_tr(GV_LDS char* img, int row, int dt, int p) {
-    const int c16 = 2 * dt + (p >> 1);
-    return GV_DS_READ_TR16(img + row * 128 + ((c16 ^ (row & 7)) << 4) + 8 * (p & 1));
-}
-__device__ __forceinline__ bf16x8 cat8(bf16x4 lo, bf16x4 hi) { return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7); }
-__device__ __forceinline__ bf16x8 pack8(f32x4 a, f32x4 b) {
-    return bf16x8{(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]};
-}
-template <int LO, int HI, class F>
-__device__ __forceinline__ void attn_static_for(F&& f) {
-    if constexpr (LO < HI) { f(std::integral_constant<int, LO>{}); attn_static_for<LO + 1, HI>(f); }
-}
-#define MFMA16(a, b, c) GV_MFMA_16x16x32((a), (b), (c))
+#include "attn_tiles.h"   // the LDS image, its LDS-DMA staging and the fragment reads (shared with attention_stream.hip)
 
 // ---------------------------------------------------------------------------------
 // forward

@@ -474,6 +474,9 @@ class VitRunner:
         tok0 = self.depth - len(cap.tokens) if cap is not None else self.depth        # first block whose normed tokens are captured
         cls_tail = self._cls_tail(G) and tok0 == self.depth
         all_q = cap is not None and cap.attn is not None and cap.attn_rows > 1
+        streams = any(sg.N > L.GV_ATTN_MAX_N for sg in G.segs)       # the fused varlen call holds whole sequences in LDS
+        if cap is not None and cap.attn is not None:
+            self.require_attention_maps(G)
 
         def capture_tokens(i, xc):
             ops.layernorm_fwd(xc, W.f("norm.weight"), W.f("norm.bias"), T, D, y=cap.tokens[i - tok0], mean=cap.stats[0], rstd=cap.stats[1])
@@ -540,13 +543,15 @@ class VitRunner:
             ops.linear(G.xn1[s], W.w(b + "attn.qkv.weight"), G.qkv[s], T, 3 * D, D, epilogue=E.EPI_BIAS, bias=W.f(b + "attn.qkv.bias"))
             # the last block under the CLS-only tail: only the CLS query's attention output is used (row 0 of every image)
             ql = 1 if (cls_tail and i == self.depth - 1 and self.sw.cls_qlimit and not all_q) else 0
-            if len(G.segs) > 1 and self.sw.varlen_attn:
+            if len(G.segs) > 1 and self.sw.varlen_attn and not streams:
                 # the crop lengths of a multi-crop pass in ONE call (gv_attention_fwd_varlen: the 37-token pairs fill the 197-token
                 # launch's half-empty last round); GIPVIT_VARLEN_ATTN=0 keeps one launch per segment for A/B runs
                 ops.attention_fwd_varlen(G.qkv[s], G.o[s], [(sg.n_img, sg.N, sg.lse[s]) for sg in G.segs], H, self.scale, q_limit=ql)
             else:
+                # a segment past one workgroup's LDS (N > 288: tiles above 256 px) streams K / V instead (gv_attention_fwd_stream)
                 for sg in G.segs:
-                    ops.attention_fwd(sg.rows(G.qkv[s]), sg.n_img, sg.N, H, self.scale, o=sg.rows(G.o[s]), lse=sg.lse[s], q_limit=ql)
+                    attn_fwd = ops.attention_fwd_stream if sg.N > L.GV_ATTN_MAX_N else ops.attention_fwd
+                    attn_fwd(sg.rows(G.qkv[s]), sg.n_img, sg.N, H, self.scale, o=sg.rows(G.o[s]), lse=sg.lse[s], q_limit=ql)
             if cap is not None and cap.attn is not None and i == self.depth - 1:
                 sg = G.segs[0]
                 ops.attention_probs(G.qkv[s], sg.lse[s], sg.n_img, sg.N, H, self.scale, cap.attn_rows, p=cap.attn)
@@ -579,6 +584,24 @@ class VitRunner:
             else:
                 ops.layernorm_fwd(sg.rows(xl), W.f("norm.weight"), W.f("norm.bias"), sg.n_img, D, x_stride=sg.N * D,
                                   y=feats[r0:r0 + sg.n_img], mean=sg.fstats[0], rstd=sg.fstats[1])
+
+    @staticmethod
+    def require_trainable(G: VitGroup):
+        """The attention backward holds a whole sequence in LDS: a group with a segment past GV_ATTN_MAX_N tokens runs forward only
+        (gv_attention_fwd_stream).  Raised before anything is launched."""
+        long = [sg.N for sg in G.segs if sg.N > L.GV_ATTN_MAX_N]
+        if long:
+            raise ValueError(f"backward: {long[0]} tokens per image ({G.segs[0].crop if len(G.segs) == 1 else 'multi-crop'} px) is past the "
+                             f"{L.GV_ATTN_MAX_N}-token limit of the attention backward (images up to 256 px at patch 16); "
+                             f"larger images run forward-only (inference, feature extraction)")
+
+    @staticmethod
+    def require_attention_maps(G: VitGroup):
+        """gv_attention_probs stops at GV_ATTN_MAX_N tokens, as the kernels it restates."""
+        long = [sg.N for sg in G.segs if sg.N > L.GV_ATTN_MAX_N]
+        if long:
+            raise ValueError(f"attention maps: {long[0]} tokens per image is past the {L.GV_ATTN_MAX_N}-token limit of gv_attention_probs "
+                             f"(images up to 256 px at patch 16); features and intermediate layers work up to {L.GV_ATTN_STREAM_MAX_N} tokens")
 
     def _cls_tail(self, G: VitGroup) -> bool:
         """Does this group run the last block's projection / MLP on the CLS rows only?  (Training groups: on the grouped
@@ -619,6 +642,7 @@ class VitRunner:
     def backward(self, W: Weights, G: VitGroup, dfeat: torch.Tensor, on_block_done=None):
         """``on_block_done(i)`` is called once block i's parameter gradients are complete
         (data-parallel engines start that block's all-reduce there)."""
+        self.require_trainable(G)
         D, T, H = self.D, G.T, self.H
         E = L
         ACC = E.EPI_ACCUM
@@ -1038,6 +1062,7 @@ class DinoEngine(TrainEngine):
         ``tiles_u8``: uint8 [B, tile, tile, 3] or float32 NCHW [B, 3, tile, tile] already normalised (engine.input_form): float
         input runs the fixed crop windows only (no ``boxes`` / ``views`` / ``fill``)."""
         B, G, V = self.B, self.G, self.V
+        self.vit.require_trainable(self.g_stu)
         input_form(tiles_u8, B, (self.tile, self.tile), (("fill", fill), ("boxes", boxes), ("views", views)))
         a = self.arena
         mj, mn = micro
@@ -1335,6 +1360,7 @@ class SupervisedEngine(TrainEngine):
         B, C, D, W = self.B, self.C, self.D, self.W
         if mix is not None and self.loss_kind == "lsce":
             raise ValueError("mix= needs loss='soft_ce' or 'bce': label-smoothing cross-entropy takes hard labels (train.py:832-842)")
+        self.vit.require_trainable(self.grp)
         self.arena.g.zero_()
         self._forward(tiles_u8, False, fill, mix, erase)
         loss_scale = self.scaler.scale if self.scaler is not None else None
@@ -1404,6 +1430,9 @@ class SupervisedEngine(TrainEngine):
 # --------------------------------------------------------------------------- #
 # forward-only encoder: slide-level inference / feature extraction
 # --------------------------------------------------------------------------- #
+F32_ATTN_MAX_N = 260       # gv_attention_fwd_f32 / gv_attention_bwd_f32 (csrc/f32path.hip)
+
+
 class FeatureExtractor:
     """The encoder run forward-only on the same kernels: per-tile CLS features (what the reference's
     ``validate()`` writes to ``<slide>_features.pt``, train.py:1281-1282) and, with a classifier head,
@@ -1419,6 +1448,12 @@ class FeatureExtractor:
         fp32, act = operand_mode(precision)
         if weights is not None:
             fp32, act = weights.fp32, (f32 if weights.fp32 else bf16)
+        n_tok = (img_size // 16) ** 2 + 1
+        if img_size % 16 or not 16 <= img_size or n_tok > L.GV_ATTN_STREAM_MAX_N:
+            raise ValueError(f"img_size {img_size}: a multiple of 16 up to 512 ({L.GV_ATTN_STREAM_MAX_N} tokens, gv_attention_fwd_stream)")
+        if fp32 and n_tok > F32_ATTN_MAX_N:
+            raise ValueError(f"precision='fp32' with img_size {img_size}: {n_tok} tokens per image, the fp32 operand mode's attention "
+                             f"stops at {F32_ATTN_MAX_N} (256-px images); larger images run in the 16-bit mode")
         dev = torch.device(device)
         self.dev, self.arch, self.B, self.img, self.C = dev, arch, batch, img_size, num_classes
         self.D = ARCHS[arch]["embed_dim"]
@@ -1483,6 +1518,7 @@ class FeatureExtractor:
         launch per batch) -> (features, logits, attention f32 [n, H, N]).  ``attention[:, :, 1:]`` reshaped to
         (img / 16, img / 16) is DINO's attention map of each head."""
         self._check_size(tiles_u8)
+        self.vit.require_attention_maps(self.grp)
         attn = torch.empty(tiles_u8.shape[0], self.vit.H, self.grp.segs[0].N, dtype=f32, device=self.dev)
         feats, logits = self._run(tiles_u8, attn)
         return feats, logits, attn
@@ -1520,6 +1556,7 @@ class FeatureExtractor:
         """The reference's get_last_selfattention (vit.pyc@L255-262) over any number of tiles (batched and padded as ``run``):
         the last block's softmax attention f32 [n, H, N, N], or only the CLS query's row, [n, H, 1, N], with ``cls_only``."""
         self._check_size(tiles_u8)
+        self.vit.require_attention_maps(self.grp)
         N, H = self.grp.segs[0].N, self.vit.H
         q = 1 if cls_only else N
         out = torch.empty(tiles_u8.shape[0], H, q, N, dtype=f32, device=self.dev)

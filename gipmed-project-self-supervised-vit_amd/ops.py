@@ -319,6 +319,22 @@ def attention_fwd(qkv, n_img: int, N: int, H: int, scale: float, o=None, lse=Non
     return o, lse
 
 
+def attention_fwd_stream(qkv, n_img: int, N: int, H: int, scale: float, o=None, lse=None, q_limit: int = 0):
+    """``attention_fwd`` for N up to ``_lib.GV_ATTN_STREAM_MAX_N`` tokens (gv_attention_fwd_stream: K / V streamed through LDS under
+    an online softmax).  Forward only and 16-bit only: the fp32 operand mode keeps its N <= 260.  ``q_limit`` > 0: whole blocks of
+    ``_lib.GV_ATTN_STREAM_QBLOCK`` query rows that hold a row < q_limit are computed, o / lse behind them are left untouched."""
+    dev = qkv.device
+    if qkv.dtype != bf16:
+        raise TypeError(f"attention_fwd_stream: qkv must be {bf16}, got {qkv.dtype} (there is no fp32 operand form: that mode stops at N = 260)")
+    o = torch.empty(n_img * N, H * 64, dtype=qkv.dtype, device=dev) if o is None else o
+    lse = torch.empty(n_img, H, N, dtype=f32, device=dev) if lse is None else lse
+    a = L.gv_attention_fwd_args(qkv.data_ptr(), o.data_ptr(), lse.data_ptr(), n_img, N, H, scale, q_limit)
+    if o.dtype != qkv.dtype:
+        raise TypeError(f"attention_fwd_stream: qkv is {qkv.dtype} but o is {o.dtype}")
+    L.call("gv_attention_fwd_stream", a, _stream())
+    return o, lse
+
+
 def attention_probs(qkv, lse, n_img: int, N: int, H: int, scale: float, q_rows: int, p=None):
     """The softmax matrix of the attention that ``attention_fwd`` computed from the same ``qkv`` and left ``lse`` for:
     f32 [n_img, H, q_rows, N], query rows 0..q_rows-1 of every image (1 = the CLS row; lse must be valid for them); see

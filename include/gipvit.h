@@ -456,6 +456,23 @@ typedef struct {
 } gv_attention_fwd_args;
 int gv_attention_fwd(const gv_attention_fwd_args* a, void* stream);
 
+/* Streaming forward for sequences past the N <= 288 of gv_attention_fwd (tiles up to 512 px at patch 16: 1 025 tokens).  Inputs and
+ * outputs are those of gv_attention_fwd -- qkv 16-bit [n_img*N, 3, H, 64], o 16-bit [n_img*N, H, 64], lse f32 [n_img, H, N] (the
+ * natural-log sum-exp of the scaled scores), head_dim 64 -- for 1 <= N <= GV_ATTN_STREAM_MAX_N (65 key tiles of 16); any other N
+ * returns GV_E_SHAPE with the limit in gv_last_error(), a null pointer GV_E_NULL, both before any launch.  scale must be > 0
+ * (GV_E_SHAPE otherwise: the running max is taken over the unscaled scores).
+ * K / V pass through LDS in key blocks under an online softmax: running max and running sum per query row in f32, an f32 O
+ * accumulator rescaled when the max moves, P rounded to the 16-bit format before P V (as gv_attention_fwd does), one division at
+ * the end, lse = max + log(sum).  Keys >= N of the last block are never counted, query rows >= N never stored.
+ * q_limit > 0: only whole blocks of GV_ATTN_STREAM_QBLOCK query rows that hold a row < q_limit are computed; o / lse rows behind
+ * the last such block are left untouched (the CLS-only last block asks for 1).  0 = every query.
+ * No atomics: the result of an (image, head) pair depends neither on the launch geometry nor on the other pairs of the launch.
+ * One plain launch (no cooperative launch, nothing waits on another workgroup), 32 KB of LDS.  There is no backward and no _f32
+ * form: training, attention maps (gv_attention_probs) and the fp32 operand mode keep their limits.                              */
+#define GV_ATTN_STREAM_MAX_N 1040
+#define GV_ATTN_STREAM_QBLOCK 128
+int gv_attention_fwd_stream(const gv_attention_fwd_args* a, void* stream);
+
 /* Varlen forward (the `cu_seqlens` form): the token-concatenated row space of a multi-crop pass -- segment i
  * holds n_img[i] images of N[i] tokens, its rows start where segment i - 1 ends, qkv / o cover all segments, lse[i] is
  * segment i's f32 [n_img[i], H, N[i]].  A long (128 < N <= 224) + a short (32 < N <= 64) segment run as ONE launch

@@ -254,6 +254,39 @@ def check_supported(args, log=_logger.warning):
     return img
 
 
+ATTN_TRAIN_MAX_TOKENS = 288     # gv_attention_bwd / gv_attention_probs hold one sequence in LDS (include/gipvit.h)
+ATTN_STREAM_MAX_TOKENS = 1040   # gv_attention_fwd_stream: forward only
+ATTN_F32_MAX_TOKENS = 260       # the fp32 operand mode's attention
+
+
+def check_token_limits(args):
+    """Image sizes against the attention kernels' sequence limits, before any device work: a run that TRAINS needs every crop within
+    288 tokens (256 px at patch 16); --extract_features on the supervised route is forward-only and goes up to 512 px
+    (gv_attention_fwd_stream); --extract-attention, --dino --extract_features (it builds the DINO training engine) and
+    --precision fp32 keep the 288- / 260-token limits."""
+    tokens = lambda px: (px // 16) ** 2 + 1
+    if args.dino:
+        sizes = [("--global-crop-size", args.global_crop_size)] + ([("--local-crop-size", args.local_crop_size)] if args.local_crops_number else [])
+    else:
+        sizes = [("image size (--img-size / --input-size / --tile-size)", args.img_size or (args.input_size[1] if args.input_size else None) or args.tile_size)]
+    for flag, px in sizes:
+        n = tokens(px)
+        if args.dino and args.extract_features and n > ATTN_TRAIN_MAX_TOKENS:
+            raise SystemExit(f"--dino --extract_features with {flag} {px}: {n} tokens per image, the DINO route builds its training engine and stops at "
+                             f"{ATTN_TRAIN_MAX_TOKENS} tokens (256 px at patch 16); extract features above that on the supervised route")
+        if not args.extract_features and n > ATTN_TRAIN_MAX_TOKENS:
+            raise SystemExit(f"{flag} {px}: {n} tokens per image, training stops at {ATTN_TRAIN_MAX_TOKENS} tokens (256 px at patch 16: the attention "
+                             f"backward holds a whole sequence in LDS); larger tiles run forward-only -- --extract_features, up to 512 px")
+        if args.extract_features and args.extract_attention and n > ATTN_TRAIN_MAX_TOKENS:
+            raise SystemExit(f"--extract-attention with {flag} {px}: {n} tokens per image, attention maps stop at {ATTN_TRAIN_MAX_TOKENS} tokens "
+                             f"(256 px at patch 16); the features themselves work up to 512 px")
+        if args.extract_features and n > ATTN_STREAM_MAX_TOKENS:
+            raise SystemExit(f"{flag} {px}: {n} tokens per image, the streaming attention forward stops at {ATTN_STREAM_MAX_TOKENS} tokens (512 px at patch 16)")
+        if args.extract_features and args.precision == "fp32" and n > ATTN_F32_MAX_TOKENS:
+            raise SystemExit(f"--precision fp32 with {flag} {px}: {n} tokens per image, the fp32 operand mode's attention stops at "
+                             f"{ATTN_F32_MAX_TOKENS} tokens (256 px); larger tiles run in the 16-bit mode")
+
+
 def mix_active(args) -> bool:
     """train.py:755."""
     return args.mixup > 0 or args.cutmix > 0.0 or args.cutmix_minmax is not None
@@ -348,6 +381,7 @@ def main(argv=None, transform=None):
     device augmentation runs, and --random-crops / --view-augment / a named --transform_type are refused."""
     args, args_text = parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
+    check_token_limits(args)
     hook_format = hook_batch_format(args, transform, argv) if transform is not None else None
     if not torch.cuda.is_available() or not str(args.device).startswith("cuda"):
         raise SystemExit("train.py: an MI355X is required (device=%s, cuda available=%s); the HIP hot path has no CPU fallback"
