@@ -18,6 +18,20 @@ constexpr int MAXV = 16, MAXG = 4;
 template <typename DT> __device__ __forceinline__ float ex(float x) { if constexpr (sizeof(DT) == 4) return expf(x); else return __expf(x); }
 template <typename DT> __device__ __forceinline__ float lg(float x) { if constexpr (sizeof(DT) == 4) return logf(x); else return __logf(x); }
 
+// logit * (1 / temperature) as loss_grad_kernel forms it.  row_stats_kernel rounds this product before it takes the row maximum and
+// the sum; contracted into an FMA with the "- rm" that follows, the second pass saw the UNROUNDED product: the row's largest
+// element came out as exp(residual - rl) instead of exp(-rl), every probability of the row was off by the same factor
+// (up to half an ulp of the scaled maximum, ~4e-6 at teacher temperature 0.04), and the loss with it.  The f32 operand mode rounds
+// the product on its own, as pass 1 does; the 16-bit path keeps its code: the factor is far below its rounding.
+template <typename DT> __device__ __forceinline__ float scaled(float x, float inv_t) {
+    if constexpr (sizeof(DT) == 4) {
+#pragma clang fp contract(off)
+        return x * inv_t;
+    } else {
+        return x * inv_t;
+    }
+}
+
 // one block per logits row: running max / sum-exp of the temperature-scaled row.  A thread takes RS_U 16-B pieces per trip, both
 // requested before the first is used, folds them into one maximum and rescales its running sum once per trip.  Measured at the
 // headline shape (768 rows x 256 KB, tools/loss_bench.py, whole call): one piece per trip 101 us, two 93, four 102, eight 119;
@@ -50,7 +64,9 @@ __global__ __launch_bounds__(NT) void row_stats_kernel(gv_dino_loss_args a) {
         float lm = -INFINITY;
 #pragma unroll
         for (int u = 0; u < RS_U; ++u) {
-            v[u] *= inv_t;
+            if constexpr (sizeof(DT) == 4) {        // rounded on its own, as both later passes form it
+                _Pragma("unroll") for (int e = 0; e < 4; ++e) v[u][e] = scaled<DT>(v[u][e], inv_t);
+            } else v[u] *= inv_t;
             lm = fmaxf(lm, fmaxf(fmaxf(v[u][0], v[u][1]), fmaxf(v[u][2], v[u][3])));
         }
         if (lm > m) { s *= ex<DT>(m - lm); m = lm; }       // (piece 0 of a trip is always inside the row: lm is finite)
@@ -103,7 +119,7 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(gv_dino_loss_args a, int
                     const float rm = a.workspace[2 * row], rl = a.workspace[2 * row + 1];
                     csum += raw;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) t[iq][e] = ex<DT>((raw[e] - c[e]) * inv_tt - rm - rl);
+                    for (int e = 0; e < 4; ++e) t[iq][e] = ex<DT>(scaled<DT>(raw[e] - c[e], inv_tt) - rm - rl);
                     tsum += t[iq];
                 }
             }
@@ -118,7 +134,7 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(gv_dino_loss_args a, int
                 f32x4 g;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float logp = sv[e] * inv_ts - rm - rl;
+                    const float logp = scaled<DT>(sv[e], inv_ts) - rm - rl;
                     loss -= ts[e] * logp;
                     g[e] = coef * (nv * ex<DT>(logp) - ts[e]);
                 }
@@ -130,10 +146,64 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(gv_dino_loss_args a, int
 #pragma unroll
         for (int e = 0; e < 4; ++e) atomicAdd(a.center_sum + k + e, csum[e]);
     }
+    // the fp32 operand mode sums its loss in a fixed order (loss_rows_kernel below); here one f32 atomic per workgroup, in arrival order
+    if constexpr (sizeof(DT) == 4) return;
     loss = wave_sum(loss);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = loss;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(a.loss, (red[0] + red[1] + red[2] + red[3]) * inv_pairs_b);
+}
+
+// fp32 operand mode only: the loss without atomics.  loss_grad_kernel's workgroups (k-blocks x batch slices, 640 at K = 65536 / B = 19)
+// each add a partial sum to one f32 in arrival order: a random walk of ~sqrt(n) half-ulps of the running sum that changes from run
+// to run (measured 2.6e-6 ... 2.4e-5 at a loss of 45, where plain f32 has 2.6e-6).  Here one workgroup per STUDENT row (v, b) sums
+// -sum_k (sum_{iq != v} t_iq[b, k]) logp_v[b, k] over the whole row with the arithmetic of loss_grad_kernel, and leaves the row's
+// loss in the row's own first workspace slot -- its maximum, which only this workgroup reads (the teacher rows' slots stay);
+// loss_rows_sum_kernel adds the V * B row losses in a fixed order.  One more pass over the logits: the price of the exact mode.
+__global__ __launch_bounds__(256) void loss_rows_kernel(gv_dino_loss_args a) {
+    __shared__ float red[4];
+    if (a.hyper) { a.teacher_temp = a.hyper[GV_HYP_TEACHER_TEMP]; a.student_temp = a.hyper[GV_HYP_STUDENT_TEMP]; }
+    const int row = blockIdx.x, B = a.B, G = a.G, K = a.K;
+    const int v = row / B, b = row - v * B;
+    const float inv_ts = 1.0f / a.student_temp, inv_tt = 1.0f / a.teacher_temp;
+    const float rm = a.workspace[2 * row], rl = a.workspace[2 * row + 1];
+    float tm[MAXG], tl[MAXG];
+#pragma unroll
+    for (int iq = 0; iq < MAXG; ++iq) {
+        const int trow = a.V * B + iq * B + b;
+        tm[iq] = iq < G ? a.workspace[2 * trow] : 0.f;
+        tl[iq] = iq < G ? a.workspace[2 * trow + 1] : 0.f;
+    }
+    float loss = 0.f;
+    for (int k = threadIdx.x * 4; k < K; k += 1024) {
+        const f32x4 sv = *(const f32x4*)(a.student + (long)row * K + k);
+        const f32x4 c = *(const f32x4*)(a.center + k);
+        f32x4 ts = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int iq = 0; iq < MAXG; ++iq) {
+            if (iq < G && iq != v) {
+                const f32x4 raw = *(const f32x4*)(a.teacher + (long)(iq * B + b) * K + k);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) ts[e] += expf(scaled<float>(raw[e] - c[e], inv_tt) - tm[iq] - tl[iq]);
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) loss -= ts[e] * (scaled<float>(sv[e], inv_ts) - rm - rl);
+    }
+    loss = wave_sum(loss);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = loss;
+    __syncthreads();                                   // every thread has read the row's slots by now
+    if (threadIdx.x == 0) a.workspace[2 * row] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void loss_rows_sum_kernel(gv_dino_loss_args a, float inv_pairs_b) {
+    __shared__ float red[4];
+    float s = 0.f;
+    for (int r = threadIdx.x; r < a.V * a.B; r += 256) s += a.workspace[2 * r];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) a.loss[0] = ((red[0] + red[1]) + (red[2] + red[3])) * inv_pairs_b;
 }
 
 template <typename DT> int dino_loss_launch(const gv_dino_loss_args* a, void* stream) {
@@ -162,6 +232,12 @@ template <typename DT> int dino_loss_launch(const gv_dino_loss_args* a, void* st
     const float coef = gs * inv_pairs_b / a->student_temp;
     hipLaunchKernelGGL(loss_grad_kernel<DT>, dim3(kblocks, bsplit), dim3(256), 0, s, *a, b_per, coef, inv_pairs_b);
     GV_LAUNCH_CHECK("gv_dino_loss(loss_grad)");
+    if constexpr (sizeof(DT) == 4) {
+        hipLaunchKernelGGL(loss_rows_kernel, dim3(a->V * a->B), dim3(256), 0, s, *a);
+        GV_LAUNCH_CHECK("gv_dino_loss(loss_rows)");
+        hipLaunchKernelGGL(loss_rows_sum_kernel, dim3(1), dim3(256), 0, s, *a, inv_pairs_b);
+        GV_LAUNCH_CHECK("gv_dino_loss(loss_rows_sum)");
+    }
     return GV_OK;
 }
 

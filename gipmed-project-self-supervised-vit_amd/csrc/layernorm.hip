@@ -36,6 +36,14 @@ template <int VEC> __device__ __forceinline__ void stb(bf16* p, const float* o) 
     *(typename VecB<VEC>::T*)p = v;
 }
 
+// A product rounded on its own: it may not be contracted into an FMA with the subtraction that consumes it.  The row mean is
+// sum * (1 / D) and 1 / D (D = 3 * 2^k) is not exact in f32; the rounding of the product absorbs that 2^-25, but contracted into
+// v - mean it reached the centred values unrounded: a row of variance 0 left ln_fwd_kernel<1> as beta +- |x| 2^-25 rstd gamma.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
 // grid-stride over rows, one wave per row; the next row's loads are issued before the current
 // row's reductions so every wave keeps two rows of HBM traffic in flight
 // F32IO: the fp32 parity mode (f32path.hip) keeps activations in f32 -- y / dy / gb are f32 rows instead of bf16
@@ -66,7 +74,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(gv_layernorm_fwd_args a) {
         for (int i = 0; i < 3; ++i)
 #pragma unroll
             for (int j = 0; j < VEC; ++j) s += v[i][j];
-        const float mean = wave_sum(s) * (1.0f / D);
+        const float mean = mul_rn(wave_sum(s), 1.0f / D);
         float q = 0.f;
 #pragma unroll
         for (int i = 0; i < 3; ++i)

@@ -623,7 +623,8 @@ def test_tokens_and_misc(dev):
     assert torch.equal(dst, src.to(bf16))
     ws = torch.empty(1024, device=dev); out = torch.empty(1, device=dev)
     o.sumsq(src, ws, out)
-    assert abs(float(out) - float((src.double() ** 2).sum())) < 1e-3 * n
+    ref = float((src.double() ** 2).sum())
+    assert abs(float(out) - ref) <= 1e-5 * ref          # <= 64 additions of non-negative terms per result: 64 * 2^-24 < 4e-6
 
 
 def test_adamw_ema(dev):
