@@ -133,6 +133,8 @@ gv_softmax_mix_loss_args = _struct("gv_softmax_mix_loss_args", [
     ("logits", vp), ("target", vp), ("partner", vp), ("lam", vp), ("loss", vp), ("dlogits", vp), ("prob", vp), ("B", i32), ("C", i32),
     ("smoothing", f32), ("kind", i32), ("has_threshold", i32), ("threshold", f32), ("loss_scale", vp)])
 gv_gather_cls_args = _struct("gv_gather_cls_args", [("x", vp), ("y", vp), ("n_img", i32), ("N", i32), ("D", i32)])
+gv_token_mean_fwd_args = _struct("gv_token_mean_fwd_args", [("x", vp), ("pooled", vp), ("n_img", i32), ("N", i32), ("D", i32)])
+gv_token_mean_bwd_args = _struct("gv_token_mean_bwd_args", [("dpool", vp), ("g", vp), ("gb", vp), ("gb_scale", vp), ("n_img", i32), ("N", i32), ("D", i32)])
 gv_store_f32_args = _struct("gv_store_f32_args", [("dst", vp), ("vals", f32 * 16), ("n", i32)])
 gv_cast_bf16_args = _struct("gv_cast_bf16_args", [("src", vp), ("dst", vp), ("n", i64)])
 gv_sumsq_args = _struct("gv_sumsq_args", [("x", vp), ("n", i64), ("workspace", vp), ("out", vp), ("accumulate", i32)])
@@ -181,6 +183,7 @@ ENTRY_POINTS = {
     "gv_tokens_bwd_f32": gv_tokens_bwd_args, "gv_l2norm_fwd_f32": gv_l2norm_fwd_args, "gv_l2norm_bwd_f32": gv_l2norm_bwd_args,
     "gv_weightnorm_fwd_f32": gv_weightnorm_fwd_args, "gv_dino_loss_f32": gv_dino_loss_args,
     "gv_knn_vote": gv_knn_vote_args,
+    "gv_token_mean_fwd": gv_token_mean_fwd_args, "gv_token_mean_bwd": gv_token_mean_bwd_args, "gv_token_mean_bwd_f32": gv_token_mean_bwd_args,
 }
 PLAIN_SYMBOLS = ("gv_version", "gv_last_error", "gv_target", "gv_act_format", "gv_linear_workspace_bytes", "gv_workspace_bytes", "gv_linear_timing", "gv_linear_timing_read",
                  "gv_linear_ln_blocks", "gv_knn_workspace_bytes")

@@ -148,8 +148,26 @@ class SideStream:
 # --------------------------------------------------------------------------- #
 # parameter inventory (timm / DINO state_dict names)
 # --------------------------------------------------------------------------- #
-def vit_param_specs(arch: str, img_size: int, num_classes: int = 0) -> "OrderedDict[str, Tuple[int, ...]]":
+POOLS = ("token", "avg")
+
+
+def resolve_pool(global_pool: Optional[str]) -> str:
+    """The reference's ``--gp`` (train.py:122, handed to create_model at train.py:490) -> "token" | "avg".  None is the model's
+    default, "token" (timm treats an unset --gp so).  "" is refused: timm then applies the head to every token and the
+    reference's loss breaks on the [B, N, C] logits; "max" / "avgmax" / anything else is not a pooling of timm's ViT."""
+    if global_pool is None:
+        return "token"
+    if global_pool not in POOLS:
+        raise ValueError(f"global_pool {global_pool!r}: 'token' (the CLS token, the default) or 'avg' (mean of the patch tokens + fc_norm)"
+                         + ("; '' would hand every token to the head (no pooling), which the reference's loss cannot take" if global_pool == "" else ""))
+    return global_pool
+
+
+def vit_param_specs(arch: str, img_size: int, num_classes: int = 0, global_pool: str = "token") -> "OrderedDict[str, Tuple[int, ...]]":
+    """``global_pool`` "avg" (timm 0.8 VisionTransformer): the final ``norm`` is Identity and ``fc_norm``, a
+    LayerNorm over the mean of the patch tokens, takes its place in the order."""
     a = ARCHS[arch]
+    fnorm = "fc_norm." if resolve_pool(global_pool) == "avg" else "norm."
     D, depth = a["embed_dim"], a["depth"]
     P = (img_size // 16) ** 2
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
@@ -165,7 +183,7 @@ def vit_param_specs(arch: str, img_size: int, num_classes: int = 0) -> "OrderedD
         s[b + "norm2.weight"] = (D,); s[b + "norm2.bias"] = (D,)
         s[b + "mlp.fc1.weight"] = (4 * D, D); s[b + "mlp.fc1.bias"] = (4 * D,)
         s[b + "mlp.fc2.weight"] = (D, 4 * D); s[b + "mlp.fc2.bias"] = (D,)
-    s["norm.weight"] = (D,); s["norm.bias"] = (D,)
+    s[fnorm + "weight"] = (D,); s[fnorm + "bias"] = (D,)
     if num_classes > 0:
         s["head.weight"] = (num_classes, D); s["head.bias"] = (num_classes,)
     return s
@@ -290,11 +308,13 @@ class Segment:
 
 
 class VitGroup:
-    def __init__(self, arch: str, segments, img_size: int, device, save: bool, act=bf16):
+    def __init__(self, arch: str, segments, img_size: int, device, save: bool, act=bf16, pool: str = "token"):
         """segments: [(n_img, crop), ...] in feature-row order.  ``act``: element type of the activation / gradient buffers
-        that feed GEMMs and attention -- bf16 on the training path, f32 in the fp32 operand mode (csrc/f32path.hip)."""
-        assert act in (bf16, f32)
-        self.act = act
+        that feed GEMMs and attention -- bf16 on the training path, f32 in the fp32 operand mode (csrc/f32path.hip).
+        ``pool``: "token" (the feature is the CLS row) or "avg" (the mean of the patch tokens, then fc_norm: every token of the
+        last block is computed and differentiated)."""
+        assert act in (bf16, f32) and pool in POOLS
+        self.act, self.pool = act, pool
         a = ARCHS[arch]
         D, depth, H = a["embed_dim"], a["depth"], a["num_heads"]
         self.save = save
@@ -327,6 +347,10 @@ class VitGroup:
             self.gb3, self.gb4 = e((T, D), act), e((T, D), act)
             self.dh_b, self.dqkv_b = e((T, 4 * D), act), e((T, 3 * D), act)
 
+        if pool == "avg":      # the pooled rows in front of fc_norm (its statistics: the segments' fstats) and their gradient
+            self.pooled = e((self.n_img, D), f32)
+            if save:
+                self.dpool = e((self.n_img, D), f32)
         self.depth, self.device = depth, device
         # CLS-only last block (VitRunner.cls_last): buffers over the n_img CLS rows, allocated on first use (alloc_cls)
         self.c_o = None
@@ -578,7 +602,12 @@ class VitRunner:
         xl = G.xbuf(2 * self.depth)
         for sg in G.segs:
             r0 = row_off + sg.img0
-            if cls_tail:         # the last block left its output for the CLS rows only, contiguous
+            if G.pool == "avg":     # mean of the patch tokens -> fc_norm (timm global_pool='avg': the final norm is Identity)
+                pooled = G.pooled[sg.img0:sg.img0 + sg.n_img]
+                ops.token_mean_fwd(sg.rows(xl), pooled, sg.n_img, sg.N, D)
+                ops.layernorm_fwd(pooled, W.f("fc_norm.weight"), W.f("fc_norm.bias"), sg.n_img, D,
+                                  y=feats[r0:r0 + sg.n_img], mean=sg.fstats[0], rstd=sg.fstats[1])
+            elif cls_tail:         # the last block left its output for the CLS rows only, contiguous
                 ops.layernorm_fwd(G.c_xc[sg.img0:sg.img0 + sg.n_img], W.f("norm.weight"), W.f("norm.bias"), sg.n_img, D,
                                   y=feats[r0:r0 + sg.n_img], mean=sg.fstats[0], rstd=sg.fstats[1])
             else:
@@ -605,8 +634,9 @@ class VitRunner:
 
     def _cls_tail(self, G: VitGroup) -> bool:
         """Does this group run the last block's projection / MLP on the CLS rows only?  (Training groups: on the grouped
-        weight-gradient path and without --drop, whose backward this build restates for that case.)"""
-        return self.cls_last and G.dropout is None and (not G.save or self.group_dw)
+        weight-gradient path and without --drop, whose backward this build restates for that case.)  Never for a mean-pooled
+        group: every token of the last block reaches the feature."""
+        return G.pool != "avg" and self.cls_last and G.dropout is None and (not G.save or self.group_dw)
 
     def _last_block_tail_fwd(self, W: Weights, G: VitGroup, i: int, xa: torch.Tensor, on_side: bool):
         """x + proj(attention) -> norm2 -> MLP -> residual of block i for the CLS rows only (vit.pyc@L146-152 on the rows that
@@ -629,7 +659,11 @@ class VitRunner:
     def prepare_backward(self, G: VitGroup):
         """Zero the backward scratch that is accumulated into or only partly written: the residual gradient (the final norm's backward
         writes the CLS rows), and the attention-output gradient of the CLS-only last block / the first dY buffer otherwise.  Stream-
-        ordered fills with no input: an engine may issue them early on its side stream (DinoEngine does, beside the forward pass)."""
+        ordered fills with no input: an engine may issue them early on its side stream (DinoEngine does, beside the forward pass).
+        A mean-pooled group needs none: gv_token_mean_bwd writes every row of both."""
+        if G.pool == "avg":
+            G.prepared = True
+            return
         G.g.zero_()
         if self._cls_tail(G):
             G.alloc_cls()
@@ -668,6 +702,17 @@ class VitRunner:
         for sg in G.segs:
             # (the final norm touches the CLS rows only, one per image: the per-image factors are its row factors)
             im = slice(sg.img0, sg.img0 + sg.n_img)
+            if G.pool == "avg":
+                # fc_norm backward over the pooled rows -> dpool, spread over the patch rows of the residual gradient and of the
+                # last block's MLP-half dY (the CLS rows: zeros).  The last mlp.fc2.bias gradient is the column sum of that dY's
+                # f32 source over every token row, sum_img gb_scale[img] * dpool[img]: the third sum of this launch
+                gs = None if rs is None else G.drop_img[self.depth - 1, 1, im]
+                ops.layernorm_bwd(dfeat[im], G.pooled[im], sg.fstats[0], sg.fstats[1], W.f("fc_norm.weight"), G.dpool[im], None, ring[0],
+                                  sg.n_img, D, g_init=True, gb_scale=gs)
+                ops.ln_finalize(ring[0], L.LN_PARTIAL_BLOCKS, D, W.g("fc_norm.weight"), W.g("fc_norm.bias"),
+                                None if dp else W.g(f"blocks.{self.depth - 1}.mlp.fc2.bias"))
+                ops.token_mean_bwd(G.dpool[im], sg.rows(G.g), sg.rows(gb_first), sg.n_img, sg.N, D, gb_scale=gs)
+                continue
             if cls_tail:
                 ops.layernorm_bwd(dfeat[im], G.c_xc[im], sg.fstats[0], sg.fstats[1], W.f("norm.weight"), G.c_g[im], G.c_gb[im], ring[0],
                                   sg.n_img, D, g_init=True, gb_scale=None if rs is None else G.drop_img[self.depth - 1, 1, im])
@@ -1224,8 +1269,11 @@ class SupervisedEngine(TrainEngine):
                  eps=1e-8, smoothing=0.1, clip_grad: float = 0.0, mean=MEAN_RON, std=STD_RON, device="cuda:0", reducer=None,
                  opt: str = "adamw", momentum: float = 0.9, train_backbone: bool = True, model_ema_decay: Optional[float] = None,
                  precision: str = "bf16", clip_mode: str = "norm", loss: str = "lsce", bce_target_thresh: Optional[float] = None,
-                 layer_decay: Optional[float] = None):
-        """``precision``: "bf16" (the training path: bf16 GEMM / attention operands, f32 accumulation and residual stream) or
+                 layer_decay: Optional[float] = None, global_pool: Optional[str] = "token"):
+        """``global_pool`` (train.py:122 --gp -> create_model, train.py:490): "token" (None: the same) = the CLS token through the
+        final norm; "avg" = timm's mean-pooled model: no final norm, the mean of the patch tokens through ``fc_norm``, so
+        ``feats`` is the pooled, normalised feature and the last block runs on every token (gv_token_mean_fwd / _bwd).
+        ``precision``: "bf16" (the training path: bf16 GEMM / attention operands, f32 accumulation and residual stream) or
         "fp32" (the reference's default arithmetic: every operand f32, csrc/f32path.hip -- the mode the 1e-4 parity gates
         of SURVEY 8d are stated for; an order of magnitude slower, kept for verification).
         ``loss`` (train.py:832-842): "lsce" LabelSmoothingCrossEntropy (gv_softmax_lsce, the default path), "soft_ce" timm
@@ -1235,6 +1283,7 @@ class SupervisedEngine(TrainEngine):
         rate for every layer, the two-launch optimizer pass.  A number (1.0 included) gives layer ``id`` the rate
         ``lr * layer_decay ** (depth + 2 - id)`` and makes ``optimizer_step`` ONE gv_adamw_ema_ranges launch over a range table
         (adamw / adam / sgd) or hands gv_lamb a per-tensor rate; ``layer_scales`` / ``mean_lr`` show the result."""
+        self.pool = resolve_pool(global_pool)
         if loss not in ("lsce", "soft_ce", "bce"):
             raise ValueError(f"loss {loss!r}: 'lsce', 'soft_ce' or 'bce' (train.py:832-842)")
         if bce_target_thresh is not None and loss != "bce":
@@ -1254,11 +1303,11 @@ class SupervisedEngine(TrainEngine):
         # --model-ema (train.py:615-622, ModelEmaV2): the EMA copy lives in the arena's teacher slot and is
         # updated by the same fused optimizer pass (train.py:1080-1081)
         self.ema_decay = model_ema_decay
-        self.arena = Arena(vit_param_specs(arch, img_size, num_classes), dev, teacher=model_ema_decay is not None)
+        self.arena = Arena(vit_param_specs(arch, img_size, num_classes, self.pool), dev, teacher=model_ema_decay is not None)
         self.W = Weights(self.arena, "", fp32=fp32)
         self.Wema = Weights(self.arena, "", teacher=True, fp32=fp32) if model_ema_decay is not None else None
         self.vit = VitRunner(arch, img_size, dev, fp32=fp32)
-        self.grp = VitGroup(arch, [(batch, img_size)], img_size, dev, save=True, act=act)
+        self.grp = VitGroup(arch, [(batch, img_size)], img_size, dev, save=True, act=act, pool=self.pool)
         e = lambda shape, dt: _empty(shape, dt, dev)
         self.feats, self.dfeats = e((batch, D), act), e((batch, D), act)
         self.logits, self.dlogits, self.prob = e((batch, num_classes), f32), e((batch, num_classes), f32), e((batch, num_classes), f32)
@@ -1443,8 +1492,11 @@ class FeatureExtractor:
     extractor then evaluates those live parameters instead of owning a copy (validation between epochs)."""
 
     def __init__(self, arch="vit_small", img_size=256, batch=256, num_classes=0, mean=MEAN_RON, std=STD_RON, device="cuda:0",
-                 weights: Optional[Weights] = None, precision: str = "bf16"):
-        """``precision``: as for the engines; with ``weights`` it follows the owning engine's mode."""
+                 weights: Optional[Weights] = None, precision: str = "bf16", global_pool: Optional[str] = "token"):
+        """``precision``: as for the engines; with ``weights`` it follows the owning engine's mode.  ``global_pool``: as
+        SupervisedEngine's -- "avg" returns the mean of the patch tokens through ``fc_norm`` (the weights must be an avg
+        model's); the attention maps do not change with it, ``intermediate_layers`` is refused (no final norm)."""
+        self.pool = resolve_pool(global_pool)
         fp32, act = operand_mode(precision)
         if weights is not None:
             fp32, act = weights.fp32, (f32 if weights.fp32 else bf16)
@@ -1459,13 +1511,16 @@ class FeatureExtractor:
         self.D = ARCHS[arch]["embed_dim"]
         self.mean, self.std = tuple(mean), tuple(std)
         if weights is None:
-            self.arena = Arena(vit_param_specs(arch, img_size, num_classes), dev, teacher=False)
+            self.arena = Arena(vit_param_specs(arch, img_size, num_classes, self.pool), dev, teacher=False)
             self.W = Weights(self.arena, "", fp32=fp32)
         else:
             self.arena, self.W = weights.a, weights
         self.vit = VitRunner(arch, img_size, dev, fp32=fp32)
         self.vit.side = None                       # a forward-only pass has nothing to put on a side stream
-        self.grp = VitGroup(arch, [(batch, img_size)], img_size, dev, save=False, act=act)
+        has_fc_norm = self.W.prefix + "fc_norm.weight" in self.arena.specs
+        if has_fc_norm != (self.pool == "avg"):
+            raise ValueError(f"global_pool={self.pool!r} over the weights of a {'mean-pooled' if has_fc_norm else 'CLS-token'} model")
+        self.grp = VitGroup(arch, [(batch, img_size)], img_size, dev, save=False, act=act, pool=self.pool)
         self.feats = _empty((batch, self.D), act, dev)
         self.logits = _empty((batch, num_classes), f32, dev) if num_classes else None
         self._pad = self._pad_f32 = None
@@ -1569,7 +1624,10 @@ class FeatureExtractor:
 
     def intermediate_layers(self, tiles_u8: torch.Tensor, n: int = 1) -> List[torch.Tensor]:
         """The reference's get_intermediate_layers (vit.pyc@L264-272) over any number of tiles: ``norm(x)`` over every token after
-        each of the last ``n`` blocks, in block order -- a list of n f32 [n_tiles, N, D]."""
+        each of the last ``n`` blocks, in block order -- a list of n f32 [n_tiles, N, D].  Not for a global_pool='avg' model."""
+        if self.pool == "avg":
+            raise ValueError("intermediate_layers: the reference applies the final norm to every token there, and a "
+                             "global_pool='avg' model has none (its fc_norm normalises the pooled vector)")
         self._check_size(tiles_u8)
         if not 1 <= n <= self.vit.depth:
             raise ValueError(f"intermediate_layers: n = {n}, need 1 <= n <= depth = {self.vit.depth}")

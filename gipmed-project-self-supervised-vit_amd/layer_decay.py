@@ -7,6 +7,9 @@ source -- parity is unpinned beyond this restatement:
 * ``VisionTransformer.group_matcher(coarse=False)`` = ``GROUP_MATCHER``.  ``group_parameters`` sorts the match keys -- stem
   ``(0,)``, ``blocks.i`` ``(1, i)``, ``norm`` ``(1, 99999)``, unmatched names (the classifier) last -- and numbers them, so for
   depth L: ``cls_token``, ``pos_embed``, ``patch_embed.*`` -> 0, ``blocks.i.*`` -> i + 1, ``norm.*`` -> L + 1, ``head.*`` -> L + 2.
+  ``fc_norm.*`` of a ``--gp avg`` model matches none of the patterns (``^norm`` does not match it): it falls into the unmatched
+  group with ``head.*``, id L + 2, scale 1.  Such a model has no ``norm.*``, so id L + 1 holds no parameter and ``mean_lr``
+  averages one group fewer.
 * ``param_groups_layer_decay``: ``num_layers = L + 3``, ``scale(id) = decay ** (num_layers - 1 - id)``; one parameter group per
   (layer, decay | no-decay) that holds a trainable parameter, ``lr_scale`` = the layer's scale; timm's schedulers set every
   group's rate to ``scheduled_lr * lr_scale`` at every update, warm-up included.  The decay / no-decay split inside a layer is

@@ -13,7 +13,7 @@ from typing import Dict, Optional
 
 import torch
 
-from .engine import ARCHS, dino_head_specs, vit_param_specs
+from .engine import ARCHS, dino_head_specs, resolve_pool, vit_param_specs
 
 # timm names used by the reference -> (arch, default img size after the documented cfg patch)
 MODEL_REGISTRY = {
@@ -37,13 +37,14 @@ def _trunc_normal_(t: torch.Tensor, std: float, gen: torch.Generator):
     return t
 
 
-def init_vit_state(arch: str, img_size: int, num_classes: int = 0, seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+def init_vit_state(arch: str, img_size: int, num_classes: int = 0, seed: int = 0, global_pool: str = "token") -> "OrderedDict[str, torch.Tensor]":
     """vit.pyc@L173-211: trunc_normal(.02) on pos/cls/Linear weights, zero biases, LayerNorm (1, 0);
-    the patch-embedding conv keeps torch's default (kaiming-uniform, bound 1/sqrt(fan_in))."""
+    the patch-embedding conv keeps torch's default (kaiming-uniform, bound 1/sqrt(fan_in)).  ``global_pool`` "avg": ``fc_norm``
+    (1, 0) in the place of ``norm``; every other tensor draws the same values."""
     gen = torch.Generator().manual_seed(seed)
     out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
     bound = 1.0 / math.sqrt(3 * 16 * 16)
-    for name, shape in vit_param_specs(arch, img_size, num_classes).items():
+    for name, shape in vit_param_specs(arch, img_size, num_classes, global_pool).items():
         t = torch.empty(shape)
         if name.startswith("patch_embed"):
             t.uniform_(-bound, bound, generator=gen)
@@ -88,10 +89,13 @@ def resize_pos_embed(pos: torch.Tensor, new_tokens: int) -> torch.Tensor:
     return torch.cat([cls, grid.permute(0, 2, 3, 1).reshape(1, s1 * s1, -1)], dim=1)
 
 
-def load_encoder_checkpoint(path: str, arch: str, img_size: int, num_classes: int = 0) -> Dict[str, torch.Tensor]:
+def load_encoder_checkpoint(path: str, arch: str, img_size: int, num_classes: int = 0, global_pool: str = "token") -> Dict[str, torch.Tensor]:
     """Read an encoder ``state_dict`` from a timm-style ``*.pth.tar`` / DINO checkpoint with a
     loader that executes nothing from the file, strip 'module.' / 'backbone.' prefixes, resize
-    the pos-embed if the grid differs and fill a missing / mismatched classifier head."""
+    the pos-embed if the grid differs and fill a missing / mismatched classifier head.
+    ``global_pool`` "avg": ``fc_norm.*`` is loaded when the file has it; from a token-style file (a DINO or supervised CLS
+    checkpoint -- the fine-tuning case) ``norm.*`` is dropped and ``fc_norm`` starts at (1, 0), with one printed notice.  A
+    "token" model given a mean-pooled file (``fc_norm.*`` and no ``norm.*``) raises KeyError: there is no final norm to load."""
     ck = torch.load(path, map_location="cpu", weights_only=True)
     for key in ("state_dict", "model", "teacher", "student"):
         if isinstance(ck, dict) and key in ck and isinstance(ck[key], dict):
@@ -103,8 +107,14 @@ def load_encoder_checkpoint(path: str, arch: str, img_size: int, num_classes: in
             if k.startswith(pre):
                 k = k[len(pre):]
         sd[k] = v
-    want = vit_param_specs(arch, img_size, num_classes)
-    fresh = init_vit_state(arch, img_size, num_classes)
+    pool = resolve_pool(global_pool)
+    want = vit_param_specs(arch, img_size, num_classes, pool)
+    fresh = init_vit_state(arch, img_size, num_classes, global_pool=pool)
+    if pool == "token" and "fc_norm.weight" in sd and "norm.weight" not in sd:
+        raise KeyError(f"norm.weight: {path} holds a global_pool='avg' model (fc_norm.*, no final norm); load it with global_pool='avg'")
+    if pool == "avg" and "fc_norm.weight" not in sd and "norm.weight" in sd:
+        print(f"load_encoder_checkpoint: {path} is a CLS-token checkpoint -- its final norm.* is dropped and fc_norm starts at (1, 0) "
+              "(global_pool='avg')")
     out = OrderedDict()
     for name, shape in want.items():
         t = sd.get(name)
@@ -223,7 +233,8 @@ class VitModel:
         return x
 
     def forward_features(self, tiles_u8: torch.Tensor) -> torch.Tensor:
-        """As ``__call__``, returning the CLS features [batch, embed_dim] (the engine's buffer)."""
+        """As ``__call__``, returning the CLS features [batch, embed_dim] (the engine's buffer); the pooled, fc_norm-ed features of
+        a global_pool='avg' model."""
         return self.engine.forward(self._images(tiles_u8))[1]
 
     def _extractor(self):
@@ -232,7 +243,7 @@ class VitModel:
         if self._fx is None:
             from .engine import FeatureExtractor
             e = self.engine
-            self._fx = FeatureExtractor(self.arch, e.img, e.B, 0, e.mean, e.std, e.dev, weights=e.W)
+            self._fx = FeatureExtractor(self.arch, e.img, e.B, 0, e.mean, e.std, e.dev, weights=e.W, global_pool=e.pool)
         return self._fx
 
     def get_last_selfattention(self, x: torch.Tensor) -> torch.Tensor:
@@ -242,7 +253,8 @@ class VitModel:
 
     def get_intermediate_layers(self, x: torch.Tensor, n: int = 1):
         """vit.pyc@L264-272: ``norm(x)`` over every token after each of the last ``n`` blocks -> a list of n f32 [batch, N,
-        embed_dim], in block order.  Evaluation semantics as ``get_last_selfattention``."""
+        embed_dim], in block order.  Evaluation semantics as ``get_last_selfattention``.  ValueError for a global_pool='avg' model
+        (it has no final norm)."""
         return self._extractor().intermediate_layers(self._images(x), n)
 
     def __call__(self, tiles_u8: torch.Tensor) -> torch.Tensor:
@@ -255,11 +267,13 @@ class VitModel:
 
 def create_model(model_name: str, pretrained: bool = False, in_chans: int = 3, num_classes: Optional[int] = None,
                  drop_rate: float = 0.0, drop_path_rate: Optional[float] = None, checkpoint_path: str = "",
-                 img_size: int = 256, batch: int = 8, device: str = "cuda:0", seed: int = 0, **engine_kwargs) -> VitModel:
+                 img_size: int = 256, batch: int = 8, device: str = "cuda:0", seed: int = 0, global_pool: Optional[str] = None,
+                 **engine_kwargs) -> VitModel:
     """Counterpart of ``timm.create_model`` as the reference calls it (train.py:482-495) for the ViT names it documents.
     Unsupported requests fail here instead of being ignored: other channel counts, dropout (not built; stochastic depth is),
     ``pretrained`` without a checkpoint file (there is no network).  ``num_classes=None`` keeps the checkpoint-less default
-    of the reference's runs (2 classes, train_instruct.txt:16-34)."""
+    of the reference's runs (2 classes, train_instruct.txt:16-34).  ``global_pool`` (train.py:490 ``global_pool=args.gp``): None
+    or "token" = the CLS token, "avg" = mean of the patch tokens + fc_norm; "" and anything else: ValueError."""
     from .engine import SupervisedEngine
     arch = resolve_arch(model_name)
     if in_chans != 3:
@@ -269,8 +283,10 @@ def create_model(model_name: str, pretrained: bool = False, in_chans: int = 3, n
     if pretrained and not checkpoint_path:
         raise ValueError("create_model: pretrained=True needs checkpoint_path (no network on this system)")
     C = 2 if num_classes is None else int(num_classes)
-    eng = SupervisedEngine(arch=arch, img_size=img_size, num_classes=C, batch=batch, device=device, **engine_kwargs)
-    state = load_encoder_checkpoint(checkpoint_path, arch, img_size, C) if checkpoint_path else init_vit_state(arch, img_size, C, seed=seed)
+    pool = resolve_pool(global_pool)
+    eng = SupervisedEngine(arch=arch, img_size=img_size, num_classes=C, batch=batch, device=device, global_pool=pool, **engine_kwargs)
+    state = (load_encoder_checkpoint(checkpoint_path, arch, img_size, C, pool) if checkpoint_path
+             else init_vit_state(arch, img_size, C, seed=seed, global_pool=pool))
     eng.load_state(state)
     model = VitModel(eng, arch)
     # stochastic depth: the training loop hands the next step's draws to the engine -- engine.set_drop_path(model.drop_path.sample())

@@ -524,6 +524,34 @@ def gather_cls(x, y, n_img: int, N: int, D: int):
     L.call("gv_gather_cls", L.gv_gather_cls_args(x.data_ptr(), y.data_ptr(), n_img, N, D), _stream())
 
 
+def token_mean_fwd(x, pooled, n_img: int, N: int, D: int):
+    """pooled[i] = mean of rows 1 .. N-1 of image i of x f32 [n_img * N, D] (the CLS row excluded; global_pool='avg'); see
+    gv_token_mean_fwd."""
+    _chk(x, f32, "x"); _chk(pooled, f32, "pooled")
+    if x.numel() < n_img * N * D or pooled.numel() < n_img * D or not (x.is_contiguous() and pooled.is_contiguous()):
+        raise ValueError(f"token_mean_fwd: need contiguous x [{n_img * N}, {D}] and pooled [{n_img}, {D}], got {tuple(x.shape)} and {tuple(pooled.shape)}")
+    L.call("gv_token_mean_fwd", L.gv_token_mean_fwd_args(x.data_ptr(), pooled.data_ptr(), n_img, N, D), _stream())
+    return pooled
+
+
+def token_mean_bwd(dpool, g, gb, n_img: int, N: int, D: int, gb_scale=None):
+    """The backward of ``token_mean_fwd`` into the residual gradient: rows t >= 1 of image i get g = dpool[i] / (N - 1) (f32) and
+    gb = g * gb_scale[i] in gb's format (the build's 16-bit one, or f32 in the fp32 operand mode); row 0 is zeros in both; see
+    gv_token_mean_bwd."""
+    _chk(dpool, f32, "dpool"); _chk(g, f32, "g")
+    if gb_scale is not None:
+        _chk(gb_scale, f32, "gb_scale")
+        if gb_scale.numel() < n_img or not gb_scale.is_contiguous():
+            raise ValueError(f"token_mean_bwd: gb_scale holds one contiguous factor per image ({n_img}), got {tuple(gb_scale.shape)}")
+    sfx = _sfx(gb)
+    if not gb.is_cuda:
+        raise TypeError(f"gb: expected a device tensor, got one on {gb.device}")
+    if dpool.numel() < n_img * D or g.numel() < n_img * N * D or gb.numel() < n_img * N * D or not (dpool.is_contiguous() and g.is_contiguous() and gb.is_contiguous()):
+        raise ValueError(f"token_mean_bwd: need contiguous dpool [{n_img}, {D}] and g / gb [{n_img * N}, {D}], got {tuple(dpool.shape)}, "
+                         f"{tuple(g.shape)}, {tuple(gb.shape)}")
+    L.call("gv_token_mean_bwd" + sfx, L.gv_token_mean_bwd_args(dpool.data_ptr(), g.data_ptr(), gb.data_ptr(), _p(gb_scale), n_img, N, D), _stream())
+
+
 def store_f32(dst, vals):
     """dst[i] = vals[i] (n <= 16) by a stream-ordered kernel whose arguments carry the values."""
     a = L.gv_store_f32_args()

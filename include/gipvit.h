@@ -629,6 +629,24 @@ int gv_softmax_mix_loss(const gv_softmax_mix_loss_args* a, void* stream);
 typedef struct { const float* x; void* y; int32_t n_img, N, D; } gv_gather_cls_args;
 int gv_gather_cls(const gv_gather_cls_args* a, void* stream);
 
+/* ---- mean pooling of the patch tokens (`--gp avg`, reference train.py:490 -> timm global_pool='avg': x[:, 1:].mean(dim=1) in
+ * front of fc_norm; the CLS row is excluded).  x f32 [n_img * N, D] compact (the residual stream), pooled f32 [n_img, D]:
+ *   fwd: pooled[i, :] = sum over t = 1 .. N-1 of x[i*N + t, :], divided by N - 1.  f32 accumulation, no atomics; the summation
+ *        order is fixed by (N, D) alone, so the result is bitwise reproducible.
+ *   bwd: for every row t >= 1 of image i: g[i*N + t, :] = dpool[i, :] / (N - 1) (f32, the residual-stream gradient) and
+ *        gb[i*N + t, :] = bf16(g * gb_scale[i]); row t = 0 (CLS) is written as zeros in both.  Every row of g and gb is written.
+ * N < 2 or D % 4 != 0: GV_E_SHAPE, a null pointer (gb_scale excepted): GV_E_NULL, both before any launch.                   */
+typedef struct { const float* x; float* pooled; int32_t n_img, N, D; } gv_token_mean_fwd_args;
+int gv_token_mean_fwd(const gv_token_mean_fwd_args* a, void* stream);
+typedef struct {
+    const float* dpool;    /* f32 [n_img, D]                                                                       */
+    float* g;              /* f32 [n_img * N, D] out                                                               */
+    void* gb;              /* bf16 [n_img * N, D] out (f32 in gv_token_mean_bwd_f32)                               */
+    const float* gb_scale; /* optional [n_img]: the stochastic-depth factor of the branch gb enters; NULL = 1      */
+    int32_t n_img, N, D;
+} gv_token_mean_bwd_args;
+int gv_token_mean_bwd(const gv_token_mean_bwd_args* a, void* stream);
+
 /* dst[i] = vals[i] for i < n <= 16: per-step schedule values (gv_adamw_ema_args.hyper)
  * delivered as KERNEL ARGUMENTS of a stream-ordered launch rather than by a memcpy.     */
 typedef struct { float* dst; float vals[16]; int32_t n; } gv_store_f32_args;
@@ -797,6 +815,7 @@ int gv_patchify_nchw_mix_f32(const gv_patchify_nchw_mix_args* a, void* stream);
 int gv_patchify_erase_f32(const gv_patchify_erase_args* a, void* stream);
 int gv_patchify_nchw_erase_f32(const gv_patchify_nchw_erase_args* a, void* stream);
 int gv_tokens_bwd_f32(const gv_tokens_bwd_args* a, void* stream);
+int gv_token_mean_bwd_f32(const gv_token_mean_bwd_args* a, void* stream);      /* gb f32 */
 /* DINO head: zn / dz (l2norm), the weight-normalised last-layer matrix, and the student-logit gradient as f32 */
 int gv_l2norm_fwd_f32(const gv_l2norm_fwd_args* a, void* stream);
 int gv_l2norm_bwd_f32(const gv_l2norm_bwd_args* a, void* stream);

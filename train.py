@@ -162,6 +162,15 @@ def check_supported(args, log=_logger.warning):
     if args.dino and args.opt.lower() != "adamw":
         raise SystemExit(f"--dino --opt {args.opt}: the DINO step is AdamW with the recipe's weight-decay schedule (paper; the frozen-last-layer and "
                          "teacher-EMA ranges are fused into that pass); pass --opt adamw")
+    if args.gp is not None:
+        # train.py:122 -> create_model(global_pool=args.gp), train.py:490: the encoder's pooling
+        if args.gp not in ("token", "avg"):
+            raise SystemExit(f"--gp {args.gp!r}: 'token' (the CLS token, the default) or 'avg' (mean of the patch tokens + fc_norm); "
+                             + ("'' would hand every token to the head, which the reference's loss cannot take"
+                                if args.gp == "" else "timm's ViT has no other pooling"))
+        if args.gp == "avg" and args.dino:
+            raise SystemExit("--gp avg with --dino: the DINO step reads the CLS token; mean pooling is the supervised model's (fine-tune "
+                             "a DINO checkpoint with --gp avg --initial-checkpoint)")
     if args.layer_decay is not None:
         # train.py:175 -> timm param_groups_layer_decay: every layer below the classifier at layer_decay times the rate of the one above
         if not args.layer_decay > 0:
@@ -517,9 +526,9 @@ def main(argv=None, transform=None):
                                opt=opt, momentum=args.momentum,
                                train_backbone=not args.no_grad, model_ema_decay=ema_decay, precision=args.precision, clip_mode=args.clip_mode,
                                loss=loss_kind(args), bce_target_thresh=args.bce_target_thresh if loss_kind(args) == "bce" else None,
-                               layer_decay=args.layer_decay)
-        st = (M.load_encoder_checkpoint(args.initial_checkpoint, arch, img, nc) if args.initial_checkpoint
-              else M.init_vit_state(arch, img, nc, seed=args.seed))
+                               layer_decay=args.layer_decay, global_pool=args.gp)
+        st = (M.load_encoder_checkpoint(args.initial_checkpoint, arch, img, nc, eng.pool) if args.initial_checkpoint
+              else M.init_vit_state(arch, img, nc, seed=args.seed, global_pool=eng.pool))
         eng.load_state(st)
     start_epoch = args.start_epoch or 0
     if args.resume:
@@ -546,7 +555,7 @@ def main(argv=None, transform=None):
         source.epoch = start_epoch                 # the synthetic source seeds every epoch: a resumed run sees epoch k's tiles
     if primary:
         n_params = sum(int(torch.tensor(s).prod()) for s in eng.arena.specs.values())
-        _logger.info(f"Model {args.model} ({arch}) created, param count:{n_params}")
+        _logger.info(f"Model {args.model} ({arch}) created, param count:{n_params}" + ("" if args.dino else f", global pool: {eng.pool}"))
 
     # ---- forward-only runners for validation / feature extraction: they evaluate the engine's LIVE weights
     eval_B = min(256, max(B, 32))
@@ -557,9 +566,9 @@ def main(argv=None, transform=None):
             if tile != img:
                 raise SystemExit(f"--extract_features with --dino: tile size {tile} must equal the teacher's image size {img}")
         else:
-            runner = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.W)
+            runner = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.W, global_pool=eng.pool)
             if ema_decay is not None:
-                runner_ema = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.Wema)
+                runner_ema = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.Wema, global_pool=eng.pool)
 
     monitor = None
     knn_names = []
