@@ -23,14 +23,15 @@
 // segments for every load and store, the arithmetic of layernorm.hip's row kernels, wave sums by DPP); the global rows
 // a pass needs are all requested before the pass's image barrier.
 #include "gemm_core.h"
+#include "linear_plan.h"
 #include "timing.h"
 #include <type_traits>
 
 namespace {
 
 using namespace gvgemm;
+using namespace gvplan;             // PN = 384 output columns (the model width this kernel is built for), MODE_* / EP_*, the FM choice
 
-constexpr int PN = 384;              // output columns = the model width this kernel is built for (ViT-S)
 constexpr int IMG_STRIDE = PN + 4;          // f32 image row stride (+4: conflict-free transposed writes)
 
 // Geometry: NW = 8 waves, each 3 column fragments x FM row fragments, BK = 64, ONE workgroup per CU (ring 2 x (A + 48 KB)).
@@ -91,12 +92,7 @@ struct PanelP {
 };
 
 
-enum { MODE_FWD = 0, MODE_BWD = 1, MODE_WIDE = 2 };
-// MODE_WIDE epilogues (the GV_EPI_* combinations of the hot path's wide products)
-// EP_BIAS_RESID: f32 output = (A W^T + bias) * row_scale + resid -- x + proj(a) / x + fc2(h) of the widths that have no fused
-// LayerNorm kernel (ViT-B: N = 768)
-enum { EP_NONE = 0, EP_BIAS = 1, EP_BIAS_GELU = 2, EP_BIAS_GELU_SAVE = 3, EP_DGELU = 4, EP_BIAS_RESID = 5 };
-constexpr int EP_MLP = 1;           // (MODE_FWD only: the fused-MLP variant of the forward kernel)
+// MODE_* and the MODE_WIDE epilogues EP_*: linear_plan.h
 
 // PP = 1: the k-loop of gemm_dw8.h (ping-pong halves, three phases per 64-deep K-tile, counted LDS-DMA stream) instead of the
 // one-stage-ahead loop: waves (wm, wn) = (wave >> 2, wave & 3); the wm = 0 half owns the first FMH = ceil(FM / 2) row fragments,
@@ -746,32 +742,6 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
     }
 }
 
-// rows per workgroup for M rows: the smallest supported FM that covers M in as few full rounds of 256 workgroups as possible
-constexpr int FM_SET8[] = {4, 7, 9, 11, 12};
-int cu_budget() { return gv_cu_budget(); }       // 256, or 256 - C under a data-parallel run that leaves C CUs to RCCL (gv_common.h)
-int pick_fm(int M) {
-    const int m16 = (M + 15) / 16;
-    const int rounds = (m16 + cu_budget() * 12 - 1) / (cu_budget() * 12);
-    const int need = (m16 + cu_budget() * rounds - 1) / (cu_budget() * rounds);
-    for (int fm : FM_SET8) if (fm >= need) return fm;
-    return 12;
-}
-
-// MODE_WIDE launch geometry (see the kernel's id mapping): groups of ncb sibling workgroups, ceil(groups / 8) per XCD
-int wide_grid(int M, int BM, int ncb) {
-    const int P = (M + BM - 1) / BM, groups = (P + ncb - 1) / ncb;
-    return 8 * ncb * ((groups + 7) / 8);
-}
-// ... and the smallest supported FM whose WORKING workgroups (ncb per group of panels; the grid's padding to 8 ncb exits at once)
-// fit one round of the CU budget; 12 (several rounds) for larger M
-int pick_fm_wide(int M, int ncb) {
-    for (int fm : FM_SET8) {
-        const int P = (M + 16 * fm - 1) / (16 * fm), groups = (P + ncb - 1) / ncb;
-        if (groups * ncb <= cu_budget() && wide_grid(M, 16 * fm, ncb) <= 256) return fm;
-    }
-    return 12;
-}
-
 template <int FM, int NW, int BK, bool TB, int MODE, int EP = 0, int PP = 0>
 int launch_panel(const PanelP& p, hipStream_t s, const char* name) {
     auto kern = panel_kernel<FM, NW, BK, TB, MODE, EP, PP>;
@@ -782,9 +752,7 @@ int launch_panel(const PanelP& p, hipStream_t s, const char* name) {
     constexpr int LDS_BYTES = MLP ? LDS_MLP : (MODE == MODE_WIDE ? C::LDS_WIDE : C::LDS);
     static GvLdsOptIn opt_in;
     if (int rc = gv_lds_opt_in(opt_in, (const void*)kern, LDS_BYTES, name)) return rc;
-    struct Name { char s[96]; Name() { snprintf(s, sizeof(s), "panel_kernel<%d, %d, %d, %s, %d, %d, %d>", FM, NW, BK, TB ? "true" : "false", MODE, EP, PP); } };
-    static const Name kn;                                           // as rocprofv3 prints it (initialised once, thread-safe)
-    const char* kname = kn.s;
+    static_assert(NW == PANEL_NW && BK == PANEL_BK, "linear_plan.h: panel geometry");
     const int grid = MODE == MODE_WIDE ? wide_grid(p.M, C::BM, p.ncb) : (p.M + C::BM - 1) / C::BM;
     // algorithmic bytes: forward  A row + f32 residual in + f32 row out + bf16 normalised row out + stats;
     // backward  dY row + f32 x row + f32 g in / out + bf16 g out; + the weight once
@@ -794,18 +762,23 @@ int launch_panel(const PanelP& p, hipStream_t s, const char* name) {
                              : MODE == MODE_FWD ? 2.0 * p.K + PN * 4 * 2 + PN * 2 + 8 : 2.0 * p.K + PN * 4 * 3 + PN * 2 + 8;
     const double flops = MLP ? 4.0 * p.M * p.hidden * p.K : 2.0 * p.M * nout * p.K;
     const double bytes = p.M * row_bytes + (MLP ? 4.0 * p.hidden * p.K : 2.0 * nout * p.K);
-    const int th = gvtime::enabled() ? gvtime::begin(kname, flops, bytes, s) : -1;
+    int th = -1;
+    if (gvtime::enabled()) {
+        char kname[96];
+        panel_kernel_name(kname, sizeof(kname), FM, TB, MODE, EP, PP != 0);
+        th = gvtime::begin(kname, flops, bytes, s);
+    }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), LDS_BYTES, s, p);
     gvtime::end(th, s);
     GV_LAUNCH_CHECK(name);
     return GV_OK;
 }
 
+// the instantiation for fm rows of 16 per workgroup (one of FM_SET8), with the ping-pong k-loop where the depth allows
 template <bool TB, int MODE, int EP = 0>
-int dispatch_fm(const PanelP& p, hipStream_t s, const char* name) {
-    // the ping-pong k-loop walks K-tiles in pairs (static ring stage): K % 128 == 0; other depths keep the one-stage-ahead loop
-    if (p.K % 128 == 0) {
-        switch (MODE == MODE_WIDE ? pick_fm_wide(p.M, p.ncb) : pick_fm(p.M)) {
+int dispatch_fm(const PanelP& p, int fm, hipStream_t s, const char* name) {
+    if (panel_pingpong(p.K)) {
+        switch (fm) {
             case 4: return launch_panel<4, 8, 64, TB, MODE, EP, 1>(p, s, name);
             case 7: return launch_panel<7, 8, 64, TB, MODE, EP, 1>(p, s, name);
             case 9: return launch_panel<9, 8, 64, TB, MODE, EP, 1>(p, s, name);
@@ -813,9 +786,9 @@ int dispatch_fm(const PanelP& p, hipStream_t s, const char* name) {
             default: return launch_panel<12, 8, 64, TB, MODE, EP, 1>(p, s, name);
         }
     }
-    if constexpr (MODE == MODE_WIDE) return -1;                     // (gv_panel_wide admits K % 128 == 0 only)
+    if constexpr (MODE == MODE_WIDE) GV_FAIL(GV_E_UNSUPPORTED, "%s: K %% 128 != 0 has no wide kernel", name);      // (plan_wide admits K % 128 == 0 only)
     else
-    switch (pick_fm(p.M)) {
+    switch (fm) {
         case 4: return launch_panel<4, 8, 64, TB, MODE, EP>(p, s, name);
         case 7: return launch_panel<7, 8, 64, TB, MODE, EP>(p, s, name);
         case 9: return launch_panel<9, 8, 64, TB, MODE, EP>(p, s, name);
@@ -826,48 +799,29 @@ int dispatch_fm(const PanelP& p, hipStream_t s, const char* name) {
 
 }  // namespace
 
-// gv_linear's wide products (timing.h): C[M, N] bf16 = epilogue(A W^T) with N a multiple of 384, K a multiple of 128 and one of
-// the hot path's epilogues, on the full-row kernel -- row panels sized for ONE round of workgroups, 768-B row segments out.
-// Returns -1 when the call is not one of these (the caller then runs the 128x128-tile kernel).
-int gv_panel_wide(const gv_linear_args* a, hipStream_t s) {
-    if (a->trans_a || a->N % PN != 0 || a->K % 128 != 0 || a->M < 2048 || a->ldc % 2 != 0) return -1;
-    if (a->alpha != 0.f && a->alpha != 1.f) return -1;
-    const bool plan = s == (hipStream_t)(intptr_t)-1;       // gv_workspace_bytes: "would this call run here?" (these kernels take no scratch)
-    if (a->c_is_f32) {      // x + Linear(a) with an f32 residual stream, where no fused LayerNorm kernel exists for the width
-        if (a->trans_b || a->epilogue != (GV_EPI_BIAS | GV_EPI_RESID) || a->ldr % 2 != 0) return -1;
-        if ((const void*)a->resid == (const void*)a->C) return -1;      // in place: the rows the last two panels share would be updated twice
-        if (plan) return GV_OK;
-        PanelP q{};
-        q.A = (const bf16*)a->A; q.W = (const bf16*)a->B; q.M = a->M; q.K = a->K; q.lda = a->lda; q.ldw = a->ldb;
-        q.bias = a->bias; q.out = (float*)a->C; q.ldo = a->ldc; q.resid = a->resid; q.ldr = a->ldr; q.row_scale = a->row_scale;
-        q.ncb = a->N / PN; q.n_total = a->N;
-        return dispatch_fm<false, MODE_WIDE, EP_BIAS_RESID>(q, s, "gv_linear(wide)");
-    }
+// gv_linear's wide products (gemm.hip hands over the calls linear_plan.h's plan_wide admits): C[M, N] = epilogue(A W^T) on the
+// full-row kernel, the epilogue and the rows per workgroup as planned
+int gv_panel_wide(const gv_linear_args* a, const LinearPlan& pl, hipStream_t s) {
     PanelP p{};
     p.A = (const bf16*)a->A; p.W = (const bf16*)a->B; p.M = a->M; p.K = a->K; p.lda = a->lda; p.ldw = a->ldb;
-    p.bias = a->bias; p.outb = (bf16*)a->C; p.ldob = a->ldc; p.aux_in = (const bf16*)a->aux_in; p.aux_out = (bf16*)a->aux_out; p.ld_aux = a->ld_aux;
-    p.ncb = a->N / PN; p.n_total = a->N;
-    if (a->ld_aux % 2 != 0) return -1;
-    const int e = a->epilogue;
-    if (plan) {
-        const bool fwd = !a->trans_b && (e == GV_EPI_BIAS || e == (GV_EPI_BIAS | GV_EPI_GELU) || e == (GV_EPI_BIAS | GV_EPI_GELU | GV_EPI_SAVE_PRE));
-        return (fwd || (a->trans_b && (e == 0 || e == GV_EPI_DGELU))) ? GV_OK : -1;
+    p.bias = a->bias; p.ncb = a->N / PN; p.n_total = a->N;
+    if (pl.wide_ep == EP_BIAS_RESID) { p.out = (float*)a->C; p.ldo = a->ldc; p.resid = a->resid; p.ldr = a->ldr; p.row_scale = a->row_scale; }
+    else { p.outb = (bf16*)a->C; p.ldob = a->ldc; p.aux_in = (const bf16*)a->aux_in; p.aux_out = (bf16*)a->aux_out; p.ld_aux = a->ld_aux; }
+    switch (pl.wide_ep) {
+        case EP_BIAS_RESID: return dispatch_fm<false, MODE_WIDE, EP_BIAS_RESID>(p, pl.fm, s, "gv_linear(wide)");
+        case EP_BIAS: return dispatch_fm<false, MODE_WIDE, EP_BIAS>(p, pl.fm, s, "gv_linear(wide)");
+        case EP_BIAS_GELU: return dispatch_fm<false, MODE_WIDE, EP_BIAS_GELU>(p, pl.fm, s, "gv_linear(wide)");
+        case EP_BIAS_GELU_SAVE: return dispatch_fm<false, MODE_WIDE, EP_BIAS_GELU_SAVE>(p, pl.fm, s, "gv_linear(wide)");
+        case EP_NONE: return dispatch_fm<true, MODE_WIDE, EP_NONE>(p, pl.fm, s, "gv_linear(wide)");
+        default: return dispatch_fm<true, MODE_WIDE, EP_DGELU>(p, pl.fm, s, "gv_linear(wide)");
     }
-    if (!a->trans_b) {
-        if (e == GV_EPI_BIAS) return dispatch_fm<false, MODE_WIDE, EP_BIAS>(p, s, "gv_linear(wide)");
-        if (e == (GV_EPI_BIAS | GV_EPI_GELU)) return dispatch_fm<false, MODE_WIDE, EP_BIAS_GELU>(p, s, "gv_linear(wide)");
-        if (e == (GV_EPI_BIAS | GV_EPI_GELU | GV_EPI_SAVE_PRE)) return dispatch_fm<false, MODE_WIDE, EP_BIAS_GELU_SAVE>(p, s, "gv_linear(wide)");
-    } else {
-        if (e == 0) return dispatch_fm<true, MODE_WIDE, EP_NONE>(p, s, "gv_linear(wide)");
-        if (e == GV_EPI_DGELU) return dispatch_fm<true, MODE_WIDE, EP_DGELU>(p, s, "gv_linear(wide)");
-    }
-    return -1;
 }
 
 
 extern "C" int gv_linear_ln_blocks(int32_t M) {
     if (M <= 0) return 0;
-    return (M + 16 * pick_fm(M) - 1) / (16 * pick_fm(M));
+    const int fm = pick_fm(M, gv_cu_budget());
+    return (M + 16 * fm - 1) / (16 * fm);
 }
 
 extern "C" int gv_linear_ln_fwd(const gv_linear_ln_fwd_args* a, void* stream) {
@@ -884,7 +838,7 @@ extern "C" int gv_linear_ln_fwd(const gv_linear_ln_fwd_args* a, void* stream) {
     p.bias = a->bias; p.resid = a->resid; p.ldr = a->ldr; p.out = a->out; p.ldo = a->ldo;
     p.gamma = a->gamma; p.beta = a->beta; p.eps = a->eps; p.y = (bf16*)a->y; p.mean = a->mean; p.rstd = a->rstd;
     p.row_scale = a->row_scale;
-    return dispatch_fm<false, MODE_FWD>(p, (hipStream_t)stream, "gv_linear_ln_fwd");
+    return dispatch_fm<false, MODE_FWD>(p, pick_fm(p.M, gv_cu_budget()), (hipStream_t)stream, "gv_linear_ln_fwd");
 }
 
 // mlp.fc1 -> GELU -> mlp.fc2 -> + residual -> the next LayerNorm in ONE launch (vit.pyc@L98-104, L146-152) for passes that keep no
@@ -908,7 +862,7 @@ extern "C" int gv_mlp_ln_fwd(const gv_mlp_ln_fwd_args* a, void* stream) {
     p.gamma = a->gamma; p.beta = a->beta; p.eps = a->eps; p.y = (bf16*)a->y; p.mean = a->mean; p.rstd = a->rstd;
     p.row_scale = a->row_scale;
     hipStream_t s = (hipStream_t)stream;
-    if (a->M <= gv_cu_budget() * 64) return launch_panel<4, 8, 64, false, MODE_FWD, EP_MLP>(p, s, "gv_mlp_ln_fwd");
+    if (pick_fm_mlp(a->M, gv_cu_budget()) == 4) return launch_panel<4, 8, 64, false, MODE_FWD, EP_MLP>(p, s, "gv_mlp_ln_fwd");
     return launch_panel<7, 8, 64, false, MODE_FWD, EP_MLP>(p, s, "gv_mlp_ln_fwd");
 }
 
@@ -926,5 +880,5 @@ extern "C" int gv_linear_ln_bwd(const gv_linear_ln_bwd_args* a, void* stream) {
     p.x = a->x; p.ldx = a->ldx; p.mean = (float*)a->mean; p.rstd = (float*)a->rstd; p.gamma = a->gamma;
     p.g = a->g; p.ldg = a->ldg; p.gb = (bf16*)a->gb; p.ldgb = a->ldgb; p.partials = a->partials; p.g_init = a->g_init;
     p.gb_scale = a->gb_scale;
-    return dispatch_fm<true, MODE_BWD>(p, (hipStream_t)stream, "gv_linear_ln_bwd");
+    return dispatch_fm<true, MODE_BWD>(p, pick_fm(p.M, gv_cu_budget()), (hipStream_t)stream, "gv_linear_ln_bwd");
 }

@@ -9,6 +9,3 @@ bool enabled();
 int begin(const char* kernel_name, double flops, double bytes, hipStream_t s);
 void end(int handle, hipStream_t s);
 }  // namespace gvtime
-
-// panel.hip: gv_linear's wide bf16 products on the full-row kernel; -1 = not one of them
-int gv_panel_wide(const gv_linear_args* a, hipStream_t s);

@@ -107,9 +107,9 @@ def test_bad_arguments_fail_loudly_without_gpu():
             cls(precision="fp16", device="cpu")
 
 
-def test_workspace_query_runs_the_entry_points_in_plan_mode():
-    """gv_workspace_bytes(op, args): the scratch one call would use, answered by the entry point's own kernel selection
-    and k-slice sizing in a plan mode -- nothing is launched, no GPU is touched."""
+def test_workspace_query_answers_from_the_entry_points_plan():
+    """gv_workspace_bytes(op, args): the scratch one call would use -- the entry point's own argument checks, then the
+    plan its launch follows (csrc/linear_plan.h) -- nothing is launched, no GPU is touched."""
     from gipvit import _lib
     q = lambda op, a: _lib.lib.gv_workspace_bytes(op, ctypes.byref(a))
     P = 1 << 20                                                        # any 16-byte aligned non-null value: never dereferenced

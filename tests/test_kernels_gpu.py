@@ -6,6 +6,8 @@ import math
 import pytest
 import torch
 
+import linear_plan_cases as lpc
+
 pytestmark = pytest.mark.gpu
 bf16, f32 = torch.bfloat16, torch.float32
 
@@ -379,6 +381,29 @@ def test_linear_dw_group_exact(dev, T):
         assert torch.equal(dW, rw)
         if cs is not None:
             assert torch.equal(cs, rc)
+
+
+_PLANS = lpc.load()
+_PLAN_ROWS = [(kind, r) for kind in ("linear", "group", "fullrow") for r in _PLANS[kind] if "kernel" in r]
+
+
+@pytest.fixture(scope="module")
+def plan_ws(dev):
+    return torch.empty(L().lib.gv_linear_workspace_bytes() // 4, dtype=f32, device=dev)
+
+
+@pytest.mark.parametrize("kind,row", _PLAN_ROWS, ids=[r["id"] for _, r in _PLAN_ROWS])
+def test_linear_plan_kernel_and_result(dev, plan_ws, kind, row):
+    """Every GPU row of tests/traces/linear_plans.json (the edges of every predicate of csrc/linear_plan.h): the call, once, under
+    linear_timing, gets exactly the kernel the fixture names -- a product that falls back to another kernel fails here, not only in
+    a benchmark -- and its result on seeded integers is exact against the f32 matmul of the same integers (tests/linear_plan_cases.py:
+    bias / residual / ACCUM / column sums as integers, GELU' at 0, GELU as the library's own polynomial, one guard row).  The
+    full-row LayerNorm-backward and fused-MLP rows have no exact form: kernel and finite outputs only, their tolerances are above."""
+    rows, checks = lpc.run_row(ops(), L(), kind, row, dev, plan_ws)
+    print(row["id"], [(r["kernel"], r["launches"]) for r in rows])
+    assert [(r["kernel"], r["launches"]) for r in rows] == [(row["kernel"], 1)]
+    for what, got, want in checks:
+        assert torch.equal(got, want), what
 
 
 def test_linear_ln_rejects_other_widths(dev):
