@@ -90,7 +90,8 @@ gv_linear_ln_bwd_args = _struct("gv_linear_ln_bwd_args", [
     ("mean", vp), ("rstd", vp), ("gamma", vp), ("g", vp), ("ldg", i64), ("gb", vp), ("ldgb", i64), ("partials", vp),
     ("partial_blocks", i32), ("g_init", i32), ("gb_scale", vp)])
 GV_ATTN_MAX_SEG = 4
-GV_ATTN_MAX_N, GV_ATTN_STREAM_MAX_N, GV_ATTN_STREAM_QBLOCK = 288, 1040, 128     # gv_attention_fwd / gv_attention_fwd_stream
+# the four attention limits of include/gipvit.h (tests/test_attn_plan_host.py holds them, and train.py's copies, to the header's text)
+GV_ATTN_MAX_N, GV_ATTN_F32_MAX_N, GV_ATTN_STREAM_MAX_N, GV_ATTN_STREAM_QBLOCK = 288, 260, 1040, 128
 gv_attention_fwd_varlen_args = _struct("gv_attention_fwd_varlen_args", [
     ("qkv", vp), ("o", vp), ("n_seg", i32), ("n_img", i32 * GV_ATTN_MAX_SEG), ("N", i32 * GV_ATTN_MAX_SEG), ("lse", vp * GV_ATTN_MAX_SEG),
     ("H", i32), ("scale", f32), ("q_limit", i32)])

@@ -1,4 +1,4 @@
-// Fused multi-head attention forward / backward for short sequences (N <= 288,
+// Fused multi-head attention forward / backward for short sequences (N <= GV_ATTN_MAX_N,
 // head_dim 64) -- replaces Attention.forward's q@k^T, softmax, attn@v ATen calls
 // (vit.pyc@L119-131) and their autograd backward; the N x N score matrix never
 // reaches HBM.  A whole sequence fits one workgroup's LDS.
@@ -15,27 +15,17 @@
 //           operands of dV^T += dO^T P and dK^T += Q^T dS, so dK/dV need no cross-wave
 //           sum.  Only dS crosses LDS (transposed image) for dQ = dS K.
 #include "gv_common.h"
+#include "attn_plan.h"    // length classes, FwdCfg / BwdCfg, launch geometry: everything the host decides
 #include <type_traits>
 
 namespace {
 
-#include "attn_tiles.h"   // the LDS image, its LDS-DMA staging and the fragment reads (shared with attention_stream.hip)
+using namespace gvattn;
+#include "attn_tiles.h"   // the LDS image, its LDS-DMA staging and the fragment reads, the entry checks (shared with attention_stream.hip)
 
 // ---------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------
-template <int NKT>
-struct FwdCfg {
-    // long sequences: 16 queries per wave and round (the score registers halve, two 8-wave workgroups
-    // fit a CU and cover each other's load phases); short ones: 32 queries per wave
-    static constexpr int QT = NKT >= 14 ? 1 : 2;                  // 16-query tiles per wave and round
-    static constexpr int NQB = (NKT + QT - 1) / QT;               // query blocks of 16 QT rows
-    static constexpr int NW = NQB >= 5 ? 8 : 4;                   // waves per workgroup
-    static constexpr int PAIRS = NQB >= NW ? 1 : (NW / NQB >= 1 ? NW / NQB : 1);
-    static constexpr int WPP = NW / PAIRS;                        // waves per (image, head) pair
-    static constexpr int ROUNDS = (NQB + WPP - 1) / WPP;          // query blocks per wave
-};
-
 // One workgroup's worth of forward work: `block` = index among the workgroups of this length class, `wave` = wave index inside
 // the NW waves that run it, `smem` = their LDS.  (A stand-alone launch passes blockIdx.x and the whole workgroup; the varlen
 // launch runs two 4-wave instances of the short class side by side in one 8-wave workgroup.)
@@ -43,8 +33,7 @@ template <int NKT>
 __device__ __forceinline__ void attn_fwd_body(const gv_attention_fwd_args a, const int n_pairs, const int block, const int wave, const int lane, GV_LDS char* const smem) {
     using F = FwdCfg<NKT>;
     constexpr int NQB = F::NQB, PAIRS = F::PAIRS, WPP = F::WPP, NW = F::NW, ROUNDS = F::ROUNDS, QT = F::QT, QB = 16 * QT;
-    constexpr int NP = NKT * 16;
-    constexpr int IMG = NP * 128;
+    constexpr int NP = F::NP, IMG = F::IMG;
     const int N = a.N, H = a.H;
     const long ld = 3L * H * 64;
     const bf16* qkv = (const bf16*)a.qkv;
@@ -183,9 +172,8 @@ __device__ __forceinline__ void attn_fwd_body(const gv_attention_fwd_args a, con
     attn_static_for<0, ROUNDS>(round);
 }
 
-// (second launch-bounds argument = waves per SIMD the register allocation must leave room for: two 8-wave workgroups per CU = 4)
 template <int NKT>
-__global__ __launch_bounds__(FwdCfg<NKT>::NW * 64, FwdCfg<NKT>::QT == 1 && NKT <= 14 ? 4 : (FwdCfg<NKT>::QT == 1 ? 2 : 1)) void attn_fwd_kernel(gv_attention_fwd_args a, int n_pairs) {
+__global__ __launch_bounds__(FwdCfg<NKT>::THREADS, FwdCfg<NKT>::OCC) void attn_fwd_kernel(gv_attention_fwd_args a, int n_pairs) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     attn_fwd_body<NKT>(a, n_pairs, blockIdx.x, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63, (GV_LDS char*)smem_raw);
 }
@@ -196,49 +184,29 @@ __global__ __launch_bounds__(FwdCfg<NKT>::NW * 64, FwdCfg<NKT>::QT == 1 && NKT <
 // registers either way: two workgroups per CU.  For the step's student pass (768 long + 3 072 short pairs) that is 768 + 768
 // workgroups = exactly three rounds of the 512 slots, where the long launch alone filled one and a half.
 // (Every instance passes the same workgroup barriers: the bodies' barrier count does not depend on the data.)
-constexpr int VL_LDS_LONG = FwdCfg<14>::PAIRS * 2 * 14 * 16 * 128, VL_LDS_SHORT = FwdCfg<4>::PAIRS * 2 * 4 * 16 * 128;
-constexpr int VL_LDS = VL_LDS_LONG > 2 * VL_LDS_SHORT ? VL_LDS_LONG : 2 * VL_LDS_SHORT;
-static_assert(FwdCfg<14>::NW == 8 && FwdCfg<4>::NW == 4, "varlen launch: 8-wave long class, two 4-wave short instances");
-__global__ __launch_bounds__(512, 4) void attn_fwd_varlen_kernel(gv_attention_fwd_args al, int np_long, int nblk_long, gv_attention_fwd_args as, int np_short) {
+__global__ __launch_bounds__(VarlenCfg::THREADS, VarlenCfg::OCC) void attn_fwd_varlen_kernel(gv_attention_fwd_args al, int np_long, int nblk_long, gv_attention_fwd_args as, int np_short) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     GV_LDS char* smem = (GV_LDS char*)smem_raw;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if ((int)blockIdx.x < nblk_long) {
-        attn_fwd_body<14>(al, np_long, blockIdx.x, wave, lane, smem);
+        attn_fwd_body<VarlenCfg::LONG>(al, np_long, blockIdx.x, wave, lane, smem);
     } else {
         const int sub = wave >> 2;
-        attn_fwd_body<4>(as, np_short, ((int)blockIdx.x - nblk_long) * 2 + sub, wave & 3, lane, smem + sub * VL_LDS_SHORT);
+        attn_fwd_body<VarlenCfg::SHORT>(as, np_short, ((int)blockIdx.x - nblk_long) * VarlenCfg::SHORT_PER_WG + sub, wave & 3, lane, smem + sub * VarlenCfg::LDS_SHORT);
     }
 }
 
 // ---------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------
-// KT = 16-key tiles per wave.  KT = 2: 32 keys per wave, ~190 registers, 2 waves per SIMD.  KT = 1: 16 keys per wave, the same
-// chain on half the keys in < 128 registers, 4 waves per SIMD -- but every wave still reads all of Q and dO from LDS, so the
-// workgroup's LDS read traffic of phase A doubles (measured: the short crops gain 20 %, N = 197 gains nothing; see gv_attention_bwd).
 template <int NKT, int KT>
-struct BwdCfg {
-    static constexpr int NKB = NKT / KT;               // key blocks of 16 KT keys = waves per pair
-    static constexpr int PAIRS = NKB >= 4 ? 1 : 4 / NKB;
-    static constexpr int NW = NKB * PAIRS;             // waves per workgroup
-    // dS^T images.  2 where a (image, head) pair holds its CU alone anyway (N = 197: 142 KB instead of 114): the image alternates per
-    // 64-query step and the step's second barrier goes (72.9 -> 70.4 us per launch; the short classes, several workgroups per CU, keep 1)
-    static constexpr int NDS = NKT == 14 ? 2 : 1;
-};
-template <int NKT, int KT>
-// short sequences run two 4-wave workgroups per CU: the second launch-bounds argument keeps them within 256 registers
-__global__ __launch_bounds__((BwdCfg<NKT, KT>::NW * 64), ((NKT >= 14 || BwdCfg<NKT, KT>::NW > 8) ? 1 : 2)) void attn_bwd_kernel(gv_attention_bwd_args a, int n_pairs) {
-    constexpr int NKB = BwdCfg<NKT, KT>::NKB, PAIRS = BwdCfg<NKT, KT>::PAIRS, NW = BwdCfg<NKT, KT>::NW;
+__global__ __launch_bounds__((BwdCfg<NKT, KT>::THREADS), (BwdCfg<NKT, KT>::OCC)) void attn_bwd_kernel(gv_attention_bwd_args a, int n_pairs) {
+    using B = BwdCfg<NKT, KT>;
+    constexpr int NKB = B::NKB, PAIRS = B::PAIRS, NW = B::NW;
     constexpr int KW = 16 * KT;                        // keys per wave
     constexpr int NK32 = NKT / 2;                      // 32-key slices of the dQ reduction
-    constexpr int NP = NKT * 16;
-    constexpr int IMG = NP * 128;
-    constexpr int QH = NKT >= 8 ? 2 : 1;               // 32-query halves per barrier pair (short sequences keep 1)
-    constexpr int DROW = 64 * QH;                      // dS^T image: [key][32 QH q] bf16
-    constexpr int DST = NP * DROW;
-    constexpr int NDS = BwdCfg<NKT, KT>::NDS;          // dS^T images (2: the image alternates per step and the step's second barrier goes)
-    constexpr int PER_PAIR = 3 * IMG + NDS * DST + 2 * NP * 4;
+    // the LDS layout, as the launcher sized it: per pair Q, K, dO images, NDS dS^T images [key][32 QH q], delta and lse
+    constexpr int NP = B::NP, IMG = B::IMG, QH = B::QH, DROW = B::DROW, DST = B::DST, NDS = B::NDS, PER_PAIR = B::PER_PAIR;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     GV_LDS char* smem = (GV_LDS char*)smem_raw;
     const int lane = threadIdx.x & 63;
@@ -263,7 +231,7 @@ __global__ __launch_bounds__((BwdCfg<NKT, KT>::NW * 64), ((NKT >= 14 || BwdCfg<N
     static_assert(NW * 64 >= PAIRS * NP, "one (pair, query) per thread");
     const int dq_pr = threadIdx.x / NP, dq_q = threadIdx.x - dq_pr * NP;
     const bool dq_has = (int)threadIdx.x < PAIRS * NP, dq_live = dq_has && dq_q < N;
-    // (the 9-wave N <= 288 build has 168 registers per lane: there the row is multiplied against dO from global straight away)
+    // (the 9-wave build of the largest class has 168 registers per lane: there the row is multiplied against dO from global straight away)
     constexpr bool DELTA_LDS = NKT < 18;
     bf16x8 orow8[DELTA_LDS ? 8 : 1];
     float lse_q = 0.f, delta_q = 0.f;
@@ -470,37 +438,29 @@ __global__ __launch_bounds__((BwdCfg<NKT, KT>::NW * 64), ((NKT >= 14 || BwdCfg<N
 }
 
 template <int NKT> int launch_fwd(const gv_attention_fwd_args* a, hipStream_t s) {
-    constexpr int PAIRS = FwdCfg<NKT>::PAIRS;
-    constexpr int LDS = PAIRS * 2 * NKT * 16 * 128;
+    const int n_pairs = a->n_img * a->H;
+    const Launch l = fwd_launch<NKT>(n_pairs);
     auto kern = attn_fwd_kernel<NKT>;
     static GvLdsOptIn opt_in;
-    if (int rc = gv_lds_opt_in(opt_in, (const void*)kern, LDS, "gv_attention_fwd")) return rc;
-    const int n_pairs = a->n_img * a->H;
-    hipLaunchKernelGGL(kern, dim3((n_pairs + PAIRS - 1) / PAIRS), dim3(FwdCfg<NKT>::NW * 64), LDS, s, *a, n_pairs);
+    if (int rc = gv_lds_opt_in(opt_in, (const void*)kern, l.lds_bytes, "gv_attention_fwd")) return rc;
+    hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.block), l.lds_bytes, s, *a, n_pairs);
     GV_LAUNCH_CHECK("gv_attention_fwd");
     return GV_OK;
 }
 
-template <int NKT, int KT> int launch_bwd(const gv_attention_bwd_args* a, hipStream_t s) {
-    using B = BwdCfg<NKT, KT>;
-    constexpr int PAIRS = B::PAIRS, NW = B::NW, NP = NKT * 16;
-    constexpr int LDS = PAIRS * (3 * NP * 128 + B::NDS * NP * (NKT >= 8 ? 128 : 64) + 2 * NP * 4);
-    static_assert(NW * 64 <= 1024 && LDS <= 160 * 1024, "workgroup size / LDS");
-    auto kern = attn_bwd_kernel<NKT, KT>;
-    static GvLdsOptIn opt_in;
-    if (int rc = gv_lds_opt_in(opt_in, (const void*)kern, LDS, "gv_attention_bwd")) return rc;
+template <int NKT> int launch_bwd(const gv_attention_bwd_args* a, hipStream_t s) {
     const int n_pairs = a->n_img * a->H;
-    hipLaunchKernelGGL(kern, dim3((n_pairs + PAIRS - 1) / PAIRS), dim3(NW * 64), LDS, s, *a, n_pairs);
+    const Launch l = bwd_launch<NKT>(n_pairs);
+    auto kern = attn_bwd_kernel<NKT, bwd_kt(NKT)>;
+    static GvLdsOptIn opt_in;
+    if (int rc = gv_lds_opt_in(opt_in, (const void*)kern, l.lds_bytes, "gv_attention_bwd")) return rc;
+    hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.block), l.lds_bytes, s, *a, n_pairs);
     GV_LAUNCH_CHECK("gv_attention_bwd");
     return GV_OK;
 }
 
 int launch_fwd_any(const gv_attention_fwd_args* a, hipStream_t s) {
-    if (a->N <= 32) return launch_fwd<2>(a, s);
-    if (a->N <= 64) return launch_fwd<4>(a, s);
-    if (a->N <= 128) return launch_fwd<8>(a, s);
-    if (a->N <= 224) return launch_fwd<14>(a, s);
-    return launch_fwd<18>(a, s);
+    return with_class(a->N, [&](auto c) { return launch_fwd<decltype(c)::value>(a, s); });
 }
 
 // ---------------------------------------------------------------------------------
@@ -551,7 +511,7 @@ __device__ __forceinline__ void probs_tile(const gv_attention_probs_args& a, con
 // all query rows: one workgroup per (image, head) pair, K staged once into the swizzled LDS image by LDS-DMA, the pair's
 // 16-query tiles spread over the waves
 template <int NKT>
-__global__ __launch_bounds__(256) void attn_probs_kernel(gv_attention_probs_args a) {
+__global__ __launch_bounds__(PROBS_NW * 64) void attn_probs_kernel(gv_attention_probs_args a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     GV_LDS char* Kimg = (GV_LDS char*)smem_raw;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
@@ -571,9 +531,9 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(gv_attention_probs_args
 // q_rows <= 16 (the CLS row): a GEMV per pair -- one wave per pair, K fragments straight from global (every K element is read
 // once), all of them issued before the first MFMA
 template <int NKT>
-__global__ __launch_bounds__(256) void attn_probs_row_kernel(gv_attention_probs_args a, int n_pairs) {
+__global__ __launch_bounds__(PROBS_NW * 64) void attn_probs_row_kernel(gv_attention_probs_args a, int n_pairs) {
     const int lane = threadIdx.x & 63;
-    const long pair = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long pair = (long)blockIdx.x * PROBS_NW + (threadIdx.x >> 6);
     if (pair >= n_pairs) return;
     const int N = a.N, H = a.H;
     const long ld = 3L * H * 64;
@@ -593,63 +553,64 @@ __global__ __launch_bounds__(256) void attn_probs_row_kernel(gv_attention_probs_
 
 template <int NKT> int launch_probs(const gv_attention_probs_args* a, hipStream_t s) {
     const int n_pairs = a->n_img * a->H;
-    if (a->q_rows <= 16) {
-        hipLaunchKernelGGL(attn_probs_row_kernel<NKT>, dim3((n_pairs + 3) / 4), dim3(256), 0, s, *a, n_pairs);
+    const Launch l = probs_launch<NKT>(n_pairs, a->q_rows);
+    if (probs_by_row(a->q_rows)) {
+        hipLaunchKernelGGL(attn_probs_row_kernel<NKT>, dim3(l.grid), dim3(l.block), 0, s, *a, n_pairs);
     } else {
-        constexpr int LDS = NKT * 16 * 128;
         static GvLdsOptIn opt_in;
-        if (int rc = gv_lds_opt_in(opt_in, (const void*)attn_probs_kernel<NKT>, LDS, "gv_attention_probs")) return rc;
-        const int n_qt = (a->q_rows + 15) / 16, nw = n_qt < 4 ? n_qt : 4;
-        hipLaunchKernelGGL(attn_probs_kernel<NKT>, dim3(n_pairs), dim3(nw * 64), LDS, s, *a);
+        if (int rc = gv_lds_opt_in(opt_in, (const void*)attn_probs_kernel<NKT>, l.lds_bytes, "gv_attention_probs")) return rc;
+        hipLaunchKernelGGL(attn_probs_kernel<NKT>, dim3(l.grid), dim3(l.block), l.lds_bytes, s, *a);
     }
     GV_LAUNCH_CHECK("gv_attention_probs");
+    return GV_OK;
+}
+
+// segment i of a varlen table, rows from `row` on, as the argument struct of the plain call
+template <class Seg, class V> int varlen_segment(const char* name, const V* v, int i, long row, Seg* seg) {
+    GV_REQUIRE(shape_ok(v->n_img[i], v->H, v->N[i], GV_ATTN_MAX_N) && v->lse[i], GV_E_SHAPE,
+               "%s: segment %d: need n_img > 0, 0 < N <= %d, lse", name, i, GV_ATTN_MAX_N);
+    const long o_bytes = row * v->H * 64 * 2;
+    seg->qkv = (const char*)v->qkv + 3 * o_bytes;
+    seg->o = (char*)v->o + o_bytes;
+    if constexpr (std::is_same_v<Seg, gv_attention_bwd_args>) {
+        seg->d_o = (const char*)v->d_o + o_bytes;
+        seg->dqkv = (char*)v->dqkv + 3 * o_bytes;
+    }
+    seg->lse = v->lse[i]; seg->n_img = v->n_img[i]; seg->N = v->N[i]; seg->H = v->H; seg->scale = v->scale;
+    seg->q_limit = v->q_limit;
     return GV_OK;
 }
 
 }  // namespace
 
 extern "C" int gv_attention_probs(const gv_attention_probs_args* a, void* stream) {
-    GV_REQUIRE(a && a->qkv && a->lse && a->p, GV_E_NULL, "gv_attention_probs: null pointer");
-    GV_REQUIRE(a->n_img > 0 && a->H > 0 && a->N > 0 && a->N <= 288, GV_E_SHAPE, "gv_attention_probs: need n_img > 0, H > 0, 0 < N <= 288 (got N = %d)", a->N);
+    if (int rc = attn_check("gv_attention_probs", a, a && a->qkv && a->lse && a->p, GV_ATTN_MAX_N, true)) return rc;
     GV_REQUIRE(a->q_rows >= 1 && a->q_rows <= a->N, GV_E_SHAPE, "gv_attention_probs: need 1 <= q_rows <= N (got q_rows = %d, N = %d)", a->q_rows, a->N);
-    GV_REQUIRE(gv_aligned(a->qkv, 16), GV_E_ALIGN, "gv_attention_probs: qkv must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    if (a->N <= 32) return launch_probs<2>(a, s);
-    if (a->N <= 64) return launch_probs<4>(a, s);
-    if (a->N <= 128) return launch_probs<8>(a, s);
-    if (a->N <= 224) return launch_probs<14>(a, s);
-    return launch_probs<18>(a, s);
+    if (int rc = attn_aligned("gv_attention_probs", "qkv", {a->qkv})) return rc;
+    return with_class(a->N, [&](auto c) { return launch_probs<decltype(c)::value>(a, (hipStream_t)stream); });
 }
 
 extern "C" int gv_attention_fwd_varlen(const gv_attention_fwd_varlen_args* v, void* stream) {
     GV_REQUIRE(v && v->qkv && v->o, GV_E_NULL, "gv_attention_fwd_varlen: null pointer");
     GV_REQUIRE(v->n_seg >= 1 && v->n_seg <= GV_ATTN_MAX_SEG && v->H > 0, GV_E_SHAPE, "gv_attention_fwd_varlen: 1..%d segments, H > 0", GV_ATTN_MAX_SEG);
-    GV_REQUIRE(gv_aligned(v->qkv, 16) && gv_aligned(v->o, 16), GV_E_ALIGN, "gv_attention_fwd_varlen: qkv/o must be 16-byte aligned");
+    if (int rc = attn_aligned("gv_attention_fwd_varlen", "qkv/o", {v->qkv, v->o})) return rc;
     hipStream_t s = (hipStream_t)stream;
     gv_attention_fwd_args seg[GV_ATTN_MAX_SEG];
     long row = 0;
     for (int i = 0; i < v->n_seg; ++i) {
-        GV_REQUIRE(v->n_img[i] > 0 && v->N[i] > 0 && v->N[i] <= 288 && v->lse[i], GV_E_SHAPE, "gv_attention_fwd_varlen: segment %d: need n_img > 0, 0 < N <= 288, lse", i);
-        seg[i].qkv = (const char*)v->qkv + row * 3 * v->H * 64 * 2;
-        seg[i].o = (char*)v->o + row * v->H * 64 * 2;
-        seg[i].lse = v->lse[i]; seg[i].n_img = v->n_img[i]; seg[i].N = v->N[i]; seg[i].H = v->H; seg[i].scale = v->scale;
-        seg[i].q_limit = v->q_limit;
+        if (int rc = varlen_segment("gv_attention_fwd_varlen", v, i, row, &seg[i])) return rc;
         row += (long)v->n_img[i] * v->N[i];
     }
     // one launch for a long + a short segment (either order); any other mix runs one launch per segment
-    if (v->n_seg == 2) {
-        const int il = (seg[0].N > 128 && seg[0].N <= 224) ? 0 : ((seg[1].N > 128 && seg[1].N <= 224) ? 1 : -1);
-        const int is = il < 0 ? -1 : 1 - il;
-        if (il >= 0 && seg[is].N > 32 && seg[is].N <= 64) {
-            static GvLdsOptIn opt_in;
-            if (int rc = gv_lds_opt_in(opt_in, (const void*)attn_fwd_varlen_kernel, VL_LDS, "gv_attention_fwd_varlen")) return rc;
-            const int np_long = seg[il].n_img * v->H, np_short = seg[is].n_img * v->H;
-            const int nblk_long = (np_long + FwdCfg<14>::PAIRS - 1) / FwdCfg<14>::PAIRS;
-            const int nblk_short = (np_short + 2 * FwdCfg<4>::PAIRS - 1) / (2 * FwdCfg<4>::PAIRS);
-            hipLaunchKernelGGL(attn_fwd_varlen_kernel, dim3(nblk_long + nblk_short), dim3(512), VL_LDS, s, seg[il], np_long, nblk_long, seg[is], np_short);
-            GV_LAUNCH_CHECK("gv_attention_fwd_varlen");
-            return GV_OK;
-        }
+    const int il = v->n_seg == 2 ? varlen_long_segment(seg[0].N, seg[1].N) : -1;
+    if (il >= 0) {
+        const int is = 1 - il, np_long = seg[il].n_img * v->H, np_short = seg[is].n_img * v->H;
+        const Launch l = VarlenCfg::launch(np_long, np_short);
+        static GvLdsOptIn opt_in;
+        if (int rc = gv_lds_opt_in(opt_in, (const void*)attn_fwd_varlen_kernel, l.lds_bytes, "gv_attention_fwd_varlen")) return rc;
+        hipLaunchKernelGGL(attn_fwd_varlen_kernel, dim3(l.grid), dim3(l.block), l.lds_bytes, s, seg[il], np_long, VarlenCfg::long_blocks(np_long), seg[is], np_short);
+        GV_LAUNCH_CHECK("gv_attention_fwd_varlen");
+        return GV_OK;
     }
     for (int i = 0; i < v->n_seg; ++i)
         if (int rc = launch_fwd_any(&seg[i], s)) return rc;
@@ -657,9 +618,8 @@ extern "C" int gv_attention_fwd_varlen(const gv_attention_fwd_varlen_args* v, vo
 }
 
 extern "C" int gv_attention_fwd(const gv_attention_fwd_args* a, void* stream) {
-    GV_REQUIRE(a && a->qkv && a->o && a->lse, GV_E_NULL, "gv_attention_fwd: null pointer");
-    GV_REQUIRE(a->n_img > 0 && a->H > 0 && a->N > 0 && a->N <= 288, GV_E_SHAPE, "gv_attention_fwd: need 0 < N <= 288 (got %d)", a->N);
-    GV_REQUIRE(gv_aligned(a->qkv, 16) && gv_aligned(a->o, 16), GV_E_ALIGN, "gv_attention_fwd: qkv/o must be 16-byte aligned");
+    if (int rc = attn_check("gv_attention_fwd", a, a && a->qkv && a->o && a->lse, GV_ATTN_MAX_N, false)) return rc;
+    if (int rc = attn_aligned("gv_attention_fwd", "qkv/o", {a->qkv, a->o})) return rc;
     return launch_fwd_any(a, (hipStream_t)stream);
 }
 
@@ -668,14 +628,8 @@ extern "C" int gv_attention_bwd_varlen(const gv_attention_bwd_varlen_args* v, vo
     GV_REQUIRE(v->n_seg >= 1 && v->n_seg <= GV_ATTN_MAX_SEG && v->H > 0, GV_E_SHAPE, "gv_attention_bwd_varlen: 1..%d segments, H > 0", GV_ATTN_MAX_SEG);
     long row = 0;
     for (int i = 0; i < v->n_seg; ++i) {
-        GV_REQUIRE(v->n_img[i] > 0 && v->N[i] > 0 && v->N[i] <= 288 && v->lse[i], GV_E_SHAPE, "gv_attention_bwd_varlen: segment %d: need n_img > 0, 0 < N <= 288, lse", i);
         gv_attention_bwd_args seg;
-        seg.qkv = (const char*)v->qkv + row * 3 * v->H * 64 * 2;
-        seg.o = (const char*)v->o + row * v->H * 64 * 2;
-        seg.d_o = (const char*)v->d_o + row * v->H * 64 * 2;
-        seg.dqkv = (char*)v->dqkv + row * 3 * v->H * 64 * 2;
-        seg.lse = v->lse[i]; seg.n_img = v->n_img[i]; seg.N = v->N[i]; seg.H = v->H; seg.scale = v->scale;
-        seg.q_limit = v->q_limit;
+        if (int rc = varlen_segment("gv_attention_bwd_varlen", v, i, row, &seg)) return rc;
         if (int rc = gv_attention_bwd(&seg, stream)) return rc;
         row += (long)v->n_img[i] * v->N[i];
     }
@@ -683,17 +637,7 @@ extern "C" int gv_attention_bwd_varlen(const gv_attention_bwd_varlen_args* v, vo
 }
 
 extern "C" int gv_attention_bwd(const gv_attention_bwd_args* a, void* stream) {
-    GV_REQUIRE(a && a->qkv && a->o && a->d_o && a->lse && a->dqkv, GV_E_NULL, "gv_attention_bwd: null pointer");
-    GV_REQUIRE(a->n_img > 0 && a->H > 0 && a->N > 0 && a->N <= 288, GV_E_SHAPE, "gv_attention_bwd: need 0 < N <= 288 (got %d)", a->N);
-    GV_REQUIRE(gv_aligned(a->qkv, 16) && gv_aligned(a->o, 16) && gv_aligned(a->d_o, 16) && gv_aligned(a->dqkv, 16), GV_E_ALIGN,
-               "gv_attention_bwd: buffers must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    // keys per wave: 16 for the short crops (N = 37: 39.2 -> 31.4 us per launch of 512 images x 6 heads), 32 from N = 65 on (N = 197:
-    // 72.6 us against 73.8 with 16 -- twice the waves buy nothing there: per (image, head) pair the kernel is the SUM of ~8 us of
-    // exp / dS arithmetic, ~4 us of MFMA and ~8 us (32 keys) or ~12 us (16 keys) of LDS reads, phase-aligned by its barriers)
-    if (a->N <= 32) return launch_bwd<2, 2>(a, s);
-    if (a->N <= 64) return launch_bwd<4, 1>(a, s);
-    if (a->N <= 128) return launch_bwd<8, 2>(a, s);
-    if (a->N <= 224) return launch_bwd<14, 2>(a, s);
-    return launch_bwd<18, 2>(a, s);
+    if (int rc = attn_check("gv_attention_bwd", a, a && a->qkv && a->o && a->d_o && a->lse && a->dqkv, GV_ATTN_MAX_N, false)) return rc;
+    if (int rc = attn_aligned("gv_attention_bwd", "buffers", {a->qkv, a->o, a->d_o, a->dqkv})) return rc;
+    return with_class(a->N, [&](auto c) { return launch_bwd<decltype(c)::value>(a, (hipStream_t)stream); });
 }

@@ -1,6 +1,6 @@
 // Streaming attention forward for sequences past one workgroup's LDS (N <= GV_ATTN_STREAM_MAX_N, head_dim 64): the forward of
 // attention.hip with K / V passed through LDS in 64-key blocks and an online softmax, so that inference runs on tiles up to
-// 512 px (1 025 tokens).  Forward only: nothing here is saved for, or read by, a backward past 288 tokens.
+// 512 px (1 025 tokens).  Forward only: nothing here is saved for, or read by, a backward past GV_ATTN_MAX_N tokens.
 //
 // A workgroup = one (image, head) pair x one block of GV_ATTN_STREAM_QBLOCK = 128 query rows: 4 waves of 32 queries, Q fragments
 // in registers.  K / V key blocks are double buffered in the swizzled image of attn_tiles.h, filled by LDS-DMA: block j + 1 is
@@ -15,23 +15,20 @@
 // Every block multiplies by alpha (there is no "max did not move" branch to get wrong), keys >= N of the last block score -inf,
 // one division at the end, lse = m scale + log l.  No atomics, nothing shared between workgroups.
 #include "gv_common.h"
+#include "attn_plan.h"    // StreamCfg: the workgroup's shape, its LDS and the launch geometry
 #include <type_traits>
 
 namespace {
 
 #include "attn_tiles.h"
 
-constexpr int SQB = GV_ATTN_STREAM_QBLOCK;      // query rows per workgroup
-constexpr int SNW = 4;                          // waves per workgroup
+using S = gvattn::StreamCfg;
+constexpr int SQB = S::QB, SNW = S::NW, SKB = S::KB, SIMG = S::IMG;
 constexpr int SQT = SQB / (16 * SNW);           // 16-query tiles per wave
-constexpr int SKT = 4;                          // 16-key tiles per key block
-constexpr int SKB = 16 * SKT;                   // keys per block
-constexpr int SIMG = SKB * 128;                 // one K or V block image
-constexpr int SLDS = 2 * 2 * SIMG;              // two stages of (K, V)
+constexpr int SKT = SKB / 16;                   // 16-key tiles per key block
 static_assert(SQB % 32 == 0 && SQT == 2 && SKT % 2 == 0, "4 waves x 32 queries, 32-key P V slabs");
-static_assert(GV_ATTN_STREAM_MAX_N % 16 == 0 && SLDS <= 160 * 1024, "key tiles / LDS");
 
-__global__ __launch_bounds__(SNW * 64, 4) void attn_fwd_stream_kernel(gv_attention_fwd_args a, int nqb) {
+__global__ __launch_bounds__(S::THREADS, S::OCC) void attn_fwd_stream_kernel(gv_attention_fwd_args a, int nqb) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     GV_LDS char* const smem = (GV_LDS char*)smem_raw;
     const int lane = threadIdx.x & 63;
@@ -172,20 +169,15 @@ __global__ __launch_bounds__(SNW * 64, 4) void attn_fwd_stream_kernel(gv_attenti
 }  // namespace
 
 extern "C" int gv_attention_fwd_stream(const gv_attention_fwd_args* a, void* stream) {
-    GV_REQUIRE(a && a->qkv && a->o && a->lse, GV_E_NULL, "gv_attention_fwd_stream: null pointer");
-    GV_REQUIRE(a->n_img > 0 && a->H > 0 && a->N > 0 && a->N <= GV_ATTN_STREAM_MAX_N, GV_E_SHAPE,
-               "gv_attention_fwd_stream: need n_img > 0, H > 0, 0 < N <= %d (got N = %d)", GV_ATTN_STREAM_MAX_N, a->N);
+    if (int rc = attn_check("gv_attention_fwd_stream", a, a && a->qkv && a->o && a->lse, GV_ATTN_STREAM_MAX_N, true)) return rc;
     // the running max is taken over the raw scores and alpha = exp2((-inf - m') c) must be 0 on the first block: both need c > 0
     GV_REQUIRE(a->scale > 0.f, GV_E_SHAPE, "gv_attention_fwd_stream: scale must be > 0 (got %g)", (double)a->scale);
-    GV_REQUIRE(gv_aligned(a->qkv, 16) && gv_aligned(a->o, 16), GV_E_ALIGN, "gv_attention_fwd_stream: qkv/o must be 16-byte aligned");
-    // q_limit: whole query blocks that hold a row < q_limit
-    const int qe = (a->q_limit > 0 && a->q_limit < a->N) ? a->q_limit : a->N;
-    const int nqb = (qe + SQB - 1) / SQB;
-    const long blocks = (long)a->n_img * a->H * nqb;
-    GV_REQUIRE(blocks <= 0x7fffffffL, GV_E_SHAPE, "gv_attention_fwd_stream: n_img * H * query blocks = %ld exceeds the grid", blocks);
+    if (int rc = attn_aligned("gv_attention_fwd_stream", "qkv/o", {a->qkv, a->o})) return rc;
+    const gvattn::Launch l = S::launch(a->n_img, a->H, a->N, a->q_limit);
+    GV_REQUIRE(l.grid <= 0x7fffffffL, GV_E_SHAPE, "gv_attention_fwd_stream: n_img * H * query blocks = %ld exceeds the grid", l.grid);
     static GvLdsOptIn opt_in;
-    if (int rc = gv_lds_opt_in(opt_in, (const void*)attn_fwd_stream_kernel, SLDS, "gv_attention_fwd_stream")) return rc;
-    hipLaunchKernelGGL(attn_fwd_stream_kernel, dim3((unsigned)blocks), dim3(SNW * 64), SLDS, (hipStream_t)stream, *a, nqb);
+    if (int rc = gv_lds_opt_in(opt_in, (const void*)attn_fwd_stream_kernel, l.lds_bytes, "gv_attention_fwd_stream")) return rc;
+    hipLaunchKernelGGL(attn_fwd_stream_kernel, dim3((unsigned)l.grid), dim3(l.block), l.lds_bytes, (hipStream_t)stream, *a, S::query_blocks(a->N, a->q_limit));
     GV_LAUNCH_CHECK("gv_attention_fwd_stream");
     return GV_OK;
 }

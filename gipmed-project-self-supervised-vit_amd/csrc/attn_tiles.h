@@ -1,4 +1,5 @@
-// The attention kernels' common LDS image and fragment helpers (attention.hip, attention_stream.hip).
+// The attention kernels' common LDS image and fragment helpers, and their entry points' common checks (attention.hip,
+// attention_stream.hip; both include attn_plan.h first).
 //
 // LDS image: [rows = tokens][64 d] bf16, 128-B rows, 16-B chunk index XOR (row & 7).  Filled by LDS-DMA with the swizzle on
 // the per-lane SOURCE address.  The same image serves k-contiguous fragment reads (ds_read_b128) and hardware-transposed
@@ -6,6 +7,21 @@
 //
 // Included inside each file's anonymous namespace: every translation unit has its own copy (and its own zero page).
 #pragma once
+#include <initializer_list>
+
+// What every entry point checks first, in the order it always has: pointers, then the shape against the limit `max_n` of
+// include/gipvit.h.  full_text: the wording of gv_attention_probs and gv_attention_fwd_stream, which name every condition.
+template <class A> int attn_check(const char* name, const A* a, bool pointers_ok, int max_n, bool full_text) {
+    GV_REQUIRE(pointers_ok, GV_E_NULL, "%s: null pointer", name);
+    GV_REQUIRE(gvattn::shape_ok(a->n_img, a->H, a->N, max_n), GV_E_SHAPE,
+               full_text ? "%s: need n_img > 0, H > 0, 0 < N <= %d (got N = %d)" : "%s: need 0 < N <= %d (got %d)", name, max_n, a->N);
+    return GV_OK;
+}
+// ... and last: the buffers the kernels read and write in 16-byte pieces
+inline int attn_aligned(const char* name, const char* what, std::initializer_list<const void*> buffers) {
+    for (const void* p : buffers) GV_REQUIRE(gv_aligned(p, 16), GV_E_ALIGN, "%s: %s must be 16-byte aligned", name, what);
+    return GV_OK;
+}
 
 __device__ __attribute__((aligned(256))) unsigned short attn_zero_page[128];
 

@@ -179,7 +179,8 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(LinP p) {
 // takes one row at a time: lane j holds the score against row j (+64, +128 ...), a per-wave LDS strip hands the
 // 64-lane result back as a broadcast operand for the second product.  Softmax statistics are exact (expf, logf).
 // ------------------------------------------------------------------------------------------------
-constexpr int ALD = 65, AMAXC = 5, AMAXN = 260;
+constexpr int ALD = 65, AMAXC = 5;
+static_assert(GV_ATTN_F32_MAX_N <= 64 * AMAXC, "a lane holds one score per 64-row chunk");
 
 __device__ __forceinline__ void stage_rows(float* dst, const float* __restrict__ src, long ld, int N) {
     for (int e = threadIdx.x; e < N * 16; e += 256) {
@@ -474,7 +475,7 @@ extern "C" int gv_linear_f32(const gv_linear_args* a, void* stream) {
 
 extern "C" int gv_attention_fwd_f32(const gv_attention_fwd_args* a, void* stream) {
     GV_REQUIRE(a && a->qkv && a->o && a->lse, GV_E_NULL, "gv_attention_fwd_f32: null pointer");
-    GV_REQUIRE(a->n_img > 0 && a->H > 0 && a->N > 0 && a->N <= AMAXN, GV_E_SHAPE, "gv_attention_fwd_f32: need 0 < N <= %d (got %d)", AMAXN, a->N);
+    GV_REQUIRE(a->n_img > 0 && a->H > 0 && a->N > 0 && a->N <= GV_ATTN_F32_MAX_N, GV_E_SHAPE, "gv_attention_fwd_f32: need 0 < N <= %d (got %d)", GV_ATTN_F32_MAX_N, a->N);
     GV_REQUIRE(gv_aligned(a->qkv, 16) && gv_aligned(a->o, 16), GV_E_ALIGN, "gv_attention_fwd_f32: qkv/o must be 16-byte aligned");
     const int NP = ((a->N + 63) / 64) * 64, lds = (2 * a->N * ALD + 4 * NP + 4 * 64) * 4;
     int rc = set_lds(attn_fwd_f32_kernel, lds, "gv_attention_fwd_f32");
@@ -486,7 +487,7 @@ extern "C" int gv_attention_fwd_f32(const gv_attention_fwd_args* a, void* stream
 
 extern "C" int gv_attention_bwd_f32(const gv_attention_bwd_args* a, void* stream) {
     GV_REQUIRE(a && a->qkv && a->o && a->d_o && a->lse && a->dqkv, GV_E_NULL, "gv_attention_bwd_f32: null pointer");
-    GV_REQUIRE(a->n_img > 0 && a->H > 0 && a->N > 0 && a->N <= AMAXN, GV_E_SHAPE, "gv_attention_bwd_f32: need 0 < N <= %d (got %d)", AMAXN, a->N);
+    GV_REQUIRE(a->n_img > 0 && a->H > 0 && a->N > 0 && a->N <= GV_ATTN_F32_MAX_N, GV_E_SHAPE, "gv_attention_bwd_f32: need 0 < N <= %d (got %d)", GV_ATTN_F32_MAX_N, a->N);
     GV_REQUIRE(gv_aligned(a->qkv, 16) && gv_aligned(a->o, 16) && gv_aligned(a->d_o, 16) && gv_aligned(a->dqkv, 16), GV_E_ALIGN,
                "gv_attention_bwd_f32: buffers must be 16-byte aligned");
     const int NP = ((a->N + 63) / 64) * 64;
@@ -504,7 +505,7 @@ extern "C" int gv_attention_bwd_f32(const gv_attention_bwd_args* a, void* stream
 
 extern "C" int gv_attention_probs_f32(const gv_attention_probs_args* a, void* stream) {
     GV_REQUIRE(a && a->qkv && a->lse && a->p, GV_E_NULL, "gv_attention_probs_f32: null pointer");
-    GV_REQUIRE(a->n_img > 0 && a->H > 0 && a->N > 0 && a->N <= AMAXN, GV_E_SHAPE, "gv_attention_probs_f32: need n_img > 0, H > 0, 0 < N <= %d (got N = %d)", AMAXN, a->N);
+    GV_REQUIRE(a->n_img > 0 && a->H > 0 && a->N > 0 && a->N <= GV_ATTN_F32_MAX_N, GV_E_SHAPE, "gv_attention_probs_f32: need n_img > 0, H > 0, 0 < N <= %d (got N = %d)", GV_ATTN_F32_MAX_N, a->N);
     GV_REQUIRE(a->q_rows >= 1 && a->q_rows <= a->N, GV_E_SHAPE, "gv_attention_probs_f32: need 1 <= q_rows <= N (got q_rows = %d, N = %d)", a->q_rows, a->N);
     GV_REQUIRE(gv_aligned(a->qkv, 16), GV_E_ALIGN, "gv_attention_probs_f32: qkv must be 16-byte aligned");
     const int lds = (a->N * ALD + 4 * 64) * 4;

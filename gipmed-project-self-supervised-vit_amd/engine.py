@@ -572,7 +572,7 @@ class VitRunner:
                 # launch's half-empty last round); GIPVIT_VARLEN_ATTN=0 keeps one launch per segment for A/B runs
                 ops.attention_fwd_varlen(G.qkv[s], G.o[s], [(sg.n_img, sg.N, sg.lse[s]) for sg in G.segs], H, self.scale, q_limit=ql)
             else:
-                # a segment past one workgroup's LDS (N > 288: tiles above 256 px) streams K / V instead (gv_attention_fwd_stream)
+                # a segment past one workgroup's LDS (N > GV_ATTN_MAX_N: tiles above 256 px) streams K / V instead (gv_attention_fwd_stream)
                 for sg in G.segs:
                     attn_fwd = ops.attention_fwd_stream if sg.N > L.GV_ATTN_MAX_N else ops.attention_fwd
                     attn_fwd(sg.rows(G.qkv[s]), sg.n_img, sg.N, H, self.scale, o=sg.rows(G.o[s]), lse=sg.lse[s], q_limit=ql)
@@ -1479,9 +1479,6 @@ class SupervisedEngine(TrainEngine):
 # --------------------------------------------------------------------------- #
 # forward-only encoder: slide-level inference / feature extraction
 # --------------------------------------------------------------------------- #
-F32_ATTN_MAX_N = 260       # gv_attention_fwd_f32 / gv_attention_bwd_f32 (csrc/f32path.hip)
-
-
 class FeatureExtractor:
     """The encoder run forward-only on the same kernels: per-tile CLS features (what the reference's
     ``validate()`` writes to ``<slide>_features.pt``, train.py:1281-1282) and, with a classifier head,
@@ -1503,9 +1500,9 @@ class FeatureExtractor:
         n_tok = (img_size // 16) ** 2 + 1
         if img_size % 16 or not 16 <= img_size or n_tok > L.GV_ATTN_STREAM_MAX_N:
             raise ValueError(f"img_size {img_size}: a multiple of 16 up to 512 ({L.GV_ATTN_STREAM_MAX_N} tokens, gv_attention_fwd_stream)")
-        if fp32 and n_tok > F32_ATTN_MAX_N:
+        if fp32 and n_tok > L.GV_ATTN_F32_MAX_N:
             raise ValueError(f"precision='fp32' with img_size {img_size}: {n_tok} tokens per image, the fp32 operand mode's attention "
-                             f"stops at {F32_ATTN_MAX_N} (256-px images); larger images run in the 16-bit mode")
+                             f"stops at {L.GV_ATTN_F32_MAX_N} (256-px images); larger images run in the 16-bit mode")
         dev = torch.device(device)
         self.dev, self.arch, self.B, self.img, self.C = dev, arch, batch, img_size, num_classes
         self.D = ARCHS[arch]["embed_dim"]

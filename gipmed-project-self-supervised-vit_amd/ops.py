@@ -308,31 +308,31 @@ def linear_dw_group(problems, K: int, workspace):
     L.call("gv_linear_dw_group", a, _stream())
 
 
-def attention_fwd(qkv, n_img: int, N: int, H: int, scale: float, o=None, lse=None, q_limit: int = 0):
+def _attention_fwd(name, entry, qkv, n_img, N, H, scale, o, lse, q_limit):
+    """attention_fwd / attention_fwd_stream: the same buffers and argument struct through the entry point ``entry``"""
     dev = qkv.device
     o = torch.empty(n_img * N, H * 64, dtype=qkv.dtype, device=dev) if o is None else o
     lse = torch.empty(n_img, H, N, dtype=f32, device=dev) if lse is None else lse
     a = L.gv_attention_fwd_args(qkv.data_ptr(), o.data_ptr(), lse.data_ptr(), n_img, N, H, scale, q_limit)
     if o.dtype != qkv.dtype:
-        raise TypeError(f"attention_fwd: qkv is {qkv.dtype} but o is {o.dtype}")
-    L.call("gv_attention_fwd" + _sfx(qkv), a, _stream())
+        raise TypeError(f"{name}: qkv is {qkv.dtype} but o is {o.dtype}")
+    L.call(entry, a, _stream())
     return o, lse
+
+
+def attention_fwd(qkv, n_img: int, N: int, H: int, scale: float, o=None, lse=None, q_limit: int = 0):
+    return _attention_fwd("attention_fwd", "gv_attention_fwd" + _sfx(qkv), qkv, n_img, N, H, scale, o, lse, q_limit)
 
 
 def attention_fwd_stream(qkv, n_img: int, N: int, H: int, scale: float, o=None, lse=None, q_limit: int = 0):
     """``attention_fwd`` for N up to ``_lib.GV_ATTN_STREAM_MAX_N`` tokens (gv_attention_fwd_stream: K / V streamed through LDS under
-    an online softmax).  Forward only and 16-bit only: the fp32 operand mode keeps its N <= 260.  ``q_limit`` > 0: whole blocks of
-    ``_lib.GV_ATTN_STREAM_QBLOCK`` query rows that hold a row < q_limit are computed, o / lse behind them are left untouched."""
-    dev = qkv.device
+    an online softmax).  Forward only and 16-bit only: the fp32 operand mode keeps its ``_lib.GV_ATTN_F32_MAX_N``.  ``q_limit`` > 0:
+    whole blocks of ``_lib.GV_ATTN_STREAM_QBLOCK`` query rows that hold a row < q_limit are computed, o / lse behind them are left
+    untouched."""
     if qkv.dtype != bf16:
-        raise TypeError(f"attention_fwd_stream: qkv must be {bf16}, got {qkv.dtype} (there is no fp32 operand form: that mode stops at N = 260)")
-    o = torch.empty(n_img * N, H * 64, dtype=qkv.dtype, device=dev) if o is None else o
-    lse = torch.empty(n_img, H, N, dtype=f32, device=dev) if lse is None else lse
-    a = L.gv_attention_fwd_args(qkv.data_ptr(), o.data_ptr(), lse.data_ptr(), n_img, N, H, scale, q_limit)
-    if o.dtype != qkv.dtype:
-        raise TypeError(f"attention_fwd_stream: qkv is {qkv.dtype} but o is {o.dtype}")
-    L.call("gv_attention_fwd_stream", a, _stream())
-    return o, lse
+        raise TypeError(f"attention_fwd_stream: qkv must be {bf16}, got {qkv.dtype} (there is no fp32 operand form: that mode stops at "
+                        f"N = {L.GV_ATTN_F32_MAX_N})")
+    return _attention_fwd("attention_fwd_stream", "gv_attention_fwd_stream", qkv, n_img, N, H, scale, o, lse, q_limit)
 
 
 def attention_probs(qkv, lse, n_img: int, N: int, H: int, scale: float, q_rows: int, p=None):
@@ -352,27 +352,36 @@ def attention_probs(qkv, lse, n_img: int, N: int, H: int, scale: float, q_rows: 
     return p
 
 
-def attention_fwd_varlen(qkv, o, segments, H: int, scale: float, q_limit: int = 0):
-    """All segments of a token-concatenated row space in one call: ``segments`` = [(n_img, N, lse f32 [n_img, H, N]), ...] in row
-    order; qkv [T, 3 H 64], o [T, H 64].  bf16: gv_attention_fwd_varlen (a long + a short segment share ONE launch); the fp32
-    operand mode runs one call per segment."""
-    if qkv.dtype != bf16 or len(segments) > L.GV_ATTN_MAX_SEG:
-        row = 0
-        for n_img, N, lse in segments:
-            attention_fwd(qkv[row:row + n_img * N], n_img, N, H, scale, o=o[row:row + n_img * N], lse=lse, q_limit=q_limit)
-            row += n_img * N
-        return
-    if o.dtype != qkv.dtype:
-        raise TypeError(f"attention_fwd_varlen: qkv is {qkv.dtype} but o is {o.dtype}")
-    a = L.gv_attention_fwd_varlen_args()
-    a.qkv, a.o, a.n_seg, a.H, a.scale, a.q_limit = qkv.data_ptr(), o.data_ptr(), len(segments), H, scale, q_limit
+def _varlen(entry, a, fields, segments, H, scale, q_limit, per_segment, mismatch):
+    """attention_fwd_varlen / attention_bwd_varlen.  ``a``: the entry point's argument struct, ``fields``: its buffers {field: tensor},
+    qkv first.  f32 operands, or a table past GV_ATTN_MAX_SEG: ``per_segment(row slice, n_img, N, lse)`` for every segment."""
+    bufs = list(fields.values())
     rows = 0
+    if bufs[0].dtype != bf16 or len(segments) > L.GV_ATTN_MAX_SEG:
+        for n_img, N, lse in segments:
+            per_segment(slice(rows, rows + n_img * N), n_img, N, lse)
+            rows += n_img * N
+        return
+    if any(t.dtype != bufs[0].dtype for t in bufs):
+        raise TypeError(mismatch)
+    for k, t in fields.items():
+        setattr(a, k, t.data_ptr())
+    a.n_seg, a.H, a.scale, a.q_limit = len(segments), H, scale, q_limit
     for i, (n_img, N, lse) in enumerate(segments):
         assert lse.dtype == f32 and lse.numel() >= n_img * H * N
         a.n_img[i], a.N[i], a.lse[i] = n_img, N, lse.data_ptr()
         rows += n_img * N
-    assert qkv.shape[0] >= rows and o.shape[0] >= rows and qkv.is_contiguous() and o.is_contiguous()
-    L.call("gv_attention_fwd_varlen", a, _stream())
+    assert all(t.shape[0] >= rows and t.is_contiguous() for t in bufs)
+    L.call(entry, a, _stream())
+
+
+def attention_fwd_varlen(qkv, o, segments, H: int, scale: float, q_limit: int = 0):
+    """All segments of a token-concatenated row space in one call: ``segments`` = [(n_img, N, lse f32 [n_img, H, N]), ...] in row
+    order; qkv [T, 3 H 64], o [T, H 64].  bf16: gv_attention_fwd_varlen (a long + a short segment share ONE launch); the fp32
+    operand mode runs one call per segment."""
+    _varlen("gv_attention_fwd_varlen", L.gv_attention_fwd_varlen_args(), dict(qkv=qkv, o=o), segments, H, scale, q_limit,
+            lambda r, n_img, N, lse: attention_fwd(qkv[r], n_img, N, H, scale, o=o[r], lse=lse, q_limit=q_limit),
+            f"attention_fwd_varlen: qkv is {qkv.dtype} but o is {o.dtype}")
 
 
 def attention_bwd(qkv, o, d_o, lse, n_img: int, N: int, H: int, scale: float, dqkv=None, q_limit: int = 0):
@@ -389,25 +398,9 @@ def attention_bwd_varlen(qkv, o, d_o, dqkv, segments, H: int, scale: float, q_li
     """Backward of all segments of a token-concatenated row space in one call: ``segments`` = [(n_img, N, lse), ...] as for
     attention_fwd_varlen; qkv / dqkv [T, 3 H 64], o / d_o [T, H 64].  bf16: gv_attention_bwd_varlen; the fp32 operand mode runs
     one call per segment."""
-    if qkv.dtype != bf16 or len(segments) > L.GV_ATTN_MAX_SEG:
-        row = 0
-        for n_img, N, lse in segments:
-            r = slice(row, row + n_img * N)
-            attention_bwd(qkv[r], o[r], d_o[r], lse, n_img, N, H, scale, dqkv=dqkv[r], q_limit=q_limit)
-            row += n_img * N
-        return dqkv
-    if not (o.dtype == d_o.dtype == dqkv.dtype == qkv.dtype):
-        raise TypeError("attention_bwd_varlen: qkv / o / d_o / dqkv must share one dtype")
-    a = L.gv_attention_bwd_varlen_args()
-    a.qkv, a.o, a.d_o, a.dqkv, a.n_seg, a.H, a.scale = qkv.data_ptr(), o.data_ptr(), d_o.data_ptr(), dqkv.data_ptr(), len(segments), H, scale
-    a.q_limit = q_limit
-    rows = 0
-    for i, (n_img, N, lse) in enumerate(segments):
-        assert lse.dtype == f32 and lse.numel() >= n_img * H * N
-        a.n_img[i], a.N[i], a.lse[i] = n_img, N, lse.data_ptr()
-        rows += n_img * N
-    assert all(t.shape[0] >= rows and t.is_contiguous() for t in (qkv, o, d_o, dqkv))
-    L.call("gv_attention_bwd_varlen", a, _stream())
+    _varlen("gv_attention_bwd_varlen", L.gv_attention_bwd_varlen_args(), dict(qkv=qkv, o=o, d_o=d_o, dqkv=dqkv), segments, H, scale, q_limit,
+            lambda r, n_img, N, lse: attention_bwd(qkv[r], o[r], d_o[r], lse, n_img, N, H, scale, dqkv=dqkv[r], q_limit=q_limit),
+            "attention_bwd_varlen: qkv / o / d_o / dqkv must share one dtype")
     return dqkv
 
 

@@ -446,7 +446,8 @@ int gv_expand_rows(const gv_expand_rows_args* a, void* stream);
 /* ---- attention (vit.pyc@L119-131): softmax(q k^T * scale) v per (image, head)
  * on packed qkv bf16 [n_img*N, 3, H, 64] -> o bf16 [n_img*N, H, 64];
  * lse f32 [n_img, H, N] (natural-log sum-exp of the scaled scores).
- * head_dim is fixed at 64 (ViT-T/S/B); N <= 288.                            */
+ * head_dim is fixed at 64 (ViT-T/S/B); N <= GV_ATTN_MAX_N (a whole sequence
+ * sits in one workgroup's LDS; the _f32 entry points: N <= GV_ATTN_F32_MAX_N). */
 typedef struct {
     const void* qkv; void* o; float* lse;
     int32_t n_img, N, H; float scale;
@@ -456,7 +457,7 @@ typedef struct {
 } gv_attention_fwd_args;
 int gv_attention_fwd(const gv_attention_fwd_args* a, void* stream);
 
-/* Streaming forward for sequences past the N <= 288 of gv_attention_fwd (tiles up to 512 px at patch 16: 1 025 tokens).  Inputs and
+/* Streaming forward for sequences past the GV_ATTN_MAX_N of gv_attention_fwd (tiles up to 512 px at patch 16: 1 025 tokens).  Inputs and
  * outputs are those of gv_attention_fwd -- qkv 16-bit [n_img*N, 3, H, 64], o 16-bit [n_img*N, H, 64], lse f32 [n_img, H, N] (the
  * natural-log sum-exp of the scaled scores), head_dim 64 -- for 1 <= N <= GV_ATTN_STREAM_MAX_N (65 key tiles of 16); any other N
  * returns GV_E_SHAPE with the limit in gv_last_error(), a null pointer GV_E_NULL, both before any launch.  scale must be > 0
@@ -469,6 +470,8 @@ int gv_attention_fwd(const gv_attention_fwd_args* a, void* stream);
  * No atomics: the result of an (image, head) pair depends neither on the launch geometry nor on the other pairs of the launch.
  * One plain launch (no cooperative launch, nothing waits on another workgroup), 32 KB of LDS.  There is no backward and no _f32
  * form: training, attention maps (gv_attention_probs) and the fp32 operand mode keep their limits.                              */
+#define GV_ATTN_MAX_N 288            /* gv_attention_fwd / _bwd / _probs and the varlen calls */
+#define GV_ATTN_F32_MAX_N 260        /* the _f32 entry points */
 #define GV_ATTN_STREAM_MAX_N 1040
 #define GV_ATTN_STREAM_QBLOCK 128
 int gv_attention_fwd_stream(const gv_attention_fwd_args* a, void* stream);
@@ -518,7 +521,8 @@ int gv_attention_bwd_varlen(const gv_attention_bwd_varlen_args* a, void* stream)
  *     p[img, h, q, key] = exp(scale * q.k - lse[img, h, q])     for q < q_rows, key < N
  * so P is exactly the softmax that produced o (one pass, no row reduction).  p is compact and need not be aligned: at N = 257 a
  * row is 1 028 bytes.  q_rows = 1 is the CLS row (a forward with q_limit = 1 leaves lse valid for it); q_rows = N needs a
- * forward with q_limit = 0.  N <= 288, head_dim 64 (the _f32 entry point: N <= 260, every 16-bit buffer as f32).            */
+ * forward with q_limit = 0.  N <= GV_ATTN_MAX_N, head_dim 64 (the _f32 entry point: N <= GV_ATTN_F32_MAX_N, every 16-bit buffer
+ * as f32).                                                                                                                   */
 typedef struct {
     const void*  qkv;   /* 16-bit [n_img*N, 3, H, 64], as gv_attention_fwd read it                          */
     const float* lse;   /* f32 [n_img, H, N], as gv_attention_fwd left it: rows [0, q_rows) must be valid */
@@ -801,7 +805,7 @@ int gv_lamb(const gv_lamb_args* a, void* stream);
  * GEMM operands incl. the weights, aux_in / aux_out, attention q/k/v/o/dO/dqkv, LayerNorm y / dy / gb, patch rows);
  * f32 fields keep their meaning.  Linear: v_mfma_f32_16x16x4_f32, any M / N / K, exact erf GELU and GELU', c_is_f32
  * must be 1, workspace ignored (pure-ACCUM launches with few output tiles split K through f32 atomics).
- * Attention: N <= 260.  A parity mode: it holds the 1e-4 logits / loss and 1e-3 gradient-norm gates against the fp32
+ * Attention: N <= GV_ATTN_F32_MAX_N.  A parity mode: it holds the 1e-4 logits / loss and 1e-3 gradient-norm gates against the fp32
  * oracle (tests/test_fp32_gpu.py); the training path stays bf16.                                                   */
 int gv_linear_f32(const gv_linear_args* a, void* stream);
 int gv_attention_fwd_f32(const gv_attention_fwd_args* a, void* stream);

@@ -182,6 +182,34 @@ def test_probe_varlen(dev, probe, n_long, n_short, order):
         CHECKS[probe](got, case)
 
 
+@pytest.mark.parametrize("n_a,n_b", [(128, 64), (225, 64), (224, 32), (224, 65)])
+def test_varlen_just_outside_the_fused_window(dev, n_a, n_b):
+    """Two segments one token class off the long + short pair that shares a launch (csrc/attn_plan.h VarlenCfg::fuses): the call
+    runs one launch per segment, so o and lse of ONE gv_attention_fwd_varlen call equal the per-segment gv_attention_fwd calls bit
+    for bit -- and at (225, 64) dqkv of one gv_attention_bwd_varlen call the per-segment gv_attention_bwd calls.  Probe A, 3 x 3
+    pairs per segment (every N here is held to probe A's own checks by test_probe)."""
+    o = ops()
+    segs = [Segment(dev, build("A", N), N_IMG, H, bf16) for N in (n_a, n_b)]
+    T = sum(s.n_img * s.N for s in segs)
+    qkv, d_o = torch.cat([s.qkv for s in segs]), torch.cat([s.d_o for s in segs])
+    obuf, out = _guarded(T, H * 64, bf16, dev)
+    gbuf, dqkv = _guarded(T, 3 * H * 64, bf16, dev)
+    table = [(s.n_img, s.N, s.lse) for s in segs]
+    o.attention_fwd_varlen(qkv, out, table, H, SCALE)
+    if (n_a, n_b) == (225, 64):
+        o.attention_bwd_varlen(qkv, out, d_o, dqkv, table, H, SCALE)
+    _guards_untouched((obuf, out), (gbuf, dqkv), *[(s.lbuf, s.lse) for s in segs])
+    row = 0
+    for s in segs:
+        r = slice(row, row + s.n_img * s.N)
+        ref_o, ref_lse = o.attention_fwd(qkv[r], s.n_img, s.N, H, SCALE)
+        assert torch.equal(out[r], ref_o) and torch.equal(s.lse, ref_lse), f"forward, segment N={s.N}"
+        if (n_a, n_b) == (225, 64):
+            ref_g = o.attention_bwd(qkv[r], ref_o, d_o[r], ref_lse, s.n_img, s.N, H, SCALE)
+            assert torch.equal(dqkv[r], ref_g), f"backward, segment N={s.N}"
+        row = r.stop
+
+
 @pytest.mark.parametrize("N", [33, 225, 288])
 @pytest.mark.parametrize("ql", [1, 32, 33])
 def test_probe_q_limit(dev, ql, N):
