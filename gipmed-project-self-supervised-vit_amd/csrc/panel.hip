@@ -37,8 +37,9 @@ constexpr int IMG_STRIDE = PN + 4;          // f32 image row stride (+4: conflic
 // Geometry: NW = 8 waves, each 3 column fragments x FM row fragments, BK = 64, ONE workgroup per CU (ring 2 x (A + 48 KB)).
 // (A 4-wave, BK = 32 variant with two workgroups per CU -- one workgroup's HBM-bound epilogue under the other's k-loop -- is
 // expressible with the same template and was measured: 103 vs 87 us on the K = 1536 forward; not instantiated.)
-template <int FM, int NW_, int BK_>
+template <int FM_, int NW_, int BK_>
 struct PC {
+    static constexpr int FM = FM_, FMH = (FM + 1) / 2;      // 16-row fragments per workgroup; of the first ping-pong half
     static constexpr int NW = NW_, BK = BK_, KS = BK / 32, NF = 24 / NW;      // waves, k depth per stage, MFMA k-steps, column fragments per wave
     static constexpr int BM = FM * 16;
     static constexpr int RPP = 1024 / (BK * 2);             // rows per 1-KB piece of the A image
@@ -91,8 +92,73 @@ struct PanelP {
     const bf16* W2; long ldw2; const float* bias1; int hidden;
 };
 
-
 // MODE_* and the MODE_WIDE epilogues EP_*: linear_plan.h
+
+// The accumulators in the layout of the k-loop that fills them (one array, the other layout does not exist in the instantiation):
+//   one-stage-ahead: acc[i][j][r]: row m0 + 16 i + (lane & 15), column 16 (NW j + wave) + 4 (lane >> 4) + r
+//   PP: acc[b][i][j][r]: row m0 + 16 (wm FMH + i) + (lane & 15), column 128 b + 16 (2 wn + j) + 4 (lane >> 4) + r
+template <class C, int PP> using PanelAcc = std::conditional_t<PP != 0, f32x4[3][C::FMH][2], f32x4[C::FM][C::NF]>;
+
+// ---- the pieces of panel_kernel that live outside its body (__forceinline__: one kernel all the same).  The k-loops and the
+// epilogues are still inside it: profiles/panel_split.txt has what moving each of them did to the code objects.
+
+// MODE_WIDE (N = ncb x 384 output columns): a workgroup owns ONE 384-column block of the output and walks up to ncb
+// consecutive row panels with it; the ncb workgroups that walk the SAME panels (one per column block) are neighbours on
+// one XCD (workgroup ids go round-robin over the 8 XCDs: id & 7 is the XCD, id >> 3 the slot on it), so an A panel is
+// fetched from HBM once and its other ncb - 1 readers hit that XCD's L2 -- the XCD's working set is 32 / ncb panels
+// + the weights (~2.3 MB), where the round-2 mapping (one workgroup = one panel x all column blocks) re-read every panel
+// ncb times out of an L2 that 32 different panels (4.3 MB) had already left: 1.41 x the algorithmic traffic on fc1.
+struct WideWalk { int cb = 0, nit = 1, first_panel = 0; };      // column block; row panels this workgroup walks, the first one's index
+// the walk of workgroup blockIdx.x and its first panel's first row; false: the grid's padding, no panel is left for it
+template <class C>
+__device__ __forceinline__ bool wide_walk(const PanelP& p, WideWalk& w, int& m0) {
+    const int M = p.M;
+    // (integer division runs on the vector ALU: readfirstlane brings the uniform results back to scalar registers, or every
+    //  row address derived from m0 / cb would occupy vector registers this kernel does not have)
+    const int ncb_ = p.ncb, slot = blockIdx.x >> 3;
+    const int lg = __builtin_amdgcn_readfirstlane(slot / ncb_);
+    const int grp = lg * 8 + (blockIdx.x & 7);
+    w.cb = slot - lg * ncb_;
+    const int P = __builtin_amdgcn_readfirstlane((M + C::BM - 1) / C::BM), first = grp * ncb_;
+    if (first >= P) return false;                         // (whole workgroup: no barrier is pending)
+    w.nit = P - first < ncb_ ? P - first : ncb_;
+    w.first_panel = first;
+    m0 = first * C::BM;
+    m0 = m0 < M - C::BM ? m0 : M - C::BM;                 // the last panel is shifted back to end at row M (see panel_origin below)
+    return true;
+}
+// MODE_WIDE row panels: panel i starts at min(i BM, M - BM) -- every panel holds BM valid rows, so the per-lane source offsets
+// of the A pieces are the same for all panels (no clamp at M to recompute when the stream moves on to the next panel: that
+// cost 6 vector registers this kernel does not have -- spills whose reloads drained the counted DMA stream).  The rows the
+// last two panels share are computed twice, by the same arithmetic in the same order: bit-identical stores.  (The wide
+// epilogues are pure functions of the row; gv_panel_wide refuses out == resid for the one that reads what it overwrites.)
+template <class C>
+__device__ __forceinline__ int panel_origin(int idx, int M) { const int o = idx * C::BM; return o < M - C::BM ? o : M - C::BM; }
+
+// backward: column sums over this workgroup's rows, and their reduction over the waves -> partials[blockIdx][3][384]
+// (gv_ln_finalize folds them)
+struct ColSums { float dg[3][2], db[3][2], g[3][2]; };
+template <int NW>
+__device__ __forceinline__ void store_colsums(GV_LDS char* smem, int tid, int lane, int wave, float* partials, const ColSums& sums) {
+    GV_LDS float* red = (GV_LDS float*)smem;                  // [NW waves][3][384]
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int col = (c * 64 + lane) * 2 + e;
+            red[(wave * 3 + 0) * PN + col] = sums.dg[c][e];
+            red[(wave * 3 + 1) * PN + col] = sums.db[c][e];
+            red[(wave * 3 + 2) * PN + col] = sums.g[c][e];
+        }
+    __syncthreads();
+    float* outp = partials + (long)blockIdx.x * 3 * PN;
+    for (int idx = tid; idx < 3 * PN; idx += NW * 64) {
+        float s = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) s += red[w * 3 * PN + idx];
+        outp[idx] = s;
+    }
+}
 
 // PP = 1: the k-loop of gemm_dw8.h (ping-pong halves, three phases per 64-deep K-tile, counted LDS-DMA stream) instead of the
 // one-stage-ahead loop: waves (wm, wn) = (wave >> 2, wave & 3); the wm = 0 half owns the first FMH = ceil(FM / 2) row fragments,
@@ -106,46 +172,19 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
     // (+ bias + residual + the next LayerNorm): the hidden activation never exists in HBM.  See the k-loop below.
     constexpr bool MLP = MODE == MODE_FWD && EP == EP_MLP;
     static_assert(!MLP || (!PP && NW == 8 && BK == 64 && !TB && C::A_BYTES <= C::W_BLOCK), "fused MLP: one-stage-ahead loop, 8 waves, natural weights, <= 128 rows");
-    constexpr int FMH = (FM + 1) / 2;
+    static_assert(MODE != MODE_WIDE || PP, "MODE_WIDE runs on the ping-pong k-loop only (gv_panel_wide requires K % 128 == 0)");
+    constexpr int FMH = C::FMH;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     GV_LDS char* smem = (GV_LDS char*)smem_raw;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li16 = lane & 15, gq = lane >> 4;
     const int M = p.M;
-    // MODE_WIDE (N = ncb x 384 output columns): a workgroup owns ONE 384-column block of the output and walks up to ncb
-    // consecutive row panels with it; the ncb workgroups that walk the SAME panels (one per column block) are neighbours on
-    // one XCD (workgroup ids go round-robin over the 8 XCDs: id & 7 is the XCD, id >> 3 the slot on it), so an A panel is
-    // fetched from HBM once and its other ncb - 1 readers hit that XCD's L2 -- the XCD's working set is 32 / ncb panels
-    // + the weights (~2.3 MB), where the round-2 mapping (one workgroup = one panel x all column blocks) re-read every panel
-    // ncb times out of an L2 that 32 different panels (4.3 MB) had already left: 1.41 x the algorithmic traffic on fc1.
     int m0 = blockIdx.x * C::BM;
-    int cb = 0, nit = 1, first_panel = 0;                 // column block; row panels this workgroup walks, the first one's index
-    if constexpr (MODE == MODE_WIDE) {
-        // (integer division runs on the vector ALU: readfirstlane brings the uniform results back to scalar registers, or every
-        //  row address derived from m0 / cb would occupy vector registers this kernel does not have)
-        const int ncb_ = p.ncb, slot = blockIdx.x >> 3;
-        const int lg = __builtin_amdgcn_readfirstlane(slot / ncb_);
-        const int grp = lg * 8 + (blockIdx.x & 7);
-        cb = slot - lg * ncb_;
-        const int P = __builtin_amdgcn_readfirstlane((M + C::BM - 1) / C::BM), first = grp * ncb_;
-        if (first >= P) return;                           // (whole workgroup: no barrier is pending)
-        nit = P - first < ncb_ ? P - first : ncb_;
-        first_panel = first;
-        m0 = first * C::BM;
-        m0 = m0 < M - C::BM ? m0 : M - C::BM;             // the last panel is shifted back to end at row M (see panel_origin below)
-    }
-    // MODE_WIDE row panels: panel i starts at min(i BM, M - BM) -- every panel holds BM valid rows, so the per-lane source offsets
-    // of the A pieces are the same for all panels (no clamp at M to recompute when the stream moves on to the next panel: that
-    // cost 6 vector registers this kernel does not have -- spills whose reloads drained the counted DMA stream).  The rows the
-    // last two panels share are computed twice, by the same arithmetic in the same order: bit-identical stores.  (The wide
-    // epilogues are pure functions of the row; gv_panel_wide refuses out == resid for the one that reads what it overwrites.)
-    auto panel_origin = [&](int idx) { const int o = idx * C::BM; return o < M - C::BM ? o : M - C::BM; };
-
-    // acc[i][j][r]: row m0 + 16 i + (lane & 15), column 16 (NW j + wave) + 4 (lane >> 4) + r
-    f32x4 acc[PP ? 1 : FM][NF];
-    // PP: acc8[b][i][j][r]: row m0 + 16 (wm FMH + i) + (lane & 15), column 128 b + 16 (2 wn + j) + 4 (lane >> 4) + r
-    f32x4 acc8[PP ? 3 : 1][PP ? FMH : 1][2];
+    WideWalk walk;
+    if constexpr (MODE == MODE_WIDE) { if (!wide_walk<C>(p, walk, m0)) return; }
+    const int cb = walk.cb, nit = walk.nit, first_panel = walk.first_panel;
+    PanelAcc<C, PP> acc;
     const int wm = wave >> 2, wn = wave & 3;
     const int f0 = wm * FMH, nfr = wm == 0 ? FMH : FM - FMH;
 
@@ -181,8 +220,8 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
     // PP: LDS-DMA sources as uniform base (SGPRs) + per-lane 32-bit byte offset, as in gemm_dw8.h.  A image piece pc: rows
     // (wave a + pc) 8 .. + 7 (clamped at M), 128 B each, 16-B chunk XOR (row & 7); W block piece pc: natural -- weight rows
     // (wave 2 + pc) 8 .. + 7 of the block; transposed -- reduction rows (wave 2 + pc) 4 .. + 3, 256 B of the block's columns each
-    unsigned voffA[PP ? C::A_PPW : 1], voffW[2];
-    auto a_offsets = [&](unsigned (&vo)[PP ? C::A_PPW : 1], int origin) {      // per-lane byte offsets of a panel's A pieces from its first row
+    unsigned voffA[C::A_PPW], voffW[2];
+    auto a_offsets = [&](unsigned (&vo)[C::A_PPW], int origin) {      // per-lane byte offsets of a panel's A pieces from its first row
 #pragma unroll
         for (int pc = 0; pc < C::A_PPW; ++pc) {
             const int rr = (wave * C::A_PPW + pc) * 8 + (lane >> 3);
@@ -242,24 +281,21 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
     if constexpr (PP) static_for<0, PN_T>([&](auto X) { issue_x(X, 0, 0, baseA); });
     else if constexpr (MLP) mlp_issue1(0, 0, 0);
     else issue(0);
-    float s_dg[3][2], s_db[3][2], s_g[3][2];          // backward: column sums over this workgroup's rows
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int e = 0; e < 2; ++e) { s_dg[c][e] = 0.f; s_db[c][e] = 0.f; s_g[c][e] = 0.f; }
+    ColSums sums{};
     for (int it = 0; it < nit; ++it) {
     int m0_next = m0;
+    // (inline: as a function the ping-pong loop changed register or spill counts in 19 or more of the 52 kernels -- profiles/panel_split.txt)
     if constexpr (PP) {
         const bool has_next = MODE == MODE_WIDE && it + 1 < nit;
         uc_past = has_next ? 0 : nt - 1;
-        m0_next = has_next ? panel_origin(first_panel + it + 1) : m0;
+        m0_next = has_next ? panel_origin<C>(first_panel + it + 1, M) : m0;
         baseA_past = (unsigned long long)(p.A + (long)m0_next * p.lda);
 #pragma unroll
         for (int b = 0; b < 3; ++b)
 #pragma unroll
             for (int i = 0; i < FMH; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc8[b][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int j = 0; j < 2; ++j) acc[b][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         // prologue: tile 0 is out (start of the kernel / before the previous block's epilogue); A, W0, W1 of tile 1 follow
         static_for<0, PA + 4>([&](auto X) { issue_x(X, 1, 1, baseA); });
         wait_vmcnt<PN_T + 2>();                               // A and W0 of tile 0 landed
@@ -320,7 +356,7 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
 #pragma unroll
                 for (int i = 0; i < FMH; ++i)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) acc8[J][i][j] = GV_MFMA_16x16x32(fb[ks][j], fa[ks][i], acc8[J][i][j]);
+                    for (int j = 0; j < 2; ++j) acc[J][i][j] = GV_MFMA_16x16x32(fb[ks][j], fa[ks][i], acc[J][i][j]);
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();
@@ -343,6 +379,7 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
 #pragma unroll
         for (int j = 0; j < NF; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
+    // (inline: as a function the fused-MLP loops changed the SGPR count of one of their two kernels, the wait counts of both -- profiles/panel_split.txt)
     if constexpr (MLP) {
         // Per chunk c of 256 hidden columns: fc1 over K (nt stages; wave w owns the chunk's column fragments {w, w + 8}) -> + bias1,
         // GELU, bf16 -> H in LDS -> fc2 over the chunk (4 stages; wave w owns output fragments {w, w + 8, w + 16} as in the plain
@@ -408,6 +445,7 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
             }
         }
     }
+    // (inline: as a function this loop changed the wait-count order of three kernels -- profiles/panel_split.txt)
     if constexpr (!PP && !MLP) for (int t = 0; t < nt; ++t) {
         wait_vmcnt<0>();                      // my pieces of stage t have landed (nothing younger is in flight yet)
         __builtin_amdgcn_s_barrier();         // everybody's have; every wave is past its reads of stage t - 1
@@ -437,6 +475,7 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
     // Round 2 ran the wide epilogues on the LayerNorm kernels' scheme -- a workgroup-wide image, one wave per 768-B row, two
     // barriers per 32 rows: 8 us per 176 x 384 panel with NO global store in it (a lab build without stores), as long as
     // the panel's k-loop.  Nothing here needs a whole row in one wave, so nothing needs the other waves.
+    // (inline: as a function the wide epilogue changed the wait counts of two kernels, FM = 4 / 7 with EP_BIAS -- profiles/panel_split.txt)
     if constexpr (MODE == MODE_WIDE) {
         constexpr int RS = 100;
         static_assert(C::STAGE + NW * 16 * RS * 4 <= C::LDS_WIDE, "per-wave images must fit behind ring stage 0");
@@ -487,7 +526,7 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
                 for (int b = 0; b < 3; ++b)
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        f32x4 v = acc8[b][i][j];
+                        f32x4 v = acc[b][i][j];
                         if constexpr (WB) v += bw[b][j];
                         *(GV_LDS f32x4*)(wimg + li16e * RS + 32 * b + 16 * j + gqe * 4) = v;
                     }
@@ -516,6 +555,8 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
         });
         __syncthreads();                                          // images are read: stage 1 may receive the next panel's tile 1
     }
+    // (inline: as a function the row epilogues changed register counts in 12 of the 52 kernels, wait counts in 14 -- profiles/panel_split.txt)
+    if constexpr (MODE != MODE_WIDE) {
     // ---- epilogue (FWD / BWD).  The accumulators pass through an LDS image so that the row phase works on whole rows, ONE WAVE PER
     // ROW (wave w: rows w, w + 8, .. of the pass): every global access is a full 512-B row segment and the row reductions
     // of the LayerNorm stay inside a wave.  The global rows a pass needs (forward: the residual; backward: x and g, mean,
@@ -528,19 +569,19 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
     static_assert(!PP || IB * 16 * IMG_STRIDE * 4 + (MODE == MODE_WIDE ? C::STAGE : 0) <= (MODE == MODE_WIDE ? C::LDS_WIDE : C::LDS), "PP image");
     constexpr int RPW = 16 * IB / NW;                             // rows per wave and pass
     GV_LDS float* img = (GV_LDS float*)(smem + (MODE == MODE_WIDE ? C::STAGE : 0));
-    constexpr bool HAS_BIAS = MODE == MODE_FWD || (MODE == MODE_WIDE && ((EP >= EP_BIAS && EP <= EP_BIAS_GELU_SAVE) || EP == EP_BIAS_RESID));
-    f32x4 bias4[NF], bias8[3][2];
-    if constexpr (HAS_BIAS) {
-#pragma unroll
-        for (int j = 0; j < NF; ++j)
-            bias4[j] = p.bias ? *(const f32x4*)(p.bias + cb * PN + 16 * (NW * j + wave) + gq * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+    constexpr bool HAS_BIAS = MODE == MODE_FWD;
+    std::conditional_t<PP != 0, f32x4[3][2], f32x4[NF]> bias;         // (the layout of acc's columns)
+    if constexpr (HAS_BIAS && PP) {
 #pragma unroll
         for (int b = 0; b < 3; ++b)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
-                bias8[b][j] = (PP && p.bias) ? *(const f32x4*)(p.bias + cb * PN + 128 * b + 16 * (2 * wn + j) + gq * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+                bias[b][j] = p.bias ? *(const f32x4*)(p.bias + cb * PN + 128 * b + 16 * (2 * wn + j) + gq * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+    } else if constexpr (HAS_BIAS) {
+#pragma unroll
+        for (int j = 0; j < NF; ++j)
+            bias[j] = p.bias ? *(const f32x4*)(p.bias + cb * PN + 16 * (NW * j + wave) + gq * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    static_assert(MODE != MODE_WIDE || PP, "MODE_WIDE runs on the ping-pong k-loop only (gv_panel_wide requires K % 128 == 0)");
     // per-lane column constants of the row phase: lane owns columns (c * 64 + lane) * 2 + {0, 1}, c = 0..2
     float gm[3][2], bt[3][2];
     const bool ln = MODE == MODE_BWD || (MODE == MODE_FWD && p.gamma != nullptr);
@@ -565,7 +606,6 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
         const int slot = rr >> 1, h = slot / IBH, ii = slot % IBH;
         return 16 * (h * FMH + i0 + ii) + 8 * (rr & 1);
     };
-    if constexpr (MODE != MODE_WIDE) {
     // The row phase is HBM-bound (s_memtime stamps of a lab build: forward 170 MB, backward 237 MB per launch at 5.6 - 5.9 TB/s, as long
     // as the k-loop).  Requesting pass p + 1's rows ahead of pass p's stores was measured and changes nothing (LAB_NOTES.md).
     constexpr int PSTEP = PP ? IBH : IB, NPASS = ((PP ? FMH : FM) + PSTEP - 1) / PSTEP;
@@ -608,8 +648,8 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
                     for (int b = 0; b < 3; ++b)
 #pragma unroll
                         for (int j = 0; j < 2; ++j) {
-                            f32x4 v = acc8[b][i][j];
-                            if constexpr (HAS_BIAS) v += bias8[b][j];
+                            f32x4 v = acc[b][i][j];
+                            if constexpr (HAS_BIAS) v += bias[b][j];
                             *(GV_LDS f32x4*)(img + ((wm * IBH + i - i0) * 16 + li16) * IMG_STRIDE + 128 * b + 16 * (2 * wn + j) + gq * 4) = v;
                         }
                 }
@@ -621,7 +661,7 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
 #pragma unroll
                     for (int j = 0; j < NF; ++j) {
                         f32x4 v = acc[i0 + ii][j];
-                        if constexpr (HAS_BIAS) v += bias4[j];
+                        if constexpr (HAS_BIAS) v += bias[j];
                         *(GV_LDS f32x4*)(img + (ii * 16 + li16) * IMG_STRIDE + 16 * (NW * j + wave) + gq * 4) = v;
                     }
                 }
@@ -630,8 +670,6 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
         __syncthreads();
         // (pass 0 still holds most of the accumulators: its successor's rows are requested at the top of pass 1, as before --
         //  requesting them here overflows the register file by ~20 registers at FM = 11 / 12)
-        if constexpr (false) {}
-
         // ---- one wave per row
 #pragma unroll
         for (int rr = 0; rr < RPW; ++rr) {
@@ -685,8 +723,8 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
                                 wdy[c][e] = v[c][e] * gm[c][e];
                                 c1 += wdy[c][e];
                                 c2 += wdy[c][e] * xh[c][e];
-                                s_dg[c][e] += v[c][e] * xh[c][e];
-                                s_db[c][e] += v[c][e];
+                                sums.dg[c][e] += v[c][e] * xh[c][e];
+                                sums.db[c][e] += v[c][e];
                             }
                         c1 = wave_sum_dpp(c1) * (1.0f / PN);
                         c2 = wave_sum_dpp(c2) * (1.0f / PN);
@@ -699,7 +737,7 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
                             for (int e = 0; e < 2; ++e) {
                                 gv[c][e] += rstd * (wdy[c][e] - c1 - xh[c][e] * c2);
                                 gbv[e] = gv[c][e] * gs;
-                                s_g[c][e] += gbv[e];
+                                sums.g[c][e] += gbv[e];
                             }
                             // nontemporal: neither row is read again by this launch, and 100 MB of them would pass through the L2
                             // that holds the weights every workgroup re-reads (fc1-dX + LayerNorm backward 88.3 -> 85.7 us)
@@ -719,27 +757,7 @@ __global__ __launch_bounds__(NW * 64, 2) void panel_kernel(const PanelP p) {
     }   // row panels (MODE_WIDE)
     if constexpr (MODE == MODE_WIDE) wait_vmcnt<0>();             // the stream's last, never-consumed pieces land before the LDS is released
 
-    if constexpr (MODE == MODE_BWD) {
-        // column sums over this workgroup's rows -> partials[blockIdx][3][384] (gv_ln_finalize folds them)
-        GV_LDS float* red = (GV_LDS float*)smem;                  // [NW waves][3][384]
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int col = (c * 64 + lane) * 2 + e;
-                red[(wave * 3 + 0) * PN + col] = s_dg[c][e];
-                red[(wave * 3 + 1) * PN + col] = s_db[c][e];
-                red[(wave * 3 + 2) * PN + col] = s_g[c][e];
-            }
-        __syncthreads();
-        float* outp = p.partials + (long)blockIdx.x * 3 * PN;
-        for (int idx = tid; idx < 3 * PN; idx += NW * 64) {
-            float s = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) s += red[w * 3 * PN + idx];
-            outp[idx] = s;
-        }
-    }
+    if constexpr (MODE == MODE_BWD) store_colsums<NW>(smem, tid, lane, wave, p.partials, sums);
 }
 
 template <int FM, int NW, int BK, bool TB, int MODE, int EP = 0, int PP = 0>
@@ -774,27 +792,38 @@ int launch_panel(const PanelP& p, hipStream_t s, const char* name) {
     return GV_OK;
 }
 
-// the instantiation for fm rows of 16 per workgroup (one of FM_SET8), with the ping-pong k-loop where the depth allows
+// the instantiation for fm rows of 16 per workgroup (one of FM_SET8) on k-loop PP
+template <bool TB, int MODE, int EP, int PP>
+int dispatch_fm_loop(const PanelP& p, int fm, hipStream_t s, const char* name) {
+    switch (fm) {
+        case 4: return launch_panel<4, 8, 64, TB, MODE, EP, PP>(p, s, name);
+        case 7: return launch_panel<7, 8, 64, TB, MODE, EP, PP>(p, s, name);
+        case 9: return launch_panel<9, 8, 64, TB, MODE, EP, PP>(p, s, name);
+        case 11: return launch_panel<11, 8, 64, TB, MODE, EP, PP>(p, s, name);
+        default: return launch_panel<12, 8, 64, TB, MODE, EP, PP>(p, s, name);
+    }
+}
+
+// ... with the ping-pong k-loop where the depth allows
 template <bool TB, int MODE, int EP = 0>
 int dispatch_fm(const PanelP& p, int fm, hipStream_t s, const char* name) {
-    if (panel_pingpong(p.K)) {
-        switch (fm) {
-            case 4: return launch_panel<4, 8, 64, TB, MODE, EP, 1>(p, s, name);
-            case 7: return launch_panel<7, 8, 64, TB, MODE, EP, 1>(p, s, name);
-            case 9: return launch_panel<9, 8, 64, TB, MODE, EP, 1>(p, s, name);
-            case 11: return launch_panel<11, 8, 64, TB, MODE, EP, 1>(p, s, name);
-            default: return launch_panel<12, 8, 64, TB, MODE, EP, 1>(p, s, name);
-        }
-    }
+    if (panel_pingpong(p.K)) return dispatch_fm_loop<TB, MODE, EP, 1>(p, fm, s, name);
     if constexpr (MODE == MODE_WIDE) GV_FAIL(GV_E_UNSUPPORTED, "%s: K %% 128 != 0 has no wide kernel", name);      // (plan_wide admits K % 128 == 0 only)
-    else
-    switch (fm) {
-        case 4: return launch_panel<4, 8, 64, TB, MODE, EP>(p, s, name);
-        case 7: return launch_panel<7, 8, 64, TB, MODE, EP>(p, s, name);
-        case 9: return launch_panel<9, 8, 64, TB, MODE, EP>(p, s, name);
-        case 11: return launch_panel<11, 8, 64, TB, MODE, EP>(p, s, name);
-        default: return launch_panel<12, 8, 64, TB, MODE, EP>(p, s, name);
-    }
+    else return dispatch_fm_loop<TB, MODE, EP, 0>(p, fm, s, name);
+}
+
+// gv_linear_ln_fwd / gv_mlp_ln_fwd (`name`): what the two ask of the forward epilogue's operands, and those operands into p.
+// `bias` is the bias in front of the residual add (a->bias / a->bias2, `bias_name`).
+template <class Args>
+int forward_params(const Args* a, const float* bias, const char* bias_name, const char* name, PanelP& p) {
+    if (bias) GV_REQUIRE(gv_aligned(bias, 16), GV_E_ALIGN, "%s: %s misaligned", name, bias_name);
+    if (a->resid) GV_REQUIRE(gv_aligned(a->resid, 16), GV_E_ALIGN, "%s: resid misaligned", name);
+    if (a->gamma) GV_REQUIRE(a->beta && a->y && a->mean && a->rstd, GV_E_NULL, "%s: gamma given, so beta / y / mean / rstd are required", name);
+    p.A = (const bf16*)a->A; p.M = a->M; p.K = a->K; p.lda = a->lda;
+    p.bias = bias; p.resid = a->resid; p.ldr = a->ldr; p.out = a->out; p.ldo = a->ldo;
+    p.gamma = a->gamma; p.beta = a->beta; p.eps = a->eps; p.y = (bf16*)a->y; p.mean = a->mean; p.rstd = a->rstd;
+    p.row_scale = a->row_scale;
+    return GV_OK;
 }
 
 }  // namespace
@@ -830,14 +859,9 @@ extern "C" int gv_linear_ln_fwd(const gv_linear_ln_fwd_args* a, void* stream) {
     GV_REQUIRE(a->M > 0 && a->K > 0 && a->K % 64 == 0, GV_E_SHAPE, "gv_linear_ln_fwd: need M > 0 and K %% 64 == 0 (got M=%d K=%d)", a->M, a->K);
     GV_REQUIRE(a->lda % 8 == 0 && a->ldw % 8 == 0 && a->ldo % 2 == 0 && a->ldr % 4 == 0, GV_E_ALIGN, "gv_linear_ln_fwd: leading dimensions misaligned");
     GV_REQUIRE(gv_aligned(a->A, 16) && gv_aligned(a->W, 16) && gv_aligned(a->out, 16), GV_E_ALIGN, "gv_linear_ln_fwd: A/W/out must be 16-byte aligned");
-    if (a->bias) GV_REQUIRE(gv_aligned(a->bias, 16), GV_E_ALIGN, "gv_linear_ln_fwd: bias misaligned");
-    if (a->resid) GV_REQUIRE(gv_aligned(a->resid, 16), GV_E_ALIGN, "gv_linear_ln_fwd: resid misaligned");
-    if (a->gamma) GV_REQUIRE(a->beta && a->y && a->mean && a->rstd, GV_E_NULL, "gv_linear_ln_fwd: gamma given, so beta / y / mean / rstd are required");
     PanelP p{};
-    p.A = (const bf16*)a->A; p.W = (const bf16*)a->W; p.M = a->M; p.K = a->K; p.lda = a->lda; p.ldw = a->ldw;
-    p.bias = a->bias; p.resid = a->resid; p.ldr = a->ldr; p.out = a->out; p.ldo = a->ldo;
-    p.gamma = a->gamma; p.beta = a->beta; p.eps = a->eps; p.y = (bf16*)a->y; p.mean = a->mean; p.rstd = a->rstd;
-    p.row_scale = a->row_scale;
+    if (int rc = forward_params(a, a->bias, "bias", "gv_linear_ln_fwd", p)) return rc;
+    p.W = (const bf16*)a->W; p.ldw = a->ldw;
     return dispatch_fm<false, MODE_FWD>(p, pick_fm(p.M, gv_cu_budget()), (hipStream_t)stream, "gv_linear_ln_fwd");
 }
 
@@ -852,15 +876,10 @@ extern "C" int gv_mlp_ln_fwd(const gv_mlp_ln_fwd_args* a, void* stream) {
     GV_REQUIRE(a->lda % 8 == 0 && a->ldw1 % 8 == 0 && a->ldw2 % 8 == 0 && a->ldo % 2 == 0 && a->ldr % 4 == 0, GV_E_ALIGN, "gv_mlp_ln_fwd: leading dimensions misaligned");
     GV_REQUIRE(gv_aligned(a->A, 16) && gv_aligned(a->W1, 16) && gv_aligned(a->W2, 16) && gv_aligned(a->out, 16) && gv_aligned(a->bias1, 16), GV_E_ALIGN,
                "gv_mlp_ln_fwd: A / W1 / W2 / out / bias1 must be 16-byte aligned");
-    if (a->bias2) GV_REQUIRE(gv_aligned(a->bias2, 16), GV_E_ALIGN, "gv_mlp_ln_fwd: bias2 misaligned");
-    if (a->resid) GV_REQUIRE(gv_aligned(a->resid, 16), GV_E_ALIGN, "gv_mlp_ln_fwd: resid misaligned");
-    if (a->gamma) GV_REQUIRE(a->beta && a->y && a->mean && a->rstd, GV_E_NULL, "gv_mlp_ln_fwd: gamma given, so beta / y / mean / rstd are required");
     PanelP p{};
-    p.A = (const bf16*)a->A; p.W = (const bf16*)a->W1; p.M = a->M; p.K = a->K; p.lda = a->lda; p.ldw = a->ldw1;
+    if (int rc = forward_params(a, a->bias2, "bias2", "gv_mlp_ln_fwd", p)) return rc;
+    p.W = (const bf16*)a->W1; p.ldw = a->ldw1;
     p.W2 = (const bf16*)a->W2; p.ldw2 = a->ldw2; p.bias1 = a->bias1; p.hidden = a->hidden;
-    p.bias = a->bias2; p.resid = a->resid; p.ldr = a->ldr; p.out = a->out; p.ldo = a->ldo;
-    p.gamma = a->gamma; p.beta = a->beta; p.eps = a->eps; p.y = (bf16*)a->y; p.mean = a->mean; p.rstd = a->rstd;
-    p.row_scale = a->row_scale;
     hipStream_t s = (hipStream_t)stream;
     if (pick_fm_mlp(a->M, gv_cu_budget()) == 4) return launch_panel<4, 8, 64, false, MODE_FWD, EP_MLP>(p, s, "gv_mlp_ln_fwd");
     return launch_panel<7, 8, 64, false, MODE_FWD, EP_MLP>(p, s, "gv_mlp_ln_fwd");
