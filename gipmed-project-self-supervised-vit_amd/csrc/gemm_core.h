@@ -90,7 +90,10 @@ __device__ __forceinline__ void glds16_s(unsigned long long sbase, unsigned voff
 // up once per work item so the k-loop only adds the k offset.  natural: [R rows][BK k] image,
 // pointer = row start + swizzled 16-B chunk; transposed: [BK k][R cols] image, pointer = column
 // position in reduction row r (r = this lane's row inside a stage), `ok` = column in range.
-template <bool T, int R, int BK, int NW>
+// KEDGE (natural operands): the reduction length need not be a multiple of BK (gv_linear asks K % 32 == 0 only) -- the 16-B chunks of
+// the last k-step that lie at or past klim come from the zero page, as the transposed form's rows past klim do; r = this lane's k
+// offset inside a stage.  Without it the caller guarantees whole k-steps (the full-row kernels: K % 64 == 0).
+template <bool T, int R, int BK, int NW, bool KEDGE = false>
 struct TileSrc {
     static constexpr int PPW = R * BK * 2 / 1024 / NW;
     const bf16* ptr[PPW];
@@ -111,6 +114,11 @@ struct TileSrc {
                 ok[p] = true; r[p] = 0;
             }
             all_ok = true;
+            if constexpr (KEDGE) {
+                const int kc = ((lane % LPR) ^ swz_n<BK>(lane / LPR)) * 8;      // (= c * 8 of every piece: the swizzle repeats every RPP rows)
+#pragma unroll
+                for (int p = 0; p < PPW; ++p) r[p] = kc;
+            }
         } else {
             constexpr int RB = R * 2, RPP = 1024 / RB, LPR = RB / 16;
 #pragma unroll
@@ -132,7 +140,8 @@ struct TileSrc {
     // issue piece p of this wave's share of the k-step starting at reduction index k0
     __device__ __forceinline__ void issue_one(int p, long ld, int k0, int klim, GV_LDS char* tile, int wave) const {
         const bf16* src;
-        if constexpr (!T) src = ptr[p] + k0;
+        if constexpr (!T && KEDGE) src = k0 + r[p] < klim ? ptr[p] + k0 : (const bf16*)zero_page;
+        else if constexpr (!T) src = ptr[p] + k0;
         else src = (ok[p] && k0 + r[p] < klim) ? ptr[p] + (long)k0 * ld : (const bf16*)zero_page;
         glds16(src, tile + (wave * PPW + p) * 1024);
     }
@@ -145,6 +154,12 @@ struct TileSrc {
                 const long off = (long)k0 * ld;
 #pragma unroll
                 for (int p = 0; p < PPW; ++p) glds16(ptr[p] + off, tile + (wave * PPW + p) * 1024);
+                return;
+            }
+        } else if constexpr (KEDGE) {
+            if (k0 + BK <= klim) {      // (uniform) a whole k-step, every step of the hot shapes: no per-lane select
+#pragma unroll
+                for (int p = 0; p < PPW; ++p) glds16(ptr[p] + k0, tile + (wave * PPW + p) * 1024);
                 return;
             }
         }
@@ -255,8 +270,8 @@ __device__ __forceinline__ void gemm_body_w(const GemmP& g, GV_LDS char* smem, c
     static_assert(C::SCHED >= 0 && C::SCHED <= 3, "k-loop schedule");
     for (int it_i = 0, idx = wk.first; it_i < wk.count; ++it_i, idx += wk.stride) {
         const Item it = make_item<C>(g, wk, idx);
-        TileSrc<TA, BM, BK, C::NW> srcA;
-        TileSrc<TB, BN, BK, C::NW> srcB;
+        TileSrc<TA, BM, BK, C::NW, true> srcA;
+        TileSrc<TB, BN, BK, C::NW, true> srcB;
         srcA.setup(g.A, g.lda, it.m0, g.M, wave, lane);
         srcB.setup(g.B, g.ldb, it.n0, g.N, wave, lane);
         // ---- the LDS-DMA ring runs PD k-steps ahead of the MFMAs

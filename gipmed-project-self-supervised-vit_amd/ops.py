@@ -270,40 +270,47 @@ def linear_timing_read():
 
 
 def linear_ln_fwd(A, W, out, M: int, K: int, *, bias=None, resid=None, gamma=None, beta=None, y=None, mean=None, rstd=None, eps: float = 1e-6,
-                  N: int = 384, row_scale=None):
-    """out = A W^T + bias + resid (f32) and, with gamma, y / mean / rstd = LayerNorm of the new row; see gv_linear_ln_fwd."""
-    a = L.gv_linear_ln_fwd_args(A.data_ptr(), W.data_ptr(), M, N, K, K, K, _p(bias), _p(resid), N, out.data_ptr(), N,
+                  N: int = 384, row_scale=None, lda=None, ldw=None, ldr=None, ldo=None):
+    """out = A W^T + bias + resid (f32) and, with gamma, y / mean / rstd = LayerNorm of the new row; see gv_linear_ln_fwd.
+    Leading dimensions (elements) default to the compact widths."""
+    a = L.gv_linear_ln_fwd_args(A.data_ptr(), W.data_ptr(), M, N, K, K if lda is None else lda, K if ldw is None else ldw, _p(bias), _p(resid),
+                                N if ldr is None else ldr, out.data_ptr(), N if ldo is None else ldo,
                                 _p(gamma), _p(beta), eps, _p(y), _p(mean), _p(rstd), _p(row_scale))
     L.call("gv_linear_ln_fwd", a, _stream())
 
 
 def mlp_ln_fwd(A, W1, b1, W2, out, M: int, K: int, hidden: int, *, bias2=None, resid=None, gamma=None, beta=None, y=None, mean=None, rstd=None,
-               eps: float = 1e-6, N: int = 384, row_scale=None):
+               eps: float = 1e-6, N: int = 384, row_scale=None, lda=None, ldw1=None, ldw2=None, ldr=None, ldo=None):
     """out = resid + row_scale (GELU(A W1^T + b1) W2^T + bias2) (f32) and, with gamma, y / mean / rstd = LayerNorm of the new row, in one
-    launch; the hidden activation is not stored (forward-only passes); see gv_mlp_ln_fwd."""
-    a = L.gv_mlp_ln_fwd_args(A.data_ptr(), W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), _p(bias2), M, N, K, hidden, K, K, hidden,
-                             _p(resid), N, out.data_ptr(), N, _p(gamma), _p(beta), eps, _p(y), _p(mean), _p(rstd), _p(row_scale))
+    launch; the hidden activation is not stored (forward-only passes); see gv_mlp_ln_fwd.  Leading dimensions (elements) default to
+    the compact widths."""
+    a = L.gv_mlp_ln_fwd_args(A.data_ptr(), W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), _p(bias2), M, N, K, hidden, K if lda is None else lda,
+                             K if ldw1 is None else ldw1, hidden if ldw2 is None else ldw2,
+                             _p(resid), N if ldr is None else ldr, out.data_ptr(), N if ldo is None else ldo, _p(gamma), _p(beta), eps, _p(y), _p(mean), _p(rstd), _p(row_scale))
     L.call("gv_mlp_ln_fwd", a, _stream())
 
 
-def linear_ln_bwd(dY, W, x, mean, rstd, gamma, g, gb, partials, M: int, K: int, *, g_init: bool = False, N: int = 384, gb_scale=None) -> int:
+def linear_ln_bwd(dY, W, x, mean, rstd, gamma, g, gb, partials, M: int, K: int, *, g_init: bool = False, N: int = 384, gb_scale=None,
+                  lda=None, ldw=None, ldx=None, ldg=None, ldgb=None) -> int:
     """dXn = dY W (W stored [K, N]) fused with the LayerNorm backward it feeds; returns the number of partial blocks
-    written (the n_blocks argument of ln_finalize); see gv_linear_ln_bwd."""
-    a = L.gv_linear_ln_bwd_args(dY.data_ptr(), W.data_ptr(), M, N, K, K, N, x.data_ptr(), N, mean.data_ptr(), rstd.data_ptr(),
-                                gamma.data_ptr(), g.data_ptr(), N, _p(gb), N, partials.data_ptr(), partials.shape[0], int(g_init), _p(gb_scale))
+    written (the n_blocks argument of ln_finalize); see gv_linear_ln_bwd.  Leading dimensions (elements) default to the compact widths."""
+    a = L.gv_linear_ln_bwd_args(dY.data_ptr(), W.data_ptr(), M, N, K, K if lda is None else lda, N if ldw is None else ldw, x.data_ptr(),
+                                N if ldx is None else ldx, mean.data_ptr(), rstd.data_ptr(),
+                                gamma.data_ptr(), g.data_ptr(), N if ldg is None else ldg, _p(gb), N if ldgb is None else ldgb, partials.data_ptr(), partials.shape[0], int(g_init), _p(gb_scale))
     L.call("gv_linear_ln_bwd", a, _stream())
     return L.lib.gv_linear_ln_blocks(M)
 
 
 def linear_dw_group(problems, K: int, workspace):
     """problems: [(dY [K, M] bf16, X [K, N] bf16, dW [M, N] f32 (accumulated), colsum_dy [M] f32 or None), ...] (at most 4) that
-    reduce over the same K token rows -- one split-K launch + one reduce for all of them; see gv_linear_dw_group."""
+    reduce over the same K token rows -- one split-K launch + one reduce for all of them; see gv_linear_dw_group.  The matrices may be
+    2-D views of wider buffers: a matrix's leading dimension is its .stride(0)."""
     a = L.gv_linear_dw_group_args()
     a.n, a.K = len(problems), K
     a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
     for q, (dY, X, dW, cs) in enumerate(problems):
         pr = a.prob[q]
-        pr.dY, pr.ldy, pr.X, pr.ldx, pr.dW, pr.ldw = dY.data_ptr(), dY.shape[1], X.data_ptr(), X.shape[1], dW.data_ptr(), dW.shape[1]
+        pr.dY, pr.ldy, pr.X, pr.ldx, pr.dW, pr.ldw = dY.data_ptr(), dY.stride(0), X.data_ptr(), X.stride(0), dW.data_ptr(), dW.stride(0)
         pr.colsum_dy, pr.M, pr.N = _p(cs), dY.shape[1], X.shape[1]
     L.call("gv_linear_dw_group", a, _stream())
 

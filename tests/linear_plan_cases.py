@@ -102,6 +102,20 @@ def gelu_ref(v):
     return (x * f(xc * q + 0.5)).float()
 
 
+def dgelu_ref(v):
+    """gv_common.h's dgelu_f on f32 values, emulated like gelu_ref."""
+    import torch
+    f = lambda t: t.float().double()
+    xd = v.double().clamp(-4.0, 4.0)
+    s = f(xd * xd)
+    c = [float(torch.tensor(t, dtype=torch.float32)) for t in (-1.154122852e-11, 1.5301791658e-09, -8.8285028494e-08, 2.9218555444e-06, -6.1681373513e-05,
+                                                                8.7549978582e-04, -8.5804168959e-03, 5.8243992531e-02, -2.6485431579e-01, 7.9775551922e-01)]
+    r = f(c[0] * s + c[1])
+    for ck in c[2:]:
+        r = f(r * s + ck)
+    return f(xd * r + 0.5).float()
+
+
 def timed(o, fn):
     """fn() between linear_timing(True) and (False): the timing rows."""
     o.linear_timing(True)
