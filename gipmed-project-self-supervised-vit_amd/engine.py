@@ -24,6 +24,7 @@ from __future__ import annotations
 import dataclasses
 import math
 import os
+import weakref
 from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -45,16 +46,48 @@ STD_RON = (0.1125, 0.1751, 0.0787)    # transformations.py:113
 PAD = 64                              # arena offsets are multiples of 64 elements
 
 
-def _empty(shape, dt, device):
+_POISON_POOL: List["weakref.ref"] = []      # the tensors _empty handed out under GIPVIT_POISON=1 (repoison refills the live ones)
+
+
+def _poison(t: torch.Tensor):
+    t.fill_(float("nan") if t.dtype.is_floating_point else 255)
+
+
+def _empty(shape, dt, device, carried: bool = False):
     """torch.empty, or NaN / 0xFF-poisoned memory when GIPVIT_POISON=1 (debug: any read of a
-    buffer before it was written then shows up as NaN in the loss / gradients)."""
+    buffer before it was written then shows up as NaN in the loss / gradients).  This is scratch: nothing may read it before the
+    same step / pass wrote it, and a poisoned one is registered for ``repoison`` (``carried``: it is not -- ``_carried``).
+    Float types and uint8 only: all-ones in a wider integer would be a wild index, and index tables are built from their
+    values (torch.cat / torch.tensor), never allocated empty."""
+    if not (dt.is_floating_point or dt == torch.uint8):
+        raise TypeError(f"_empty / _carried: {dt} -- float types and uint8 only (poison in a wider integer would be a wild index)")
     t = torch.empty(shape, dtype=dt, device=device)
     if os.environ.get("GIPVIT_POISON"):
-        if dt.is_floating_point:
-            t.fill_(float("nan"))
-        else:
-            t.fill_(-1)
+        _poison(t)
+        if not carried:
+            _POISON_POOL.append(weakref.ref(t))
     return t
+
+
+def _carried(shape, dt, device):
+    """``_empty`` for a buffer that legitimately holds values from one step to the next: poisoned when allocated (a read before
+    its FIRST write still shows) and never refilled.  Every call site names who writes it and when."""
+    return _empty(shape, dt, device, carried=True)
+
+
+def repoison() -> int:
+    """Refill every live ``_empty`` buffer that was allocated under GIPVIT_POISON=1 (NaN, all-ones for uint8) and return how
+    many there were: 0 with poison off.  Called between steps / passes it shows a read of what the PREVIOUS one left behind.
+    The fills are queued on the current stream, so the caller synchronises the device first (the last step's side-stream work
+    may still be using the buffers)."""
+    live = [(r, r()) for r in _POISON_POOL]
+    _POISON_POOL[:] = [r for r, t in live if t is not None]
+    n = 0
+    for _, t in live:
+        if t is not None:
+            _poison(t)
+            n += 1
+    return n
 
 
 def input_form(x, n: Optional[int], hw: Optional[Tuple[int, int]], float_extras: Sequence[Tuple[str, object]] = ()) -> str:
@@ -373,7 +406,7 @@ class VitGroup:
         if self._row_img is None:
             m = torch.cat([sg.img0 + torch.arange(sg.T, dtype=torch.int32) // sg.N for sg in self.segs])
             self._row_img = m.to(self.device)
-            self._rs_buf = _empty((self.depth, 2, self.T), f32, self.device)
+            self._rs_buf = _carried((self.depth, 2, self.T), f32, self.device)      # written by every set_drop (below), valid until the next one
         ops.expand_rows(per_img.contiguous(), self._row_img, self._rs_buf, self.depth * 2, self.n_img, self.T)
         self.rs = self._rs_buf
 
@@ -1016,8 +1049,8 @@ class DinoEngine(TrainEngine):
         self.s_wins = [self.gwins] + ([self.lwins] if n_local else [])
         self.hb_s = HeadBuffers(self.V * B, D, out_dim, hidden, bottleneck, dev, save=True, act=act)
         self.hb_t = HeadBuffers(n_global * B, D, out_dim, hidden, bottleneck, dev, save=False, act=act)
-        self.wn_s = _empty((out_dim, bottleneck), act, dev)
-        self.wn_t = _empty((out_dim, bottleneck), act, dev)
+        self.wn_s = _carried((out_dim, bottleneck), act, dev)      # written by _refresh_wn: at load_state and behind every optimizer step
+        self.wn_t = _carried((out_dim, bottleneck), act, dev)      # written by _refresh_wn, as wn_s
         self.center = torch.zeros(out_dim, dtype=f32, device=dev)
         self.center_sum = torch.zeros(out_dim, dtype=f32, device=dev)
         self.loss = torch.zeros(1, dtype=f32, device=dev)

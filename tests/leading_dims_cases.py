@@ -333,6 +333,7 @@ def run(o, L, r, dev, ws, pads):
     import torch
     ops, kw, expect = build(o, L, r, dev)
     fr = frames(ops, pads)
+    ws.fill_(float("nan"))      # the split-K scratch as a kernel must expect it, in front of every call: a slab reduce that reads a slice nothing stored gives NaN
     rows = lpc.timed(o, lambda: CALLS[r["op"]](o, r, fr, kw, ws))
     torch.cuda.synchronize()
     return rows, fr, expect

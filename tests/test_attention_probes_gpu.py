@@ -45,16 +45,37 @@ class Segment:
         return dict(o=unpack_rows(out, self.n_img, self.H), lse=unpack_lse(self.lse, self.n_img, self.H), dq=dq, dk=dk, dv=dv)
 
 
+def _bits(t):
+    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+def _nan_like(t):
+    return torch.full_like(t, float("nan"))
+
+
 def run(dev, case, n_img=N_IMG, H=H, dtype=bf16, q_limit=0, d_o=None):
-    """forward + backward (from the forward's own o / lse) of one case through gv_attention_fwd / gv_attention_bwd"""
+    """forward + backward (from the forward's own o / lse) of one case through gv_attention_fwd / gv_attention_bwd.  Under
+    q_limit everything the header says is neither written nor read is NaN: o / lse are NaN-filled before the forward, the rows
+    behind ceil32(q_limit) must keep that bit pattern, the backward runs on those NaN-tailed o / lse (as the limited forward
+    leaves them in the engine) and on a dO whose rows behind ceil32(q_limit) are NaN too (a finite sentinel times the zero dO
+    would hide a read)."""
     o, sg = ops(), Segment(dev, case, n_img, H, dtype, d_o)
     T = n_img * sg.N
     obuf, out = _guarded(T, H * 64, dtype, dev)
     gbuf, dqkv = _guarded(T, 3 * H * 64, dtype, dev)
+    qe = min(sg.N, (q_limit + 31) // 32 * 32) if q_limit else sg.N
+    if q_limit:
+        out.fill_(float("nan")); sg.lse.fill_(float("nan"))
+        sg.d_o.view(n_img, sg.N, H * 64)[:, qe:] = float("nan")
     o.attention_fwd(sg.qkv, n_img, sg.N, H, SCALE, o=out, lse=sg.lse, q_limit=q_limit)
+    if qe < sg.N:
+        ov, lv = out.view(n_img, sg.N, H * 64)[:, qe:], sg.lse[:, :, qe:]
+        assert torch.equal(_bits(ov), _bits(_nan_like(ov))) and torch.equal(_bits(lv), _bits(_nan_like(lv))), "forward wrote behind q_limit"
     o.attention_bwd(sg.qkv, out, sg.d_o, sg.lse, n_img, sg.N, H, SCALE, dqkv=dqkv, q_limit=q_limit)
     _guards_untouched((obuf, out), (gbuf, dqkv), (sg.lbuf, sg.lse))
-    return sg.result(out, dqkv)
+    res = sg.result(out, dqkv)
+    res["dqkv_raw"] = dqkv.clone()
+    return res
 
 
 def run_varlen(dev, cases, n_imgs, H=H):
@@ -213,8 +234,10 @@ def test_varlen_just_outside_the_fused_window(dev, n_a, n_b):
 @pytest.mark.parametrize("N", [33, 225, 288])
 @pytest.mark.parametrize("ql", [1, 32, 33])
 def test_probe_q_limit(dev, ql, N):
-    """Probe A under q_limit: the forward's rows < min(N, ceil32(q_limit)) are exact, the rest untouched; the backward with dO zero
-    behind q_limit: dV exact (dO of the matching query, ~0 for a key whose query is behind the limit), skipped dQ rows exactly 0."""
+    """Probe A under q_limit: the forward's rows < min(N, ceil32(q_limit)) are exact, the rest untouched (NaN before and after, bit
+    for bit); the backward with dO zero behind q_limit and NaN behind ceil32(q_limit), on the NaN-tailed o / lse: dV exact (dO of
+    the matching query, ~0 for a key whose query is behind the limit), skipped dQ rows exactly 0, every gradient bit-equal to the
+    full kernels' on the zero-tailed dO."""
     full = build("A", N)
     d_o = full["d_o"].clone()
     d_o[:, ql:] = 0
@@ -225,8 +248,10 @@ def test_probe_q_limit(dev, ql, N):
     qe = min(N, (ql + 31) // 32 * 32)
     check_selector(_rows(got, slice(0, qe)), _rows(case, slice(0, qe)), parts=("o", "lse"))
     check_selector(got, case, parts=("dq", "dk", "dv"))
+    # (run() has NaN behind the limit in o, lse and dO, and checks that the forward left those o / lse rows as they were)
+    assert torch.equal(got["dqkv_raw"], run(dev, case, d_o=d_o)["dqkv_raw"]), "gradients differ from the full kernels' on the zero-tailed dO"
     if qe < N:
-        assert bool((got["o"][:, qe:] == SENT).all()) and bool((got["lse"][:, qe:] == SENT).all()), "forward wrote behind q_limit"
+        assert bool(torch.isnan(got["o"][:, qe:]).all()) and bool(torch.isnan(got["lse"][:, qe:]).all()), "forward wrote behind q_limit"
         assert bool((got["dq"][:, qe:] == 0).all()), "skipped dQ rows are not exactly zero"
 
 

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from test_attention_probes_host import H, N_IMG, SCALE, build, check_selector, pack_qkv, unpack_lse, unpack_rows
-from test_attention_probes_gpu import SENT, _all_pairs_equal_pair0, _guarded, _guards_untouched, _replicated, _rows
+from test_attention_probes_gpu import _all_pairs_equal_pair0, _bits, _guarded, _guards_untouched, _nan_like, _replicated, _rows
 from test_attention_stream_host import (B_NS, SHORT_NS, STREAM_CHECKS, STREAM_LSE_BOUND, STREAM_NS, STREAM_QBLOCK, build_spike, build_staircase,
                                         check_stream)
 
@@ -29,8 +29,14 @@ def run_stream(dev, case, n_img=N_IMG, H=H, dtype=bf16, q_limit=0):
     obuf, out = _guarded(n_img * N, H * 64, dtype, dev)
     lbuf, lse = _guarded(n_img * H, N, f32, dev)
     lse = lse.view(n_img, H, N)
+    if q_limit:      # what the limited forward must leave as it is: NaN, compared on the bit pattern
+        out.fill_(float("nan")); lse.fill_(float("nan"))
+        qe = min(N, (q_limit + STREAM_QBLOCK - 1) // STREAM_QBLOCK * STREAM_QBLOCK)
     ops.attention_fwd_stream(qkv, n_img, N, H, SCALE, o=out, lse=lse, q_limit=q_limit)
     _guards_untouched((obuf, out), (lbuf, lse))
+    if q_limit and qe < N:
+        ov, lv = out.view(n_img, N, H * 64)[:, qe:], lse[:, :, qe:]
+        assert torch.equal(_bits(ov), _bits(_nan_like(ov))) and torch.equal(_bits(lv), _bits(_nan_like(lv))), "the forward wrote behind q_limit's last block"
     return dict(o=unpack_rows(out, n_img, H), lse=unpack_lse(lse, n_img, H))
 
 
@@ -73,13 +79,13 @@ def test_forced_rescale(dev, kind, N):
 @pytest.mark.parametrize("ql,N", [(1, 289), (33, 289), (1, 1025), (33, 1025), (129, 1025)])
 def test_q_limit(dev, ql, N):
     """Probe A under q_limit: whole GV_ATTN_STREAM_QBLOCK-row blocks that hold a row < q_limit are exact (1 and 33: one block;
-    129: two), every row behind them still holds the sentinel."""
+    129: two), every row behind them still holds the NaN it was filled with (run_stream compares the bit pattern)."""
     case = build("A", N)
     got = run_stream(dev, case, q_limit=ql)
     qe = min(N, (ql + STREAM_QBLOCK - 1) // STREAM_QBLOCK * STREAM_QBLOCK)
     assert qe == (2 if ql == 129 else 1) * STREAM_QBLOCK < N
     check_selector(_rows(got, slice(0, qe)), _rows(case, slice(0, qe)), parts=("o", "lse"))
-    assert bool((got["o"][:, qe:] == SENT).all()) and bool((got["lse"][:, qe:] == SENT).all()), "the forward wrote behind q_limit's last block"
+    assert bool(torch.isnan(got["o"][:, qe:]).all()) and bool(torch.isnan(got["lse"][:, qe:]).all()), "the forward wrote behind q_limit's last block"
 
 
 @pytest.mark.parametrize("N", [289, 1025])

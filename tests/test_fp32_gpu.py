@@ -132,7 +132,8 @@ def test_layernorm_f32_io(dev, D):
     _, mean, rstd = ops.layernorm_fwd(x.to(dev), gamma.to(dev), beta.to(dev), rows, D, y=y)
     assert _rel(y, y_ref.detach()) < 2e-6
     gbuf, gb = g_in.to(dev).clone(), torch.empty(rows, D, device=dev)
-    partials = torch.zeros(L.LN_PARTIAL_BLOCKS, 3, D, device=dev)
+    # NaN, not zeros: the launch's grid is LN_PARTIAL_BLOCKS and every workgroup stores its block (csrc/layernorm.hip), rows or no rows
+    partials = torch.full((L.LN_PARTIAL_BLOCKS, 3, D), float("nan"), device=dev)
     ops.layernorm_bwd(dy.to(dev), x.to(dev), mean, rstd, gamma.to(dev), gbuf, gb, partials, rows, D)
     assert _rel(gbuf, g_in.double() + xr.grad) < 2e-6
     assert torch.equal(gb, gbuf)                       # the f32 "copy for the next GEMM" is the residual gradient itself

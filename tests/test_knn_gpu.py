@@ -28,8 +28,21 @@ def _case(case):
     return _ref_cache[case]
 
 
+def _poisoned_workspace(dev, Q, Nb, k, n_split=0):
+    """The scratch ops.knn_vote keeps per device, all-ones (similarity NaN, index -1) for the next call: made large enough here, so
+    that the call takes this buffer and not fresh, mostly zero, torch.empty memory.  The merge takes a list entry as an index only
+    inside [0, Nb) (csrc/knn.hip), so a slot the scan never stored shows as a missing neighbour / NaN similarity, never as a read."""
+    from gipvit import _lib, ops
+    need = _lib.lib.gv_knn_workspace_bytes(Q, Nb, k, n_split)
+    ws = ops._knn_workspace.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = ops._knn_workspace[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws.fill_(255)
+
+
 def _vote(dev, q, bank, labels, k, C, n_split=0, want_topk=True):
     from gipvit import ops
+    _poisoned_workspace(dev, q.shape[0], bank.shape[0], k, n_split)
     out = ops.knn_vote(q.to(dev), bank.to(dev), labels.to(dev, torch.int32), k, TEMP, C, n_split=n_split, want_topk=want_topk)
     torch.cuda.synchronize()
     return tuple(t.cpu() for t in out) if want_topk else out.cpu()
@@ -103,7 +116,9 @@ def test_knn_vote_strided_queries_and_null_outputs(dev):
     qs = wide[:, 4:4 + D]                                                  # row stride D + 8, base 16 bytes into the buffer
     assert qs.stride() == (D + 8, 1) and qs.data_ptr() % 16 == 0
     votes, top_sim, top_idx = _vote(dev, q, bank, labels, k, C)
+    _poisoned_workspace(dev, Q, Nb, k)
     v2, s2, i2 = ops.knn_vote(qs, bank.to(dev), labels.to(dev, torch.int32), k, TEMP, C, want_topk=True)
+    _poisoned_workspace(dev, Q, Nb, k)
     v3 = ops.knn_vote(qs, bank.to(dev), labels.to(dev, torch.int32), k, TEMP, C)      # votes only: top_sim / top_idx NULL
     torch.cuda.synchronize()
     assert torch.equal(v2.cpu(), votes) and torch.equal(s2.cpu(), top_sim) and torch.equal(i2.cpu(), top_idx) and torch.equal(v3.cpu(), votes)

@@ -121,14 +121,14 @@ def test_ranges_kernel_equals_two_range_launches_bitwise(dev, variant, mode):
         for step, gr in enumerate(grads, 1):
             kw = dict(lr=lr, beta1=0.9, beta2=0.999, eps=1e-8, step=step, teacher_momentum=mom, mode=mode)
             if variant == "clip_norm":
-                o.sumsq(gr, ws, gn); kw.update(clip_norm=5.0, gnorm_sq=gn)
+                o.sumsq(gr, ws.fill_(float("nan")), gn); kw.update(clip_norm=5.0, gnorm_sq=gn)
             if variant == "clip_value":
                 kw.update(clip_value=0.7, grad_scale=0.5)
             if variant == "hyper":
                 o.store_f32(hyper, [lr * step, wd, 1.0 - 0.9 ** step, 1.0 - 0.999 ** step, mom, 0.25, 0.0, 0.0])
                 kw.update(hyper=hyper, lr=0.0)
             if variant == "loss_scale":
-                o.sumsq(gr, ws, gn)
+                o.sumsq(gr, ws.fill_(float("nan")), gn)
                 if step == 2:
                     gn.fill_(float("inf"))
                 kw.update(loss_scale=scaler.scale, gnorm_sq=gn)
@@ -191,7 +191,7 @@ def test_lamb_per_tensor_rates_match_oracle(dev):
             orc.p[k].copy_(before[k] + scale[k] * (orc.p[k] - before[k]))
             t_ref[k] = 0.99 * t_ref[k] + 0.01 * orc.p[k]
         G = flat(grads).to(dev)
-        o.sumsq(G, ws, gsq)
+        o.sumsq(G, ws.fill_(float("nan")), gsq)          # the scratch as a kernel must expect it: NaN, not fresh zero pages
         for bufs, ls in (((P, M, V, Pb, T, Tb), rates), ((P1, M1, V1, Pb1, T1, Tb1), None), ((P2, M2, V2, Pb2, T2, Tb2), ones)):
             stats.zero_()
             for phase in (0, 1):

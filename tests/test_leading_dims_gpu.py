@@ -33,6 +33,7 @@ def L():
 
 @pytest.fixture(scope="module")
 def ws(dev):
+    """the split-K scratch; leading_dims_cases.run fills it with NaN in front of every call"""
     return torch.empty(L().lib.gv_linear_workspace_bytes() // 4, dtype=f32, device=dev)
 
 

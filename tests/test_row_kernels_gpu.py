@@ -474,12 +474,12 @@ def test_sumsq_exact(dev, n):
     x = rint((n,), -1, 1, seed=n)
     want = float((x != 0).sum())
     _, xd = put(dev, x)
-    ws = torch.empty(1024, device=dev)
+    ws = torch.full((1024,), float("nan"), device=dev)
     obuf, out = guarded(dev, 1)
     o.sumsq(xd, ws, out, n=n)
     assert float(out) == want, (float(out), want)
     out.fill_(41.0)
-    o.sumsq(xd, ws, out, accumulate=True, n=n)
+    o.sumsq(xd, ws.fill_(float("nan")), out, accumulate=True, n=n)
     assert float(out) == want + 41.0
     guard_ok(obuf, 1, "sumsq out")
 
@@ -494,13 +494,13 @@ def test_sumsq_randn_and_nonfinite(dev):
     x = torch.randn(n, generator=gen(77))
     ref = float((x.double() ** 2).sum())
     _, xd = put(dev, x)
-    ws = torch.empty(1024, device=dev); out = torch.empty(1, device=dev)
+    ws = torch.full((1024,), float("nan"), device=dev); out = torch.empty(1, device=dev)
     o.sumsq(xd, ws, out, n=n)
     print(f"[derived] sumsq randn: rel err {abs(float(out) - ref) / ref:.3e} (bound 1e-5)")
     assert abs(float(out) - ref) <= 1e-5 * ref, (float(out), ref)
     for bad in (float("inf"), float("nan")):
         xd[n - 1] = bad
-        o.sumsq(xd, ws, out, n=n)
+        o.sumsq(xd, ws.fill_(float("nan")), out, n=n)
         assert not math.isfinite(float(out)), bad
 
 
@@ -727,6 +727,7 @@ def _dino_case(B, V, G, K, int_teacher=False):
 def _dino_run(dev, s, t, center, B, V, G, K, dt, **kw):
     dbuf, ds = guarded(dev, V * B * K, dt); lbuf, loss = guarded(dev, 1); cbuf, csum = guarded(dev, K)
     wbuf, ws = guarded(dev, 2 * (V + G) * B)
+    ws.fill_(float("nan"))                           # the row stats are written before they are read (the guard keeps its sentinel)
     st, tt = kw.pop("student_temp", TS), kw.pop("teacher_temp", TT)
     ops().dino_loss(s.to(dev), t.to(dev), center[0].to(dev), ds.view(V * B, K), loss, csum, ws, B, V, G, K, st, tt, **kw)
     torch.cuda.synchronize()
