@@ -160,6 +160,13 @@ gv_lamb_args = _struct("gv_lamb_args", [
 gv_knn_vote_args = _struct("gv_knn_vote_args", [
     ("q", vp), ("bank", vp), ("labels", vp), ("votes", vp), ("top_sim", vp), ("top_idx", vp), ("workspace", vp), ("workspace_bytes", i64),
     ("Q", i32), ("Nb", i32), ("D", i32), ("k", i32), ("C", i32), ("n_split", i32), ("ldq", i64), ("ldb", i64), ("inv_temp", f32)])
+gv_linprobe_train_args = _struct("gv_linprobe_train_args", [
+    ("W", vp), ("b", vp), ("mW", vp), ("mb", vp), ("lr", vp), ("wd", vp), ("x", vp), ("labels", vp), ("rows", vp), ("loss_sum", vp),
+    ("workspace", vp), ("workspace_bytes", i64), ("ldx", i64), ("N", i32), ("F", i32), ("H", i32), ("C", i32), ("n_rows", i32), ("batch", i32),
+    ("lr_scale", f32), ("momentum", f32)])
+gv_linprobe_predict_args = _struct("gv_linprobe_predict_args", [
+    ("W", vp), ("b", vp), ("x", vp), ("labels", vp), ("prob", vp), ("loss", vp), ("workspace", vp), ("workspace_bytes", i64), ("ldx", i64),
+    ("Q", i32), ("F", i32), ("H", i32), ("C", i32)])
 
 # entry point -> argument struct (every `int gv_*(const args*, void* stream)` of the header)
 ENTRY_POINTS = {
@@ -183,11 +190,11 @@ ENTRY_POINTS = {
     "gv_layernorm_fwd_f32": gv_layernorm_fwd_args, "gv_layernorm_bwd_f32": gv_layernorm_bwd_args, "gv_patchify_f32": gv_patchify_args, "gv_patchify_nchw_f32": gv_patchify_nchw_args,
     "gv_tokens_bwd_f32": gv_tokens_bwd_args, "gv_l2norm_fwd_f32": gv_l2norm_fwd_args, "gv_l2norm_bwd_f32": gv_l2norm_bwd_args,
     "gv_weightnorm_fwd_f32": gv_weightnorm_fwd_args, "gv_dino_loss_f32": gv_dino_loss_args,
-    "gv_knn_vote": gv_knn_vote_args,
+    "gv_knn_vote": gv_knn_vote_args, "gv_linprobe_train": gv_linprobe_train_args, "gv_linprobe_predict": gv_linprobe_predict_args,
     "gv_token_mean_fwd": gv_token_mean_fwd_args, "gv_token_mean_bwd": gv_token_mean_bwd_args, "gv_token_mean_bwd_f32": gv_token_mean_bwd_args,
 }
 PLAIN_SYMBOLS = ("gv_version", "gv_last_error", "gv_target", "gv_act_format", "gv_linear_workspace_bytes", "gv_workspace_bytes", "gv_linear_timing", "gv_linear_timing_read",
-                 "gv_linear_ln_blocks", "gv_knn_workspace_bytes")
+                 "gv_linear_ln_blocks", "gv_knn_workspace_bytes", "gv_linprobe_workspace_bytes")
 
 
 class gv_linear_timing_row(C.Structure):
@@ -230,6 +237,8 @@ def _load():
     lib.gv_linear_ln_blocks.restype = C.c_int
     lib.gv_knn_workspace_bytes.argtypes = [C.c_int32] * 4
     lib.gv_knn_workspace_bytes.restype = C.c_int64
+    lib.gv_linprobe_workspace_bytes.argtypes = [C.c_int32] * 4
+    lib.gv_linprobe_workspace_bytes.restype = C.c_int64
     return lib
 
 

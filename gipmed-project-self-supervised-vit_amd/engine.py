@@ -32,15 +32,11 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .archs import ARCHS  # noqa: F401  (vit.pyc@L275-293; plain data, kept where the driver can read it before the library loads)
 from .layer_decay import LayerDecayPlan
 
 bf16, f32 = ops.bf16, torch.float32      # ops.bf16: the 16-bit dtype of the loaded library build (float16 under GIPVIT_ACT_FORMAT=f16)
 
-ARCHS = {   # vit.pyc@L275-293
-    "vit_tiny": dict(embed_dim=192, depth=12, num_heads=3),
-    "vit_small": dict(embed_dim=384, depth=12, num_heads=6),
-    "vit_base": dict(embed_dim=768, depth=12, num_heads=12),
-}
 MEAN_RON = (0.8998, 0.8253, 0.9357)   # transformations.py:106
 STD_RON = (0.1125, 0.1751, 0.0787)    # transformations.py:113
 PAD = 64                              # arena offsets are multiples of 64 elements
@@ -1672,3 +1668,37 @@ class FeatureExtractor:
                 for o, b in zip(outs, bufs):
                     o[lo:hi].copy_(b[: hi - lo])
         return outs
+
+    def probe_features(self, tiles_u8: torch.Tensor, n_last: int = 4, avgpool: bool = False) -> torch.Tensor:
+        """The input of DINO's eval_linear over any number of tiles: the CLS rows of ``norm(x)`` after each of the last ``n_last``
+        blocks, concatenated in block order, with ``avgpool`` followed by the mean of the last block's normalised patch tokens
+        -- f32 [n_tiles, n_last * D (+ D)].  Built on the token capture of ``intermediate_layers`` one batch at a time: the
+        scratch is n_last x B x N x D whatever the number of tiles.  Not for a global_pool='avg' model."""
+        if self.pool == "avg":
+            raise ValueError("probe_features: the probe reads the final norm's tokens, and a global_pool='avg' model has no "
+                             "final norm (its fc_norm normalises the pooled vector)")
+        self._check_size(tiles_u8)
+        if not 1 <= n_last <= self.vit.depth:
+            raise ValueError(f"probe_features: n_last = {n_last}, need 1 <= n_last <= depth = {self.vit.depth}")
+        N, D, T, B = self.grp.segs[0].N, self.D, self.grp.T, self.B
+        out = torch.empty(tiles_u8.shape[0], (n_last + bool(avgpool)) * D, dtype=f32, device=self.dev)
+        bufs = []
+        for k in range(n_last):
+            buf = self._scratch.get(f"_tok_buf{k}")
+            if buf is None or tuple(buf.shape) != (B, N, D):
+                buf = self._scratch[f"_tok_buf{k}"] = torch.empty(B, N, D, dtype=f32, device=self.dev)
+            bufs.append(buf)
+        if self._tok_stats is None:
+            self._tok_stats = torch.empty(2, T, dtype=f32, device=self.dev)
+        if avgpool:
+            pooled = self._scratch.get("_probe_pool")
+            if pooled is None:
+                pooled = self._scratch["_probe_pool"] = torch.empty(B, D, dtype=f32, device=self.dev)
+        for lo, hi, part in self._batches(tiles_u8):
+            self.forward(part, Capture(tokens=[b.view(T, D) for b in bufs], stats=self._tok_stats))
+            for k, b in enumerate(bufs):
+                out[lo:hi, k * D:(k + 1) * D].copy_(b[: hi - lo, 0, :])          # the CLS rows: a strided copy
+            if avgpool:
+                ops.token_mean_fwd(bufs[-1].view(T, D), pooled, B, N, D)
+                out[lo:hi, n_last * D:].copy_(pooled[: hi - lo])
+        return out

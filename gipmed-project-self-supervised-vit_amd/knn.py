@@ -23,6 +23,24 @@ _logger = logging.getLogger("train")
 f32 = torch.float32
 
 
+def tile_slide_metrics(prefix: str, pred: np.ndarray, score: Optional[np.ndarray], labels: np.ndarray, slide_ids) -> "OrderedDict[str, float]":
+    """Per-tile predictions pred [N], positive-class scores score [N] (None: one class only), labels [N], slide_ids [N] (any
+    hashable per tile; tiles of a slide share one) -> OrderedDict(<prefix>top1 in percent, and with scores <prefix>auc_per_patch,
+    <prefix>auc_per_slide): the slide score is the mean of its patch scores, the slide label its first tile's.  Shared by the
+    k-NN monitor and the linear probe (gipvit/linprobe.py)."""
+    out = OrderedDict()
+    out[prefix + "top1"] = 100.0 * float((pred == labels).mean()) if len(labels) else float("nan")
+    if score is not None and len(labels):
+        out[prefix + "auc_per_patch"] = _auc(labels, score)
+        first, inv = {}, np.empty(len(labels), dtype=np.int64)
+        for i, s in enumerate(slide_ids):                      # slides in order of first appearance
+            inv[i] = first.setdefault(s if not isinstance(s, np.generic) else s.item(), len(first))
+        n = len(first)
+        mean = np.bincount(inv, weights=score, minlength=n) / np.bincount(inv, minlength=n)
+        out[prefix + "auc_per_slide"] = _auc(labels[np.unique(inv, return_index=True)[1]], mean)      # a slide's label: its first tile's
+    return out
+
+
 def knn_metrics(votes: np.ndarray, labels: np.ndarray, slide_ids: np.ndarray) -> "OrderedDict[str, float]":
     """votes [N, C] (>= 0), labels [N] in [0, C), slide_ids [N] (any hashable per tile; tiles of a slide share one) ->
     OrderedDict(knn_top1 in percent, and for C > 1: knn_auc_per_patch, knn_auc_per_slide).  The predicted class is the arg-max
@@ -32,19 +50,40 @@ def knn_metrics(votes: np.ndarray, labels: np.ndarray, slide_ids: np.ndarray) ->
     labels = np.asarray(labels).reshape(-1).astype(np.int64)
     if votes.ndim != 2 or votes.shape[0] != labels.shape[0] or len(slide_ids) != labels.shape[0]:
         raise ValueError(f"knn_metrics: votes {votes.shape}, labels {labels.shape} and {len(slide_ids)} slide ids do not match")
-    out = OrderedDict()
-    out["knn_top1"] = 100.0 * float((np.argmax(votes, axis=1) == labels).mean()) if len(labels) else float("nan")
-    if votes.shape[1] > 1 and len(labels):
+    score = None
+    if votes.shape[1] > 1:
         tot = votes.sum(1)
         score = np.divide(votes[:, 1], tot, out=np.zeros_like(tot), where=tot > 0)
-        out["knn_auc_per_patch"] = _auc(labels, score)
-        first, inv = {}, np.empty(len(labels), dtype=np.int64)
-        for i, s in enumerate(slide_ids):                      # slides in order of first appearance
-            inv[i] = first.setdefault(s if not isinstance(s, np.generic) else s.item(), len(first))
-        n = len(first)
-        mean = np.bincount(inv, weights=score, minlength=n) / np.bincount(inv, minlength=n)
-        out["knn_auc_per_slide"] = _auc(labels[np.unique(inv, return_index=True)[1]], mean)      # a slide's label: its first tile's
-    return out
+    return tile_slide_metrics("knn_", np.argmax(votes, axis=1), score, labels, slide_ids)
+
+
+def centred_window(data: torch.Tensor, img: int) -> torch.Tensor:
+    """The centred img x img window of larger uint8 tiles (a device slice copy); everything else goes to the runner as it is."""
+    if data.dtype == torch.uint8 and data.dim() == 4 and data.shape[1] == data.shape[2] and data.shape[1] > img:
+        o = (data.shape[1] - img) // 2
+        return data[:, o:o + img, o:o + img, :].contiguous()
+    return data
+
+
+def collect_features(loader, C: int, features, who: str):
+    """-> (features f32 [N, D] device, labels int64 [N], slide ordinal int64 [N], slides left out) over the slides whose label
+    is inside [0, C); ``features(data)`` maps one chunk of tiles to its f32 [n, D] rows."""
+    if hasattr(loader, "reset_counter"):
+        loader.reset_counter()
+    feats, labels, slides, skipped, ordinal = [], [], [], 0, 0
+    for mb in loader:
+        y = int(mb["Label"].reshape(-1)[0])
+        if 0 <= y < C:
+            f = features(mb["Data"])
+            feats.append(f)
+            labels.append(np.full(f.shape[0], y, dtype=np.int64))
+            slides.append(np.full(f.shape[0], ordinal, dtype=np.int64))
+        if mb["Is Last Batch"]:
+            skipped += not 0 <= y < C
+            ordinal += 1
+    if not feats:
+        raise ValueError(f"{who}: no slide with a label in [0, {C}) in the loader")
+    return torch.cat(feats), np.concatenate(labels), np.concatenate(slides), skipped
 
 
 class KnnMonitor:
@@ -62,12 +101,7 @@ class KnnMonitor:
         self.bank = self.bank_labels = None
 
     def _window(self, data: torch.Tensor) -> torch.Tensor:
-        """The centred img x img window of larger uint8 tiles (a device slice copy); everything else goes to the runner as it is."""
-        img = self.runner.img
-        if data.dtype == torch.uint8 and data.dim() == 4 and data.shape[1] == data.shape[2] and data.shape[1] > img:
-            o = (data.shape[1] - img) // 2
-            return data[:, o:o + img, o:o + img, :].contiguous()
-        return data
+        return centred_window(data, self.runner.img)
 
     def features(self, data: torch.Tensor) -> torch.Tensor:
         """L2-normalised f32 [n, D] CLS features of one chunk of tiles, on the device."""
@@ -81,24 +115,7 @@ class KnnMonitor:
         return out
 
     def _collect(self, loader):
-        """-> (features f32 [N, D] device, labels int64 [N], slide ordinal int64 [N], slides left out) over the slides whose label
-        is inside [0, C)."""
-        if hasattr(loader, "reset_counter"):
-            loader.reset_counter()
-        feats, labels, slides, skipped, ordinal = [], [], [], 0, 0
-        for mb in loader:
-            y = int(mb["Label"].reshape(-1)[0])
-            if 0 <= y < self.C:
-                f = self.features(mb["Data"])
-                feats.append(f)
-                labels.append(np.full(f.shape[0], y, dtype=np.int64))
-                slides.append(np.full(f.shape[0], ordinal, dtype=np.int64))
-            if mb["Is Last Batch"]:
-                skipped += not 0 <= y < self.C
-                ordinal += 1
-        if not feats:
-            raise ValueError(f"KnnMonitor: no slide with a label in [0, {self.C}) in the loader")
-        return torch.cat(feats), np.concatenate(labels), np.concatenate(slides), skipped
+        return collect_features(loader, self.C, self.features, "KnnMonitor")
 
     def build_bank(self, loader) -> int:
         feats, labels, slides, skipped = self._collect(loader)

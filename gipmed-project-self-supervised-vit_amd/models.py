@@ -13,20 +13,8 @@ from typing import Dict, Optional
 
 import torch
 
-from .engine import ARCHS, dino_head_specs, resolve_pool, vit_param_specs
-
-# timm names used by the reference -> (arch, default img size after the documented cfg patch)
-MODEL_REGISTRY = {
-    "vit_tiny_patch16_224": "vit_tiny", "vit_small_patch16_224": "vit_small", "vit_base_patch16_224": "vit_base",
-    "vit_small_patch16_224_dino": "vit_small", "vit_base_patch16_224_dino": "vit_base",
-    "vit_tiny": "vit_tiny", "vit_small": "vit_small", "vit_base": "vit_base",
-}
-
-
-def resolve_arch(name: str) -> str:
-    if name not in MODEL_REGISTRY:
-        raise ValueError(f"unknown model '{name}'; this build covers {sorted(MODEL_REGISTRY)}")
-    return MODEL_REGISTRY[name]
+from .archs import ARCHS, MODEL_REGISTRY, resolve_arch  # noqa: F401  (the tables live where no library is loaded)
+from .engine import dino_head_specs, resolve_pool, vit_param_specs
 
 
 def _trunc_normal_(t: torch.Tensor, std: float, gen: torch.Generator):

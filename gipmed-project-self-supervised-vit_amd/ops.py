@@ -476,6 +476,71 @@ def knn_vote(q, bank, labels, k: int, temp: float, C: int, *, n_split: int = 0, 
     return (votes, top_sim, top_idx) if want_topk else votes
 
 
+_linprobe_workspace: dict = {}   # device -> uint8 scratch of linprobe_train / linprobe_predict, grown on demand and kept
+
+
+def _linprobe_scratch(dev, M: int, H: int, C: int, F: int):
+    need = L.lib.gv_linprobe_workspace_bytes(M, H, C, F)
+    if need < 0:
+        raise L.GipvitError(f"gv_linprobe_workspace_bytes: {L.lib.gv_last_error().decode()}")
+    ws = _linprobe_workspace.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _linprobe_workspace[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _linprobe_heads(who: str, W, b, x):
+    """Shapes of the heads against the features -> (H, C, F)."""
+    _chk(W, f32, "W"); _chk(b, f32, "b"); _chk(x, f32, "x")
+    if W.dim() != 3 or b.dim() != 2 or tuple(b.shape) != tuple(W.shape[:2]) or not (W.is_contiguous() and b.is_contiguous()):
+        raise ValueError(f"{who}: expected contiguous W [H, C, F] and b [H, C], got {tuple(W.shape)} and {tuple(b.shape)}")
+    if x.dim() != 2 or x.shape[1] != W.shape[2] or x.stride(1) != 1:
+        raise ValueError(f"{who}: expected x [N, {W.shape[2]}] with unit column stride, got {tuple(x.shape)} strides {x.stride()}")
+    if W.device != x.device or b.device != x.device:
+        raise TypeError(f"{who}: W, b and x must live on one device")
+    return tuple(W.shape)
+
+
+def linprobe_train(W, b, mW, mb, lr, wd, x, labels, rows, loss_sum, batch: int, lr_scale: float = 1.0, momentum: float = 0.9):
+    """SGD steps of H linear heads on frozen features (gv_linprobe_train), in place: W / mW f32 [H, C, F], b / mb f32 [H, C],
+    lr / wd f32 [H], x f32 [N, F] (row stride free, a multiple of 4), labels int32 [N], rows int32 [n_rows] (the visiting order:
+    ceil(n_rows / batch) steps, the last one over the rows that are left), loss_sum f32 [H] (accumulated: sum of -log p[label]).
+    The step is torch.optim.SGD(lr[h] * lr_scale, momentum, weight_decay=wd[h]) under a mean cross-entropy loss."""
+    H, C, F = _linprobe_heads("linprobe_train", W, b, x)
+    for t, shape, nm in ((mW, (H, C, F), "mW"), (mb, (H, C), "mb"), (lr, (H,), "lr"), (wd, (H,), "wd"), (loss_sum, (H,), "loss_sum")):
+        _chk(t, f32, nm)
+        if tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"linprobe_train: {nm} must be a contiguous f32 {list(shape)} on {x.device}, got {tuple(t.shape)} on {t.device}")
+    _chk(labels, torch.int32, "labels"); _chk(rows, torch.int32, "rows")
+    if labels.dim() != 1 or labels.shape[0] != x.shape[0] or not labels.is_contiguous() or labels.device != x.device:
+        raise ValueError(f"linprobe_train: labels must be a contiguous int32 [{x.shape[0]}] on {x.device}, got {tuple(labels.shape)}")
+    if rows.dim() != 1 or not rows.is_contiguous() or rows.device != x.device:
+        raise ValueError(f"linprobe_train: rows must be a contiguous int32 vector on {x.device}, got {tuple(rows.shape)}")
+    ws = _linprobe_scratch(x.device, batch, H, C, F)
+    a = L.gv_linprobe_train_args(W.data_ptr(), b.data_ptr(), mW.data_ptr(), mb.data_ptr(), lr.data_ptr(), wd.data_ptr(), x.data_ptr(),
+                                 labels.data_ptr(), rows.data_ptr(), loss_sum.data_ptr(), ws.data_ptr(), ws.numel(), x.stride(0),
+                                 x.shape[0], F, H, C, rows.shape[0], batch, lr_scale, momentum)
+    L.call("gv_linprobe_train", a, _stream())
+
+
+def linprobe_predict(W, b, x, labels=None):
+    """Softmax of the H heads' logits (gv_linprobe_predict): W f32 [H, C, F], b f32 [H, C], x f32 [Q, F] -> prob f32 [Q, H, C];
+    with ``labels`` int32 [Q] also -> (prob, loss f32 [H]), loss[h] = sum over q of -log prob[q, h, labels[q]]."""
+    H, C, F = _linprobe_heads("linprobe_predict", W, b, x)
+    Q = x.shape[0]
+    if labels is not None:
+        _chk(labels, torch.int32, "labels")
+        if labels.dim() != 1 or labels.shape[0] != Q or not labels.is_contiguous() or labels.device != x.device:
+            raise ValueError(f"linprobe_predict: labels must be a contiguous int32 [{Q}] on {x.device}, got {tuple(labels.shape)}")
+    ws = _linprobe_scratch(x.device, max(1, min(Q, 4096)), H, C, F)
+    prob = torch.empty(Q, H, C, dtype=f32, device=x.device)
+    loss = torch.empty(H, dtype=f32, device=x.device) if labels is not None else None
+    a = L.gv_linprobe_predict_args(W.data_ptr(), b.data_ptr(), x.data_ptr(), _p(labels), prob.data_ptr(), _p(loss), ws.data_ptr(), ws.numel(),
+                                   x.stride(0), Q, F, H, C)
+    L.call("gv_linprobe_predict", a, _stream())
+    return prob if labels is None else (prob, loss)
+
+
 def weightnorm_fwd(v, g, w, rows: int, C: int):
     L.call("gv_weightnorm_fwd" + _sfx(w), L.gv_weightnorm_fwd_args(v.data_ptr(), g.data_ptr(), w.data_ptr(), rows, C), _stream())
 

@@ -855,6 +855,61 @@ int gv_knn_vote(const gv_knn_vote_args* a, void* stream);
  * for arguments the call would refuse.  Touches no GPU.                                                                    */
 int64_t gv_knn_workspace_bytes(int32_t Q, int32_t Nb, int32_t k, int32_t n_split);
 
+/* ---- linear probe on frozen features: DINO's eval_linear as H linear heads over F features and C classes, trained together so
+ * that every head shares one read of every feature row (gipvit/linprobe.py; a grid of learning rates in one pass over the bank).
+ * State, caller-owned f32: W [H, C, F], b [H, C], momentum buffers mW / mb of the same shapes, lr [H], wd [H].
+ * gv_linprobe_train performs ceil(n_rows / batch) SGD steps over x[rows[...]], all enqueued on the stream; the last step takes the
+ * n_rows % batch rows that are left and averages over that count.  One step on the rows r_0 .. r_{m-1}, per head h, in f32:
+ *     z[h,j,c] = b[h,c] + sum_f W[h,c,f] x[r_j,f];  p = softmax_c(z) (max-subtracted);  loss_sum[h] += sum_j -log p[h,j,y_j]
+ *     g[h,j,c] = (p[h,j,c] - [c == y_j]) / m
+ *     dW[h,c,:] = sum_j g[h,j,c] x[r_j,:] + wd[h] W[h,c,:];   db[h,c] = sum_j g[h,j,c] + wd[h] b[h,c]
+ *     mW = momentum mW + dW;  W -= lr[h] lr_scale mW          (same for b)
+ * -- torch.optim.SGD(momentum, weight_decay) on nn.Linear heads under a mean cross-entropy loss.  loss_sum is accumulated across
+ * calls (the caller zeroes it).  A step is two launches: logits on the f32 MFMA per 64-row tile (g and per-tile partial sums go to
+ * the workspace), then dW = g^T x per 32 columns of F with the update in the epilogue (dW never reaches memory).  No grid barrier,
+ * no atomics, every sum in a fixed order that does not depend on the grid: the result, loss_sum included, is bitwise the same run
+ * to run.  Every load is bounds-checked (padding is zero-filled, never read).  A label outside [0, C) or a row index outside
+ * [0, N) is never used as an index: that row contributes nothing (the step still divides by m).
+ * Limits: 1 <= C <= 32, H >= 1, H * C <= 64, F a multiple of 4 and <= 4096, ldx >= F and a multiple of 4, x and W 16-byte aligned,
+ * 1 <= batch <= 4096, n_rows >= 1, N >= 1, lr_scale finite and >= 0, 0 <= momentum < 1,
+ * workspace (16-byte aligned) of gv_linprobe_workspace_bytes(batch, H, C, F) bytes. */
+typedef struct {
+    float*         W;        /* f32 [H, C, F]                                                            */
+    float*         b;        /* f32 [H, C]                                                               */
+    float*         mW;       /* f32 [H, C, F] momentum buffer                                            */
+    float*         mb;       /* f32 [H, C]    momentum buffer                                            */
+    const float*   lr;       /* f32 [H]                                                                  */
+    const float*   wd;       /* f32 [H]                                                                  */
+    const float*   x;        /* f32 [N, F], row stride ldx                                               */
+    const int32_t* labels;   /* i32 [N]                                                                  */
+    const int32_t* rows;     /* i32 [n_rows]: the visiting order, any multiset of row indices            */
+    float*         loss_sum; /* f32 [H], accumulated                                                     */
+    void*          workspace; int64_t workspace_bytes;
+    int64_t ldx;
+    int32_t N, F, H, C, n_rows, batch;
+    float   lr_scale;        /* the schedule's factor for these steps                                    */
+    float   momentum;        /* SGD momentum (DINO: 0.9)                                                 */
+} gv_linprobe_train_args;
+int gv_linprobe_train(const gv_linprobe_train_args* a, void* stream);
+/* prob[q, h, c] = softmax_c of the same logits for every row of x [Q, F]; with labels and loss non-NULL also loss[h] = the sum
+ * over q of -log prob[q, h, labels[q]] (overwritten; a label outside [0, C) adds nothing).  Same limits; any Q >= 1 (chunks of
+ * 4096 rows), workspace of gv_linprobe_workspace_bytes(min(Q, 4096), H, C, F) bytes.                                          */
+typedef struct {
+    const float*   W;        /* f32 [H, C, F]                                                            */
+    const float*   b;        /* f32 [H, C]                                                               */
+    const float*   x;        /* f32 [Q, F], row stride ldx                                               */
+    const int32_t* labels;   /* i32 [Q]; may be NULL when loss is                                        */
+    float*         prob;     /* f32 [Q, H, C]                                                            */
+    float*         loss;     /* f32 [H]; may be NULL                                                     */
+    void*          workspace; int64_t workspace_bytes;
+    int64_t ldx;
+    int32_t Q, F, H, C;
+} gv_linprobe_predict_args;
+int gv_linprobe_predict(const gv_linprobe_predict_args* a, void* stream);
+/* scratch bytes of a gv_linprobe_train call with this batch (gv_linprobe_predict: batch = min(Q, 4096)); -1 with gv_last_error()
+ * set for arguments the call would refuse.  Touches no GPU.                                                                    */
+int64_t gv_linprobe_workspace_bytes(int32_t batch, int32_t H, int32_t C, int32_t F);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@ import argparse
 import csv
 import json
 import logging
+import math
 import os
 import sys
 import time
@@ -102,6 +103,19 @@ def build_parser():
     g.add_argument("--knn-temp", type=float, default=0.07, help="--knn-monitor: a neighbour votes with weight exp(similarity / temp)")
     g.add_argument("--knn-bank-tiles", type=int, default=None, help="--knn-monitor: tiles per training slide in the bank (default: --num_tiles)")
     g.add_argument("--knn-rate", type=int, default=1, help="--knn-monitor: evaluate every N epochs")
+    g.add_argument("--linear-probe", action="store_true", help="DINO: linear probe on the teacher's frozen features (DINO's eval_linear on cached "
+                   "features: bank = training-fold slides, queries = evaluation fold; gv_linprobe_train): eval_linear_top1 / eval_linear_loss / "
+                   "eval_linear_auc_per_patch / eval_linear_auc_per_slide in summary.csv")
+    g.add_argument("--linprobe-lrs", type=float, nargs="+", default=[0.001], help="--linear-probe: one head per base rate, trained together (a "
+                   "head's rate is lr * batch / 256); with more than one the head with the lowest loss on held-out bank slides is reported")
+    g.add_argument("--linprobe-epochs", type=int, default=100, help="--linear-probe: passes over the bank (cosine schedule per epoch)")
+    g.add_argument("--linprobe-batch", type=int, default=1024, help="--linear-probe: minibatch rows (1..4096)")
+    g.add_argument("--linprobe-layers", type=int, default=4, help="--linear-probe: the CLS tokens of the last N blocks are the features")
+    g.add_argument("--linprobe-avgpool", action="store_true", help="--linear-probe: append the mean of the last block's patch tokens")
+    g.add_argument("--linprobe-wd", type=float, default=0.0, help="--linear-probe: weight decay of the heads")
+    g.add_argument("--linprobe-rate", type=int, default=0, help="--linear-probe: 0 = probe after the last epoch only, N >= 1 = every N epochs and the last")
+    g.add_argument("--linprobe-holdout", type=float, default=0.2, help="--linear-probe, more than one rate: share of the bank slides held out to "
+                   "choose the head on (0 < share <= 0.5)")
     g.add_argument("--tile-size", type=int, default=256)
     g.add_argument("--batches-per-epoch", type=int, default=100, help="synthetic source only")
     g.add_argument("--synthetic-slides", type=int, default=4, help="synthetic source only: slides of the inference set")
@@ -225,6 +239,41 @@ def check_supported(args, log=_logger.warning):
         if args.tile_size < args.global_crop_size:
             raise SystemExit(f"--knn-monitor: the teacher sees {args.global_crop_size}-px images, the centred window of a {args.tile_size}-px "
                              "tile (--tile-size) cannot be smaller than that")
+    if args.linear_probe:
+        if not args.dino:
+            raise SystemExit("--linear-probe scores the DINO teacher's frozen features: it needs --dino (a supervised run has validate())")
+        lrs = list(args.linprobe_lrs or [])
+        if not lrs or not all(math.isfinite(v) and v > 0 for v in lrs):
+            raise SystemExit(f"--linprobe-lrs {lrs}: one positive finite base rate per head, at least one")
+        if len(lrs) * (args.num_classes or 2) > 64:
+            raise SystemExit(f"--linprobe-lrs: {len(lrs)} heads x {args.num_classes or 2} classes is past the 64 logit columns of gv_linprobe_train")
+        if args.linprobe_epochs < 1:
+            raise SystemExit(f"--linprobe-epochs {args.linprobe_epochs}: at least one pass over the bank")
+        if not 1 <= args.linprobe_batch <= 4096:
+            raise SystemExit(f"--linprobe-batch {args.linprobe_batch}: 1 .. 4096 rows per step (gv_linprobe_train)")
+        from gipvit.archs import ARCHS, resolve_arch       # plain tables: nothing is loaded for them
+        spec = ARCHS[resolve_arch(args.model)]
+        if not 1 <= args.linprobe_layers <= spec["depth"]:
+            raise SystemExit(f"--linprobe-layers {args.linprobe_layers}: the last 1 .. {spec['depth']} blocks of {args.model}")
+        width = (args.linprobe_layers + bool(args.linprobe_avgpool)) * spec["embed_dim"]
+        if width > 4096:
+            raise SystemExit(f"--linprobe-layers {args.linprobe_layers}{' --linprobe-avgpool' if args.linprobe_avgpool else ''}: {width} features per "
+                             f"tile at width {spec['embed_dim']}, gv_linprobe_train stops at 4096")
+        if not args.linprobe_wd >= 0:
+            raise SystemExit(f"--linprobe-wd {args.linprobe_wd}: weight decay must be >= 0")
+        if args.linprobe_rate < 0:
+            raise SystemExit(f"--linprobe-rate {args.linprobe_rate}: 0 = after the last epoch only, N >= 1 = every N epochs and the last")
+        if not 0 < args.linprobe_holdout <= 0.5:
+            raise SystemExit(f"--linprobe-holdout {args.linprobe_holdout}: the share of bank slides held out, 0 < share <= 0.5")
+        if args.test_fold in (-1, "-1"):
+            raise SystemExit("--test_fold -1 with --linear-probe: no evaluation fold is left to score the heads on")
+        if args.tile_size < args.global_crop_size:
+            raise SystemExit(f"--linear-probe: the teacher sees {args.global_crop_size}-px images, the centred window of a {args.tile_size}-px "
+                             "tile (--tile-size) cannot be smaller than that")
+        names = monitor_metric_names(args)
+        if resolve_eval_metric(args.eval_metric, bool(args.knn_monitor), True) not in names:
+            raise SystemExit(f"--eval-metric {args.eval_metric}: the monitors of this run report {names} (a bare name is the k-NN monitor's "
+                             "when that is on, else the probe's)")
     if args.supervised and args.dino:
         raise SystemExit("--supervised (fine-tune with labels, train.py:715-717) and --dino (self-supervised) exclude each other")
     # mixup / cutmix / BCE (train.py:752-771, 828-846): the supervised step's batch, target and loss
@@ -294,6 +343,34 @@ def check_token_limits(args):
         if args.extract_features and args.precision == "fp32" and n > ATTN_F32_MAX_TOKENS:
             raise SystemExit(f"--precision fp32 with {flag} {px}: {n} tokens per image, the fp32 operand mode's attention stops at "
                              f"{ATTN_F32_MAX_TOKENS} tokens (256 px); larger tiles run in the 16-bit mode")
+
+
+def monitor_metric_names(args):
+    """The metrics the monitors of a --dino run report, in the fixed order of their summary.csv columns: the k-NN monitor's, then
+    the linear probe's; the AUCs only with more than one class."""
+    many = (args.num_classes or 2) > 1
+    knn = (["knn_top1"] + (["knn_auc_per_patch", "knn_auc_per_slide"] if many else [])) if args.knn_monitor else []
+    probe = (["linear_top1", "linear_loss"] + (["linear_auc_per_patch", "linear_auc_per_slide"] if many else [])) if args.linear_probe else []
+    return knn + probe
+
+
+def summary_row(epoch, train_metrics, eval_metrics, monitor_names, lr) -> "OrderedDict":
+    """One row of summary.csv.  The header is written once, so every epoch's row has the same columns in the same order:
+    validate()'s metrics as they come, then one column per name in ``monitor_names`` (the k-NN monitor's, then the probe's), in
+    that order whichever of them ran this epoch -- empty where a monitor did not run (--knn-rate / --linprobe-rate)."""
+    row = OrderedDict(epoch=epoch, **{"train_" + k: v for k, v in train_metrics.items()})
+    row.update(("eval_" + k, v) for k, v in eval_metrics.items() if k not in monitor_names)
+    row.update(("eval_" + k, eval_metrics.get(k, "")) for k in monitor_names)
+    row["lr"] = lr
+    return row
+
+
+def resolve_eval_metric(name: str, knn: bool, probe: bool) -> str:
+    """--eval-metric among the metrics of a --dino run's monitors: a name that already starts knn_ / linear_ is taken as given, a
+    bare one is the k-NN monitor's when that is on ('top1' -> 'knn_top1'), else the linear probe's when only the probe is."""
+    if name.startswith("knn_") or name.startswith("linear_"):
+        return name
+    return ("knn_" + name) if knn else ("linear_" + name) if probe else name
 
 
 def mix_active(args) -> bool:
@@ -458,13 +535,14 @@ def main(argv=None, transform=None):
     inf_loader = None
     # --knn-monitor: the bank comes from the training fold, the queries from the evaluation fold; --extract_features runs alone
     want_knn = bool(args.knn_monitor) and not args.extract_features
+    want_probe = bool(args.linear_probe) and not args.extract_features     # the same bank and query loaders, shared when both are on
     knn_bank_loader = knn_query_loader = None
     bank_tiles = args.knn_bank_tiles or args.num_tiles
     if synthetic:
         source = D.SyntheticTiles(B, tile, args.batches_per_epoch, args.num_classes or 2, seed=args.seed + rank)
         if not args.no_validate and (not args.dino or args.extract_features):
             inf_loader = D.SyntheticSlides(args.synthetic_slides, min(args.num_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 99)
-        if want_knn:
+        if want_knn or want_probe:
             knn_bank_loader = D.SyntheticSlides(args.synthetic_slides, min(bank_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 77)
             knn_query_loader = D.SyntheticSlides(args.synthetic_slides, min(args.num_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 99)
     elif args.dataset.startswith("tiles:") or args.data_dir:
@@ -476,7 +554,7 @@ def main(argv=None, transform=None):
         want_eval = not args.no_validate and (not args.dino or args.extract_features)
         no_val_fold = args.test_fold in (-1, "-1")
         train_slides = D.select_fold(slides, args.test_fold, True)
-        if args.supervised or want_knn or (want_eval and not no_val_fold):
+        if args.supervised or want_knn or want_probe or (want_eval and not no_val_fold):
             eval_slides = D.select_fold(slides, args.test_fold, False)       # raises when evaluation was asked for and no slide is in the fold
         else:
             eval_slides = []
@@ -494,7 +572,7 @@ def main(argv=None, transform=None):
         if want_eval:
             inf_loader = D.InferTiles(root, tile, args.tiles_per_iter, args.num_tiles, seed=args.seed, dataset_name=args.dataset,
                                       workers=args.workers, slides=eval_slides)
-        if want_knn:
+        if want_knn or want_probe:
             knn_bank_loader = D.InferTiles(root, tile, args.tiles_per_iter, bank_tiles, seed=args.seed + 1, dataset_name=args.dataset,
                                            workers=args.workers, slides=train_slides)
             knn_query_loader = D.InferTiles(root, tile, args.tiles_per_iter, args.num_tiles, seed=args.seed, dataset_name=args.dataset,
@@ -570,25 +648,30 @@ def main(argv=None, transform=None):
             if ema_decay is not None:
                 runner_ema = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.Wema, global_pool=eng.pool)
 
-    monitor = None
-    knn_names = []
-    if want_knn:        # the teacher backbone at its own image size; larger tiles contribute their centred window (gipvit/knn.py)
-        from gipvit.knn import KnnMonitor
+    monitor = probe = None
+    knn_names, probe_names = [], []
+    if want_knn or want_probe:        # the teacher backbone at its own image size; larger tiles contribute their centred window (gipvit/knn.py)
         knn_runner = FeatureExtractor(arch, img, eval_B, 0, mean, std, dev, weights=Weights(eng.arena, "backbone.", teacher=True, fp32=args.precision == "fp32"))
+    if want_knn:
+        from gipvit.knn import KnnMonitor
         monitor = KnnMonitor(knn_runner, k=args.knn_k, temp=args.knn_temp, num_classes=args.num_classes or 2, primary=primary)
         knn_names = ["knn_top1"] + (["knn_auc_per_patch", "knn_auc_per_slide"] if monitor.C > 1 else [])
+    if want_probe:      # heads on the same runner's last-layer CLS tokens (gipvit/linprobe.py)
+        from gipvit.linprobe import LinearProbe
+        probe = LinearProbe(knn_runner, num_classes=args.num_classes or 2, lrs=args.linprobe_lrs, weight_decay=args.linprobe_wd,
+                            epochs=args.linprobe_epochs, batch=args.linprobe_batch, n_last=args.linprobe_layers, avgpool=args.linprobe_avgpool,
+                            holdout=args.linprobe_holdout, seed=args.seed, primary=primary)
+        probe_names = ["linear_top1", "linear_loss"] + (["linear_auc_per_patch", "linear_auc_per_slide"] if probe.C > 1 else [])
 
     # ---- output dir, args.yaml, saver (train.py:854-879)
-    eval_metric = args.eval_metric                              # train.py:849
-    if monitor is not None and not eval_metric.startswith("knn_"):
-        eval_metric = "knn_" + eval_metric                      # the default 'top1' selects knn_top1
-    decreasing = eval_metric == "loss"                          # train.py:866
+    eval_metric = resolve_eval_metric(args.eval_metric, monitor is not None, probe is not None)      # train.py:849; 'top1' -> knn_top1
+    decreasing = eval_metric in ("loss", "linear_loss")         # train.py:866
     saver = output_dir = None
     if primary:
         exp = args.experiment or "-".join([time.strftime("%Y%m%d-%H%M%S"), args.model.replace("/", "_"), str(img)])
         output_dir = os.path.join(args.output or "./output/train", exp, args.subexperiment or "")
         os.makedirs(output_dir, exist_ok=True)
-        saver = CheckpointSaver(output_dir, args.model, vars(args), decreasing=(decreasing or inf_loader is None or args.dino) and monitor is None,
+        saver = CheckpointSaver(output_dir, args.model, vars(args), decreasing=decreasing if (monitor is not None or probe is not None) else (decreasing or inf_loader is None or args.dino),
                                 max_history=args.checkpoint_hist)
         with open(os.path.join(output_dir, "args.yaml"), "w") as f:
             f.write(args_text)
@@ -728,20 +811,21 @@ def main(argv=None, transform=None):
             if runner_ema is not None and not args.extract_features:       # train.py:943-955: the EMA model's metrics win
                 eval_metrics = validate(runner_ema, inf_loader, smoothing=args.smoothing, log_interval=args.log_interval, primary=primary,
                                         log_suffix=" (EMA)")
-        knn_blank = []
         if monitor is not None:
             if (epoch + 1) % args.knn_rate == 0:                # the teacher moved: the bank is rebuilt at every evaluation
                 monitor.build_bank(knn_bank_loader)
                 eval_metrics.update(monitor.evaluate(knn_query_loader))
-            else:
-                knn_blank = knn_names                           # summary.csv keeps its columns, empty for this epoch
+        if probe is not None:
+            if epoch == args.epochs - 1 or (args.linprobe_rate >= 1 and (epoch + 1) % args.linprobe_rate == 0):
+                probe.fit(knn_bank_loader)                      # fresh heads on the teacher as it stands
+                eval_metrics.update(probe.evaluate(knn_query_loader))
         if args.extract_features:
             if primary:
                 _logger.info(f"*** features of {int(eval_metrics.get('slides', 0))} slides written to {args.features_dir}")
             break
         if primary:
-            row = OrderedDict(epoch=epoch, **{"train_" + k: v for k, v in train_metrics.items()}, **{"eval_" + k: v for k, v in eval_metrics.items()},
-                              **{"eval_" + k: "" for k in knn_blank}, lr=logged_lr(cur_lr))
+            # the monitors' columns stay in one order, empty for a monitor that did not run this epoch
+            row = summary_row(epoch, train_metrics, eval_metrics, knn_names + probe_names, logged_lr(cur_lr))
             fn = os.path.join(output_dir, "summary.csv")
             new = not os.path.exists(fn)
             with open(fn, "a") as f:
@@ -752,12 +836,13 @@ def main(argv=None, transform=None):
             if run is not None:
                 run.log({k: v for k, v in row.items() if v != ""})
             optim = {"exp_avg": eng.arena.m, "exp_avg_sq": eng.arena.v, "step": eng.t}
-            if eval_metrics:
-                if eval_metric not in eval_metrics:
-                    raise SystemExit(f"--eval-metric {eval_metric}: {'the k-NN monitor' if monitor is not None else 'validate()'} reports {list(eval_metrics)}")
+            if eval_metric in eval_metrics:
                 save_metric, name = eval_metrics[eval_metric], "eval " + eval_metric          # train.py:970-973
-            elif monitor is not None:
-                save_metric, name = None, "eval " + eval_metric                               # not evaluated this epoch (--knn-rate)
+            elif eval_metric in knn_names + probe_names or (not eval_metrics and (monitor is not None or probe is not None)):
+                save_metric, name = None, "eval " + eval_metric                               # not evaluated this epoch (--knn-rate / --linprobe-rate)
+            elif eval_metrics:
+                who = "the monitors of this run report" if probe is not None else "the k-NN monitor reports" if monitor is not None else "validate() reports"
+                raise SystemExit(f"--eval-metric {eval_metric}: {who} {list(eval_metrics)}")
             else:
                 save_metric, name = train_metrics["loss"], "train loss"
             best, best_ep = saver.save_checkpoint(epoch, eng.arena.state_dict(), optim, metric=save_metric, extra=extra_state())
