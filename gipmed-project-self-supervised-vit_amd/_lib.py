@@ -167,6 +167,14 @@ gv_linprobe_train_args = _struct("gv_linprobe_train_args", [
 gv_linprobe_predict_args = _struct("gv_linprobe_predict_args", [
     ("W", vp), ("b", vp), ("x", vp), ("labels", vp), ("prob", vp), ("loss", vp), ("workspace", vp), ("workspace_bytes", i64), ("ldx", i64),
     ("Q", i32), ("F", i32), ("H", i32), ("C", i32)])
+gv_mil_train_args = _struct("gv_mil_train_args", [
+    ("params", vp), ("m", vp), ("v", vp), ("x", vp), ("bag_ptr", vp), ("labels", vp), ("bags", vp), ("loss_sum", vp),
+    ("workspace", vp), ("workspace_bytes", i64), ("ldx", i64), ("N", i32), ("F", i32), ("L", i32), ("C", i32), ("n_all_bags", i32), ("n_bags", i32),
+    ("batch", i32), ("max_bag", i32), ("step0", i32), ("lr", f32), ("lr_scale", f32), ("wd", f32), ("beta1", f32), ("beta2", f32), ("eps", f32)])
+gv_mil_predict_args = _struct("gv_mil_predict_args", [
+    ("params", vp), ("x", vp), ("bag_ptr", vp), ("labels", vp), ("bags", vp), ("prob", vp), ("loss", vp), ("attn", vp), ("score", vp),
+    ("workspace", vp), ("workspace_bytes", i64), ("ldx", i64), ("N", i32), ("F", i32), ("L", i32), ("C", i32), ("n_all_bags", i32), ("n_bags", i32),
+    ("max_bag", i32), ("accumulate", i32)])
 
 # entry point -> argument struct (every `int gv_*(const args*, void* stream)` of the header)
 ENTRY_POINTS = {
@@ -191,10 +199,11 @@ ENTRY_POINTS = {
     "gv_tokens_bwd_f32": gv_tokens_bwd_args, "gv_l2norm_fwd_f32": gv_l2norm_fwd_args, "gv_l2norm_bwd_f32": gv_l2norm_bwd_args,
     "gv_weightnorm_fwd_f32": gv_weightnorm_fwd_args, "gv_dino_loss_f32": gv_dino_loss_args,
     "gv_knn_vote": gv_knn_vote_args, "gv_linprobe_train": gv_linprobe_train_args, "gv_linprobe_predict": gv_linprobe_predict_args,
+    "gv_mil_train": gv_mil_train_args, "gv_mil_predict": gv_mil_predict_args,
     "gv_token_mean_fwd": gv_token_mean_fwd_args, "gv_token_mean_bwd": gv_token_mean_bwd_args, "gv_token_mean_bwd_f32": gv_token_mean_bwd_args,
 }
 PLAIN_SYMBOLS = ("gv_version", "gv_last_error", "gv_target", "gv_act_format", "gv_linear_workspace_bytes", "gv_workspace_bytes", "gv_linear_timing", "gv_linear_timing_read",
-                 "gv_linear_ln_blocks", "gv_knn_workspace_bytes", "gv_linprobe_workspace_bytes")
+                 "gv_linear_ln_blocks", "gv_knn_workspace_bytes", "gv_linprobe_workspace_bytes", "gv_mil_workspace_bytes")
 
 
 class gv_linear_timing_row(C.Structure):
@@ -239,6 +248,8 @@ def _load():
     lib.gv_knn_workspace_bytes.restype = C.c_int64
     lib.gv_linprobe_workspace_bytes.argtypes = [C.c_int32] * 4
     lib.gv_linprobe_workspace_bytes.restype = C.c_int64
+    lib.gv_mil_workspace_bytes.argtypes = [C.c_int32] * 5
+    lib.gv_mil_workspace_bytes.restype = C.c_int64
     return lib
 
 

@@ -1,0 +1,201 @@
+"""Slide-level attention-MIL probe on frozen teacher features: the third protocol next to the weighted k-NN monitor
+(``gipvit/knn.py``) and the linear probe (``gipvit/linprobe.py``), and the one that scores SLIDES rather than tiles.
+
+A slide is a bag of its tiles' features.  Gated-attention ABMIL (Ilse et al. 2018) scores every tile, s_i = w . (tanh(V x_i + bv)
+* sigmoid(U x_i + bu)) + bw, pools the bag with a = softmax_i(s), z = sum_i a_i x_i, and classifies z with one linear layer.  No
+gradient reaches the features.  It is trained with Adam (cosine factor per epoch as in the linear probe, ``batch`` bags per
+step, one permutation of the bags per epoch) by ``ops.mil_train`` -> gv_mil_train; the attention weights a_i and scores s_i per
+tile are kept by ``tile_attention`` as the heat maps.  Collecting follows the other two monitors: a tile larger than the
+runner's image contributes its centred window, a slide whose label is outside [0, C) is left out; the cached rows come slide by
+slide with non-decreasing ordinals, which is the bag table."""
+from __future__ import annotations
+
+import logging
+import math
+from collections import OrderedDict
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .knn import centred_window, collect_features
+from .linprobe import epoch_permutations, lr_scale_at
+from .validate import _auc
+
+_logger = logging.getLogger("train")
+f32 = torch.float32
+MAX_FEATURES, MAX_HIDDEN, MAX_CLASSES, MAX_BATCH, MAX_BAG = 4096, 256, 32, 64, 4096      # gv_mil_train's limits (include/gipvit.h)
+BETA1, BETA2, EPS = 0.9, 0.999, 1e-8
+
+
+def param_count(L: int, C: int, F: int) -> int:
+    return (2 * L + C) * F + 3 * L + C + 1
+
+
+def param_views(params: torch.Tensor, L: int, C: int, F: int) -> "OrderedDict[str, torch.Tensor]":
+    """Views into a packed parameter vector (include/gipvit.h: VU | Wc | bv | bu | w | bc | bw) under nn.Linear's names."""
+    if params.dim() != 1 or params.shape[0] != param_count(L, C, F):
+        raise ValueError(f"param_views: {tuple(params.shape)} is not the packed vector of L = {L}, C = {C}, F = {F}")
+    o = (2 * L + C) * F
+    return OrderedDict([
+        ("attention_V.weight", params[:L * F].view(L, F)), ("attention_V.bias", params[o:o + L]),
+        ("attention_U.weight", params[L * F:2 * L * F].view(L, F)), ("attention_U.bias", params[o + L:o + 2 * L]),
+        ("attention_w.weight", params[o + 2 * L:o + 3 * L].view(1, L)), ("attention_w.bias", params[o + 3 * L + C:o + 3 * L + C + 1]),
+        ("classifier.weight", params[2 * L * F:o].view(C, F)), ("classifier.bias", params[o + 3 * L:o + 3 * L + C])])
+
+
+def init_params(L: int, C: int, F: int, seed: int) -> torch.Tensor:
+    """The packed f32 parameter vector with nn.Linear's default init, U(-1/sqrt(fan_in), 1/sqrt(fan_in)) for weight and bias,
+    every tensor drawn on the host from its own numpy PCG64([seed, k]) stream (k: its place in ``param_views``)."""
+    params = torch.zeros(param_count(L, C, F), dtype=f32)
+    for k, (name, view) in enumerate(param_views(params, L, C, F).items()):
+        fan_in = L if name.startswith("attention_w") else F
+        bound = 1.0 / math.sqrt(fan_in)
+        draw = np.random.Generator(np.random.PCG64([seed, k])).uniform(-bound, bound, size=tuple(view.shape))
+        view.copy_(torch.from_numpy(draw.astype(np.float32)))
+    return params
+
+
+def bag_table(slide_ordinals) -> np.ndarray:
+    """int32 [n_bags + 1]: the CSR over rows of bags that are runs of equal ordinals.  The ordinals must not decrease."""
+    s = np.asarray(slide_ordinals).reshape(-1)
+    if not len(s):
+        raise ValueError("bag_table: no rows")
+    if (np.diff(s) < 0).any():
+        raise ValueError("bag_table: the slide ordinals must be non-decreasing (the rows of a slide are one contiguous bag)")
+    starts = np.concatenate([[0], np.nonzero(np.diff(s) != 0)[0] + 1, [len(s)]])
+    return starts.astype(np.int32)
+
+
+def mil_metrics(prob: np.ndarray, labels: np.ndarray, loss: float) -> "OrderedDict[str, float]":
+    """prob [n_slides, C], labels [n_slides] in [0, C), loss = the mean cross-entropy -> OrderedDict(mil_top1 in percent over
+    slides, mil_loss, and for C > 1 mil_auc_per_slide with prob[:, 1] as the slide score).  Arg-max, the lowest class on a tie."""
+    prob = np.asarray(prob, dtype=np.float64)
+    labels = np.asarray(labels).reshape(-1).astype(np.int64)
+    if prob.ndim != 2 or prob.shape[0] != labels.shape[0] or not len(labels):
+        raise ValueError(f"mil_metrics: prob {prob.shape} and labels {labels.shape} do not match")
+    out = OrderedDict(mil_top1=100.0 * float((np.argmax(prob, axis=1) == labels).mean()), mil_loss=float(loss))
+    if prob.shape[1] > 1:
+        out["mil_auc_per_slide"] = _auc(labels, prob[:, 1])
+    return out
+
+
+class MilProbe:
+    """``runner``: an ``engine.FeatureExtractor`` of a CLS-token model.  ``fit(bank_loader)`` then ``evaluate(query_loader)``;
+    loaders are ``data.InferTiles`` / ``data.SyntheticSlides``.  ``train(feats, bag_ptr, labels)`` is the device run on its own:
+    features read back from <slide>_features.pt files train without an encoder (``runner`` may then be None with ``features=F``)."""
+
+    def __init__(self, runner, num_classes: int = 2, hidden: int = 128, lr: float = 5e-4, weight_decay: float = 1e-4, epochs: int = 50,
+                 batch: int = 8, n_last: int = 1, seed: int = 0, primary: bool = True, log: Optional[logging.Logger] = None,
+                 features: Optional[int] = None):
+        if not 1 <= num_classes <= MAX_CLASSES:
+            raise ValueError(f"MilProbe: num_classes must be in 1..{MAX_CLASSES} (got {num_classes})")
+        if hidden % 16 or not 16 <= hidden <= MAX_HIDDEN:
+            raise ValueError(f"MilProbe: hidden must be a multiple of 16 in 16..{MAX_HIDDEN} (got {hidden})")
+        if not (math.isfinite(lr) and lr > 0) or not weight_decay >= 0:
+            raise ValueError(f"MilProbe: need a positive finite lr and weight_decay >= 0 (got {lr}, {weight_decay})")
+        if epochs < 1 or not 1 <= batch <= MAX_BATCH:
+            raise ValueError(f"MilProbe: need epochs >= 1 and 1 <= batch <= {MAX_BATCH} (got {epochs}, {batch})")
+        if runner is not None:
+            depth = runner.vit.depth
+            if not 1 <= n_last <= depth:
+                raise ValueError(f"MilProbe: n_last must be in 1..{depth}, the model's depth (got {n_last})")
+            self.F = n_last * runner.D
+        elif features is None:
+            raise ValueError("MilProbe: without a runner, pass features=F (the width of the saved feature rows)")
+        else:
+            self.F = int(features)
+        if self.F % 4 or not 4 <= self.F <= MAX_FEATURES:
+            raise ValueError(f"MilProbe: {self.F} features per tile; the kernels take a multiple of 4 in 4..{MAX_FEATURES}")
+        self.runner, self.C, self.L, self.lr, self.wd, self.epochs, self.batch = runner, num_classes, hidden, float(lr), float(weight_decay), epochs, batch
+        self.n_last, self.seed, self.primary, self.log = n_last, seed, primary, log or _logger
+        self.params = None
+        self.train_loss = None
+
+    def features(self, data: torch.Tensor) -> torch.Tensor:
+        """f32 [n, F] probe features of one chunk of tiles, on the device."""
+        if data.dim() == 5:
+            data = data.squeeze(0)
+        data = centred_window(data.to(self.runner.dev, non_blocking=True), self.runner.img)
+        return self.runner.probe_features(data, self.n_last, False)
+
+    def _collect(self, loader):
+        """-> (features f32 [N, F] device, bag_ptr int32 [n + 1], slide labels int64 [n], slides left out)."""
+        feats, labels, slides, skipped = collect_features(loader, self.C, self.features, "MilProbe")
+        ptr = bag_table(slides)
+        return feats, ptr, labels[ptr[:-1]], skipped
+
+    def _check_bags(self, who: str, feats, bag_ptr):
+        if feats.dim() != 2 or feats.shape[1] != self.F:
+            raise ValueError(f"MilProbe.{who}: features of shape {tuple(feats.shape)}, expected [N, {self.F}]")
+        ptr = np.asarray(bag_ptr).reshape(-1).astype(np.int64)
+        if len(ptr) < 2 or ptr[0] != 0 or ptr[-1] != feats.shape[0] or (np.diff(ptr) < 1).any():
+            raise ValueError(f"MilProbe.{who}: bag_ptr must rise from 0 to {feats.shape[0]}, the feature rows, with no empty bag")
+        if np.diff(ptr).max() > MAX_BAG:
+            raise ValueError(f"MilProbe.{who}: a bag of {int(np.diff(ptr).max())} tiles; the kernels stop at {MAX_BAG} per slide")
+        return ptr.astype(np.int32)
+
+    def fit(self, bank_loader) -> int:
+        """Train a fresh model on the bank's slides.  -> the number of training slides."""
+        feats, ptr, labels, skipped = self._collect(bank_loader)
+        self.train(feats, ptr, labels)
+        if self.primary:
+            self.log.info("MIL probe: %d epochs of %d-slide steps on %d slides, %d tiles (%d slides left out: label outside [0, %d)); epoch loss "
+                          "%.4f -> %.4f", self.epochs, self.batch, len(labels), feats.shape[0], skipped, self.C, self.train_loss[0], self.train_loss[-1])
+        return len(labels)
+
+    def train(self, feats: torch.Tensor, bag_ptr, labels):
+        """The Adam run itself on device features f32 [N, F], the bag table [n + 1] and host slide labels [n]: fresh parameters,
+        one permutation of the bags per epoch, the cosine factor constant within an epoch.  Leaves ``params`` (packed, device),
+        the moments ``m`` / ``v`` and ``train_loss`` ([epochs] mean slide loss per epoch)."""
+        from . import ops
+        ptr = self._check_bags("train", feats, bag_ptr)
+        labels = np.asarray(labels).reshape(-1)
+        n = len(ptr) - 1
+        if labels.shape[0] != n or labels.min() < 0 or labels.max() >= self.C:
+            raise ValueError(f"MilProbe.train: {labels.shape[0]} labels for {n} bags, all must be inside [0, {self.C})")
+        dev = feats.device
+        self.params = init_params(self.L, self.C, self.F, self.seed).to(dev)
+        self.m, self.v = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        order = torch.from_numpy(epoch_permutations(n, self.epochs, self.seed).astype(np.int32)).to(dev)
+        ptr_d, y = torch.from_numpy(ptr).to(dev), torch.from_numpy(labels.astype(np.int32)).to(dev)
+        loss = torch.zeros(self.epochs, 1, dtype=f32, device=dev)      # row e: epoch e's loss_sum
+        max_bag, steps = int(np.diff(ptr).max()), -(-n // self.batch)
+        for e in range(self.epochs):
+            ops.mil_train(self.params, self.m, self.v, feats, ptr_d, y, order[e], loss[e], self.L, self.C, self.batch, max_bag, e * steps,
+                          self.lr, lr_scale_at(e, self.epochs), self.wd, BETA1, BETA2, EPS)
+        self.train_loss = (loss.double().cpu().numpy().reshape(-1) / n).tolist()      # (the copy synchronises)
+
+    def predict(self, feats: torch.Tensor, bag_ptr, labels=None, tiles: bool = False):
+        """-> ops.mil_predict's dict for the bags of ``feats``."""
+        from . import ops
+        if self.params is None:
+            raise RuntimeError("MilProbe.predict: fit first")
+        ptr = self._check_bags("predict", feats, bag_ptr)
+        dev = feats.device
+        y = None if labels is None else torch.from_numpy(np.asarray(labels).astype(np.int32)).to(dev)
+        return ops.mil_predict(self.params, feats, torch.from_numpy(ptr).to(dev), self.L, self.C, int(np.diff(ptr).max()), labels=y,
+                               want_attn=tiles, want_score=tiles)
+
+    def evaluate(self, loader) -> "OrderedDict[str, float]":
+        feats, ptr, labels, skipped = self._collect(loader)
+        out = self.predict(feats, ptr, labels)
+        metrics = mil_metrics(out["prob"].cpu().numpy(), labels, float(out["loss"].double().cpu()) / len(labels))
+        if self.primary:
+            self.log.info("MIL probe: %d query slides, %d tiles (%d left out): %s", len(labels), feats.shape[0], skipped,
+                          "  ".join(f"{n} {v:.4f}" for n, v in metrics.items()))
+        return metrics
+
+    def tile_attention(self, loader):
+        """Per slide of the loader that was kept, in order: (attn f32 [n_tiles], score f32 [n_tiles]) host tensors -- the tile
+        weights after and before the slide's softmax."""
+        feats, ptr, labels, _ = self._collect(loader)
+        out = self.predict(feats, ptr, tiles=True)
+        attn, score = out["attn"].cpu(), out["score"].cpu()
+        return [(attn[ptr[i]:ptr[i + 1]].clone(), score[ptr[i]:ptr[i + 1]].clone()) for i in range(len(ptr) - 1)]
+
+    def state_dict(self) -> "OrderedDict[str, torch.Tensor]":
+        """Host tensors under the names and shapes of the nn.Linear layers of an ABMIL module."""
+        if self.params is None:
+            raise RuntimeError("MilProbe.state_dict: fit first")
+        return OrderedDict((k, v.clone()) for k, v in param_views(self.params.detach().cpu(), self.L, self.C, self.F).items())

@@ -541,6 +541,95 @@ def linprobe_predict(W, b, x, labels=None):
     return prob if labels is None else (prob, loss)
 
 
+_mil_workspace: dict = {}   # device -> uint8 scratch of mil_train / mil_predict, grown on demand and kept
+
+
+def _mil_scratch(dev, batch: int, max_bag: int, Lh: int, C: int, F: int):
+    need = L.lib.gv_mil_workspace_bytes(batch, max_bag, Lh, C, F)
+    if need < 0:
+        raise L.GipvitError(f"gv_mil_workspace_bytes: {L.lib.gv_last_error().decode()}")
+    ws = _mil_workspace.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _mil_workspace[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _mil_inputs(who: str, params, x, bag_ptr, labels, bags, Lh: int, C: int):
+    """Shapes of the packed parameters against the features and the bag table -> (F, n_all_bags)."""
+    _chk(params, f32, "params"); _chk(x, f32, "x"); _chk(bag_ptr, torch.int32, "bag_ptr")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError(f"{who}: expected x [N, F] with unit column stride, got {tuple(x.shape)} strides {x.stride()}")
+    F = x.shape[1]
+    P = (2 * Lh + C) * F + 3 * Lh + C + 1
+    if params.dim() != 1 or params.shape[0] != P or not params.is_contiguous():
+        raise ValueError(f"{who}: params must be a contiguous f32 [{P}] ((2 L + C) F + 3 L + C + 1 with L = {Lh}, C = {C}, F = {F}), got {tuple(params.shape)}")
+    if bag_ptr.dim() != 1 or bag_ptr.shape[0] < 2 or not bag_ptr.is_contiguous():
+        raise ValueError(f"{who}: bag_ptr must be a contiguous int32 [n_bags + 1], got {tuple(bag_ptr.shape)}")
+    n_all = bag_ptr.shape[0] - 1
+    for t, nm, n in ((labels, "labels", n_all), (bags, "bags", None)):
+        if t is None:
+            continue
+        _chk(t, torch.int32, nm)
+        if t.dim() != 1 or not t.is_contiguous() or (n is not None and t.shape[0] != n) or not t.shape[0]:
+            raise ValueError(f"{who}: {nm} must be a contiguous int32 vector{'' if n is None else f' [{n}]'}, got {tuple(t.shape)}")
+    for t, nm in ((params, "params"), (bag_ptr, "bag_ptr"), (labels, "labels"), (bags, "bags")):
+        if t is not None and t.device != x.device:
+            raise TypeError(f"{who}: {nm} must live on {x.device}")
+    return F, n_all
+
+
+def mil_train(params, m, v, x, bag_ptr, labels, bags, loss_sum, hidden: int, num_classes: int, batch: int, max_bag: int, step0: int, lr: float,
+              lr_scale: float = 1.0, wd: float = 0.0, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8):
+    """Adam steps of the gated-attention MIL model on frozen features (gv_mil_train), in place: params / m / v f32 [P] packed as
+    include/gipvit.h lays them out, x f32 [N, F] (row stride free, a multiple of 4), bag_ptr int32 [n_all + 1] (bag b = rows
+    bag_ptr[b] .. bag_ptr[b + 1] - 1), labels int32 [n_all], bags int32 [n_bags] (the visiting order: ceil(n_bags / batch)
+    steps), loss_sum f32 [1] (accumulated: the sum of the bag losses).  ``step0``: Adam steps taken before this call."""
+    F, n_all = _mil_inputs("mil_train", params, x, bag_ptr, labels, bags, hidden, num_classes)
+    if labels is None or bags is None:
+        raise ValueError("mil_train: labels and bags are required")
+    for t, nm, shape in ((m, "m", tuple(params.shape)), (v, "v", tuple(params.shape)), (loss_sum, "loss_sum", (1,))):
+        _chk(t, f32, nm)
+        if tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"mil_train: {nm} must be a contiguous f32 {list(shape)} on {x.device}, got {tuple(t.shape)} on {t.device}")
+    ws = _mil_scratch(x.device, batch, max_bag, hidden, num_classes, F)
+    a = L.gv_mil_train_args(params.data_ptr(), m.data_ptr(), v.data_ptr(), x.data_ptr(), bag_ptr.data_ptr(), labels.data_ptr(), bags.data_ptr(),
+                            loss_sum.data_ptr(), ws.data_ptr(), ws.numel(), x.stride(0), x.shape[0], F, hidden, num_classes, n_all, bags.shape[0],
+                            batch, max_bag, step0, lr, lr_scale, wd, beta1, beta2, eps)
+    L.call("gv_mil_train", a, _stream())
+
+
+def mil_predict(params, x, bag_ptr, hidden: int, num_classes: int, max_bag: int, labels=None, bags=None, want_attn: bool = False,
+                want_score: bool = False, loss=None):
+    """The model's bag probabilities (gv_mil_predict) -> dict(prob f32 [n_bags, C]; with ``labels`` int32 [n_all] also loss f32
+    [1], the sum of -log p[label]; with ``want_attn`` / ``want_score`` attn / score f32 [N]: a_i after and s_i before the bag's
+    softmax, zero in rows no predicted bag covers).  ``bags`` int32: the bags to predict, default all in order.  ``loss``: an f32
+    [1] from an earlier call, to which this call's sum is added."""
+    F, n_all = _mil_inputs("mil_predict", params, x, bag_ptr, labels, bags, hidden, num_classes)
+    n_bags = n_all if bags is None else bags.shape[0]
+    if loss is not None:
+        _chk(loss, f32, "loss")
+        if labels is None or tuple(loss.shape) != (1,) or loss.device != x.device:
+            raise ValueError("mil_predict: an accumulated loss is an f32 [1] on the features' device and needs labels")
+    accumulate = loss is not None
+    if labels is not None and loss is None:
+        loss = torch.empty(1, dtype=f32, device=x.device)
+    ws = _mil_scratch(x.device, max(1, min(n_bags, 64)), max_bag, hidden, num_classes, F)
+    prob = torch.empty(n_bags, num_classes, dtype=f32, device=x.device)
+    attn = torch.zeros(x.shape[0], dtype=f32, device=x.device) if want_attn else None
+    score = torch.zeros(x.shape[0], dtype=f32, device=x.device) if want_score else None
+    a = L.gv_mil_predict_args(params.data_ptr(), x.data_ptr(), bag_ptr.data_ptr(), _p(labels), _p(bags), prob.data_ptr(), _p(loss), _p(attn), _p(score),
+                              ws.data_ptr(), ws.numel(), x.stride(0), x.shape[0], F, hidden, num_classes, n_all, n_bags, max_bag, int(accumulate))
+    L.call("gv_mil_predict", a, _stream())
+    out = dict(prob=prob)
+    if loss is not None:
+        out["loss"] = loss
+    if attn is not None:
+        out["attn"] = attn
+    if score is not None:
+        out["score"] = score
+    return out
+
+
 def weightnorm_fwd(v, g, w, rows: int, C: int):
     L.call("gv_weightnorm_fwd" + _sfx(w), L.gv_weightnorm_fwd_args(v.data_ptr(), g.data_ptr(), w.data_ptr(), rows, C), _stream())
 

@@ -910,6 +910,71 @@ int gv_linprobe_predict(const gv_linprobe_predict_args* a, void* stream);
  * set for arguments the call would refuse.  Touches no GPU.                                                                    */
 int64_t gv_linprobe_workspace_bytes(int32_t batch, int32_t H, int32_t C, int32_t F);
 
+/* ---- attention-MIL probe on frozen features: gated-attention ABMIL (Ilse et al. 2018) over bags of feature rows, one bag per
+ * slide (gipvit/mil.py).  Bag b holds the rows bag_ptr[b] .. bag_ptr[b + 1] - 1 of x (a CSR over rows), its label is labels[b].
+ * State, caller-owned f32, ONE packed vector of P = (2 L + C) F + 3 L + C + 1 values, the Adam moments m and v in the same layout:
+ *     VU [2 L, F] (rows 0 .. L-1: V, rows L .. 2L-1: U) | Wc [C, F] | bv [L] | bu [L] | w [L] | bc [C] | bw [1]
+ * The model, per bag of rows x_1 .. x_n, in f32:
+ *     t_i = tanh(V x_i + bv);  g_i = sigmoid(U x_i + bu);  s_i = w . (t_i * g_i) + bw;  a = softmax_i(s) (max-subtracted)
+ *     z = sum_i a_i x_i;  logits = Wc z + bc;  p = softmax_c(logits);  the bag's loss is -log p[label]
+ * gv_mil_train performs ceil(n_bags / batch) steps over the bags bags[0 .. n_bags), all enqueued on the stream; the last step
+ * takes the bags that are left.  A step is torch.optim.Adam(lr lr_scale, (beta1, beta2), eps, weight_decay = wd) on every
+ * parameter under the mean of the step's bag losses: the decay is added to the gradient, step k of the call (k = 0 ..) is Adam's
+ * step step0 + k + 1, its bias corrections 1 - beta^t are computed on the host in double.  loss_sum is accumulated (the caller
+ * zeroes it): the sum of the bag losses.  A step is three launches, every dependency a launch boundary (no grid barrier, no
+ * atomics): the gate (64 rows of a bag x 32 hidden units per workgroup on the f32 MFMA; t, g and partial scores go to the
+ * workspace), the pool (a workgroup per bag: softmax, z, logits, loss, and the backward down to ds_i), the update (dV | dU =
+ * (dt | dg)^T x per 64 hidden columns x 32 columns of F with Adam in the epilogue; no weight gradient reaches memory).  Every sum
+ * has an order fixed by the data layout: the result, loss_sum included, is bitwise the same run to run.  Every load is
+ * bounds-checked (padding is zero-filled, never read); rows of x that no bag covers are never read.
+ * A BAD BAG contributes nothing and is never used as an index: an index in `bags` outside [0, n_all_bags), an empty bag, one
+ * longer than max_bag, a bag_ptr range outside [0, N], a label outside [0, C).  A step averages over its good bags; a step
+ * without a good bag changes nothing (Adam's step count still advances).
+ * Limits: F a multiple of 4 in 4..4096, L a multiple of 16 in 16..256, 1 <= C <= 32, 1 <= batch <= 64, 1 <= max_bag <= 4096,
+ * N >= 1, n_all_bags >= 1, n_bags >= 1, step0 >= 0, ldx >= F and a multiple of 4, x and params / m / v 16-byte aligned, lr_scale
+ * finite and >= 0, lr > 0 and finite, wd >= 0, 0 <= beta1 < 1, 0 <= beta2 < 1, eps > 0, workspace (16-byte aligned) of
+ * gv_mil_workspace_bytes(batch, max_bag, L, C, F) bytes. */
+typedef struct {
+    float*         params;   /* f32 [P], the layout above                                                */
+    float*         m;        /* f32 [P] Adam's first moment                                              */
+    float*         v;        /* f32 [P] Adam's second moment                                             */
+    const float*   x;        /* f32 [N, F], row stride ldx                                               */
+    const int32_t* bag_ptr;  /* i32 [n_all_bags + 1]                                                     */
+    const int32_t* labels;   /* i32 [n_all_bags]                                                         */
+    const int32_t* bags;     /* i32 [n_bags]: the visiting order, any multiset of bag indices            */
+    float*         loss_sum; /* f32 [1], accumulated                                                     */
+    void*          workspace; int64_t workspace_bytes;
+    int64_t ldx;
+    int32_t N, F, L, C, n_all_bags, n_bags, batch, max_bag;
+    int32_t step0;           /* Adam steps taken before this call                                        */
+    float   lr, lr_scale, wd, beta1, beta2, eps;
+} gv_mil_train_args;
+int gv_mil_train(const gv_mil_train_args* a, void* stream);
+/* prob[j, :] = p of bag bags[j] (bags NULL: of bag j) for j < n_bags, zeros for a bad bag; optionally attn[r] = a_i and
+ * score[r] = s_i for every row r of those bags (other rows are left as they are); with loss non-NULL (labels required) loss[0] =
+ * the sum over the bags, in order, of -log p[label] -- a label outside [0, C) adds nothing -- overwritten, or added to what is
+ * there with accumulate != 0 (two calls over two halves of a list then give the bits of one call over the list).  Same limits;
+ * any n_bags >= 1 (groups of 64 bags), workspace of gv_mil_workspace_bytes(min(n_bags, 64), max_bag, L, C, F) bytes.            */
+typedef struct {
+    const float*   params;   /* f32 [P]                                                                  */
+    const float*   x;        /* f32 [N, F], row stride ldx                                               */
+    const int32_t* bag_ptr;  /* i32 [n_all_bags + 1]                                                     */
+    const int32_t* labels;   /* i32 [n_all_bags]; may be NULL when loss is                               */
+    const int32_t* bags;     /* i32 [n_bags]; may be NULL                                                */
+    float*         prob;     /* f32 [n_bags, C]                                                          */
+    float*         loss;     /* f32 [1]; may be NULL                                                     */
+    float*         attn;     /* f32 [N]; may be NULL                                                     */
+    float*         score;    /* f32 [N]; may be NULL                                                     */
+    void*          workspace; int64_t workspace_bytes;
+    int64_t ldx;
+    int32_t N, F, L, C, n_all_bags, n_bags, max_bag;
+    int32_t accumulate;
+} gv_mil_predict_args;
+int gv_mil_predict(const gv_mil_predict_args* a, void* stream);
+/* scratch bytes of a gv_mil_train call (gv_mil_predict: batch = min(n_bags, 64)); -1 with gv_last_error() set for arguments the
+ * call would refuse.  Touches no GPU.                                                                                          */
+int64_t gv_mil_workspace_bytes(int32_t batch, int32_t max_bag, int32_t L, int32_t C, int32_t F);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,16 @@ def build_parser():
     g.add_argument("--linprobe-rate", type=int, default=0, help="--linear-probe: 0 = probe after the last epoch only, N >= 1 = every N epochs and the last")
     g.add_argument("--linprobe-holdout", type=float, default=0.2, help="--linear-probe, more than one rate: share of the bank slides held out to "
                    "choose the head on (0 < share <= 0.5)")
+    g.add_argument("--mil-probe", action="store_true", help="DINO: slide-level attention-MIL probe on the teacher's frozen features (gated ABMIL "
+                   "over each slide's bag of tile features, trained with Adam; bank = training-fold slides, queries = evaluation fold; "
+                   "gv_mil_train): eval_mil_top1 / eval_mil_loss / eval_mil_auc_per_slide in summary.csv")
+    g.add_argument("--mil-hidden", type=int, default=128, help="--mil-probe: width of the gated attention (a multiple of 16 in 16..256)")
+    g.add_argument("--mil-lr", type=float, default=5e-4, help="--mil-probe: Adam's rate (cosine schedule per epoch)")
+    g.add_argument("--mil-wd", type=float, default=1e-4, help="--mil-probe: weight decay, added to the gradient")
+    g.add_argument("--mil-epochs", type=int, default=50, help="--mil-probe: passes over the bank's slides")
+    g.add_argument("--mil-batch", type=int, default=8, help="--mil-probe: slides per step (1..64)")
+    g.add_argument("--mil-layers", type=int, default=1, help="--mil-probe: the CLS tokens of the last N blocks are the features")
+    g.add_argument("--mil-rate", type=int, default=0, help="--mil-probe: 0 = probe after the last epoch only, N >= 1 = every N epochs and the last")
     g.add_argument("--tile-size", type=int, default=256)
     g.add_argument("--batches-per-epoch", type=int, default=100, help="synthetic source only")
     g.add_argument("--synthetic-slides", type=int, default=4, help="synthetic source only: slides of the inference set")
@@ -271,9 +281,44 @@ def check_supported(args, log=_logger.warning):
             raise SystemExit(f"--linear-probe: the teacher sees {args.global_crop_size}-px images, the centred window of a {args.tile_size}-px "
                              "tile (--tile-size) cannot be smaller than that")
         names = monitor_metric_names(args)
-        if resolve_eval_metric(args.eval_metric, bool(args.knn_monitor), True) not in names:
+        if resolve_eval_metric(args.eval_metric, bool(args.knn_monitor), True, bool(args.mil_probe)) not in names:
             raise SystemExit(f"--eval-metric {args.eval_metric}: the monitors of this run report {names} (a bare name is the k-NN monitor's "
                              "when that is on, else the probe's)")
+    if args.mil_probe:
+        if not args.dino:
+            raise SystemExit("--mil-probe scores the DINO teacher's frozen features: it needs --dino (a supervised run has validate())")
+        if args.mil_hidden % 16 or not 16 <= args.mil_hidden <= 256:
+            raise SystemExit(f"--mil-hidden {args.mil_hidden}: a multiple of 16 in 16 .. 256 (gv_mil_train)")
+        if not (math.isfinite(args.mil_lr) and args.mil_lr > 0):
+            raise SystemExit(f"--mil-lr {args.mil_lr}: a positive finite rate")
+        if not args.mil_wd >= 0:
+            raise SystemExit(f"--mil-wd {args.mil_wd}: weight decay must be >= 0")
+        if args.mil_epochs < 1:
+            raise SystemExit(f"--mil-epochs {args.mil_epochs}: at least one pass over the bank's slides")
+        if not 1 <= args.mil_batch <= 64:
+            raise SystemExit(f"--mil-batch {args.mil_batch}: 1 .. 64 slides per step (gv_mil_train)")
+        from gipvit.archs import ARCHS, resolve_arch       # plain tables: nothing is loaded for them
+        spec = ARCHS[resolve_arch(args.model)]
+        if not 1 <= args.mil_layers <= spec["depth"]:
+            raise SystemExit(f"--mil-layers {args.mil_layers}: the last 1 .. {spec['depth']} blocks of {args.model}")
+        if args.mil_layers * spec["embed_dim"] > 4096:
+            raise SystemExit(f"--mil-layers {args.mil_layers}: {args.mil_layers * spec['embed_dim']} features per tile at width {spec['embed_dim']}, "
+                             "gv_mil_train stops at 4096")
+        if args.mil_rate < 0:
+            raise SystemExit(f"--mil-rate {args.mil_rate}: 0 = after the last epoch only, N >= 1 = every N epochs and the last")
+        if args.test_fold in (-1, "-1"):
+            raise SystemExit("--test_fold -1 with --mil-probe: no evaluation fold is left to score the slides of")
+        if args.tile_size < args.global_crop_size:
+            raise SystemExit(f"--mil-probe: the teacher sees {args.global_crop_size}-px images, the centred window of a {args.tile_size}-px "
+                             "tile (--tile-size) cannot be smaller than that")
+        if args.num_tiles > 4096:
+            raise SystemExit(f"--num_tiles {args.num_tiles} with --mil-probe: a slide's bag holds at most 4096 tiles (gv_mil_train)")
+        if args.knn_bank_tiles is not None and args.knn_bank_tiles > 4096:
+            raise SystemExit(f"--knn-bank-tiles {args.knn_bank_tiles} with --mil-probe: a slide's bag holds at most 4096 tiles (gv_mil_train)")
+        names = monitor_metric_names(args)
+        if resolve_eval_metric(args.eval_metric, bool(args.knn_monitor), bool(args.linear_probe), True) not in names:
+            raise SystemExit(f"--eval-metric {args.eval_metric}: the monitors of this run report {names} (a bare name is the k-NN monitor's "
+                             "when that is on, else the linear probe's, else the MIL probe's)")
     if args.supervised and args.dino:
         raise SystemExit("--supervised (fine-tune with labels, train.py:715-717) and --dino (self-supervised) exclude each other")
     # mixup / cutmix / BCE (train.py:752-771, 828-846): the supervised step's batch, target and loss
@@ -347,11 +392,12 @@ def check_token_limits(args):
 
 def monitor_metric_names(args):
     """The metrics the monitors of a --dino run report, in the fixed order of their summary.csv columns: the k-NN monitor's, then
-    the linear probe's; the AUCs only with more than one class."""
+    the linear probe's, then the MIL probe's; the AUCs only with more than one class."""
     many = (args.num_classes or 2) > 1
     knn = (["knn_top1"] + (["knn_auc_per_patch", "knn_auc_per_slide"] if many else [])) if args.knn_monitor else []
     probe = (["linear_top1", "linear_loss"] + (["linear_auc_per_patch", "linear_auc_per_slide"] if many else [])) if args.linear_probe else []
-    return knn + probe
+    mil = (["mil_top1", "mil_loss"] + (["mil_auc_per_slide"] if many else [])) if getattr(args, "mil_probe", False) else []
+    return knn + probe + mil
 
 
 def summary_row(epoch, train_metrics, eval_metrics, monitor_names, lr) -> "OrderedDict":
@@ -365,12 +411,13 @@ def summary_row(epoch, train_metrics, eval_metrics, monitor_names, lr) -> "Order
     return row
 
 
-def resolve_eval_metric(name: str, knn: bool, probe: bool) -> str:
-    """--eval-metric among the metrics of a --dino run's monitors: a name that already starts knn_ / linear_ is taken as given, a
-    bare one is the k-NN monitor's when that is on ('top1' -> 'knn_top1'), else the linear probe's when only the probe is."""
-    if name.startswith("knn_") or name.startswith("linear_"):
+def resolve_eval_metric(name: str, knn: bool, probe: bool, mil: bool = False) -> str:
+    """--eval-metric among the metrics of a --dino run's monitors: a name that already starts knn_ / linear_ / mil_ is taken as
+    given, a bare one is the k-NN monitor's when that is on ('top1' -> 'knn_top1'), else the linear probe's when that is on, else
+    the MIL probe's when it is the only monitor."""
+    if name.startswith("knn_") or name.startswith("linear_") or name.startswith("mil_"):
         return name
-    return ("knn_" + name) if knn else ("linear_" + name) if probe else name
+    return ("knn_" + name) if knn else ("linear_" + name) if probe else ("mil_" + name) if mil else name
 
 
 def mix_active(args) -> bool:
@@ -536,13 +583,14 @@ def main(argv=None, transform=None):
     # --knn-monitor: the bank comes from the training fold, the queries from the evaluation fold; --extract_features runs alone
     want_knn = bool(args.knn_monitor) and not args.extract_features
     want_probe = bool(args.linear_probe) and not args.extract_features     # the same bank and query loaders, shared when both are on
+    want_mil = bool(args.mil_probe) and not args.extract_features
     knn_bank_loader = knn_query_loader = None
     bank_tiles = args.knn_bank_tiles or args.num_tiles
     if synthetic:
         source = D.SyntheticTiles(B, tile, args.batches_per_epoch, args.num_classes or 2, seed=args.seed + rank)
         if not args.no_validate and (not args.dino or args.extract_features):
             inf_loader = D.SyntheticSlides(args.synthetic_slides, min(args.num_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 99)
-        if want_knn or want_probe:
+        if want_knn or want_probe or want_mil:
             knn_bank_loader = D.SyntheticSlides(args.synthetic_slides, min(bank_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 77)
             knn_query_loader = D.SyntheticSlides(args.synthetic_slides, min(args.num_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 99)
     elif args.dataset.startswith("tiles:") or args.data_dir:
@@ -554,7 +602,7 @@ def main(argv=None, transform=None):
         want_eval = not args.no_validate and (not args.dino or args.extract_features)
         no_val_fold = args.test_fold in (-1, "-1")
         train_slides = D.select_fold(slides, args.test_fold, True)
-        if args.supervised or want_knn or want_probe or (want_eval and not no_val_fold):
+        if args.supervised or want_knn or want_probe or want_mil or (want_eval and not no_val_fold):
             eval_slides = D.select_fold(slides, args.test_fold, False)       # raises when evaluation was asked for and no slide is in the fold
         else:
             eval_slides = []
@@ -572,7 +620,7 @@ def main(argv=None, transform=None):
         if want_eval:
             inf_loader = D.InferTiles(root, tile, args.tiles_per_iter, args.num_tiles, seed=args.seed, dataset_name=args.dataset,
                                       workers=args.workers, slides=eval_slides)
-        if want_knn or want_probe:
+        if want_knn or want_probe or want_mil:
             knn_bank_loader = D.InferTiles(root, tile, args.tiles_per_iter, bank_tiles, seed=args.seed + 1, dataset_name=args.dataset,
                                            workers=args.workers, slides=train_slides)
             knn_query_loader = D.InferTiles(root, tile, args.tiles_per_iter, args.num_tiles, seed=args.seed, dataset_name=args.dataset,
@@ -648,9 +696,9 @@ def main(argv=None, transform=None):
             if ema_decay is not None:
                 runner_ema = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.Wema, global_pool=eng.pool)
 
-    monitor = probe = None
-    knn_names, probe_names = [], []
-    if want_knn or want_probe:        # the teacher backbone at its own image size; larger tiles contribute their centred window (gipvit/knn.py)
+    monitor = probe = mil = None
+    knn_names, probe_names, mil_names = [], [], []
+    if want_knn or want_probe or want_mil:        # the teacher backbone at its own image size; larger tiles contribute their centred window (gipvit/knn.py)
         knn_runner = FeatureExtractor(arch, img, eval_B, 0, mean, std, dev, weights=Weights(eng.arena, "backbone.", teacher=True, fp32=args.precision == "fp32"))
     if want_knn:
         from gipvit.knn import KnnMonitor
@@ -663,15 +711,22 @@ def main(argv=None, transform=None):
                             holdout=args.linprobe_holdout, seed=args.seed, primary=primary)
         probe_names = ["linear_top1", "linear_loss"] + (["linear_auc_per_patch", "linear_auc_per_slide"] if probe.C > 1 else [])
 
+    if want_mil:        # slide-level ABMIL on the same runner's CLS tokens, one bag per slide (gipvit/mil.py)
+        from gipvit.mil import MilProbe
+        mil = MilProbe(knn_runner, num_classes=args.num_classes or 2, hidden=args.mil_hidden, lr=args.mil_lr, weight_decay=args.mil_wd,
+                       epochs=args.mil_epochs, batch=args.mil_batch, n_last=args.mil_layers, seed=args.seed, primary=primary)
+        mil_names = ["mil_top1", "mil_loss"] + (["mil_auc_per_slide"] if mil.C > 1 else [])
+    any_monitor = monitor is not None or probe is not None or mil is not None
+
     # ---- output dir, args.yaml, saver (train.py:854-879)
-    eval_metric = resolve_eval_metric(args.eval_metric, monitor is not None, probe is not None)      # train.py:849; 'top1' -> knn_top1
-    decreasing = eval_metric in ("loss", "linear_loss")         # train.py:866
+    eval_metric = resolve_eval_metric(args.eval_metric, monitor is not None, probe is not None, mil is not None)      # train.py:849; 'top1' -> knn_top1
+    decreasing = eval_metric in ("loss", "linear_loss", "mil_loss")         # train.py:866
     saver = output_dir = None
     if primary:
         exp = args.experiment or "-".join([time.strftime("%Y%m%d-%H%M%S"), args.model.replace("/", "_"), str(img)])
         output_dir = os.path.join(args.output or "./output/train", exp, args.subexperiment or "")
         os.makedirs(output_dir, exist_ok=True)
-        saver = CheckpointSaver(output_dir, args.model, vars(args), decreasing=decreasing if (monitor is not None or probe is not None) else (decreasing or inf_loader is None or args.dino),
+        saver = CheckpointSaver(output_dir, args.model, vars(args), decreasing=decreasing if any_monitor else (decreasing or inf_loader is None or args.dino),
                                 max_history=args.checkpoint_hist)
         with open(os.path.join(output_dir, "args.yaml"), "w") as f:
             f.write(args_text)
@@ -819,13 +874,17 @@ def main(argv=None, transform=None):
             if epoch == args.epochs - 1 or (args.linprobe_rate >= 1 and (epoch + 1) % args.linprobe_rate == 0):
                 probe.fit(knn_bank_loader)                      # fresh heads on the teacher as it stands
                 eval_metrics.update(probe.evaluate(knn_query_loader))
+        if mil is not None:
+            if epoch == args.epochs - 1 or (args.mil_rate >= 1 and (epoch + 1) % args.mil_rate == 0):
+                mil.fit(knn_bank_loader)                        # a fresh model on the teacher as it stands
+                eval_metrics.update(mil.evaluate(knn_query_loader))
         if args.extract_features:
             if primary:
                 _logger.info(f"*** features of {int(eval_metrics.get('slides', 0))} slides written to {args.features_dir}")
             break
         if primary:
             # the monitors' columns stay in one order, empty for a monitor that did not run this epoch
-            row = summary_row(epoch, train_metrics, eval_metrics, knn_names + probe_names, logged_lr(cur_lr))
+            row = summary_row(epoch, train_metrics, eval_metrics, knn_names + probe_names + mil_names, logged_lr(cur_lr))
             fn = os.path.join(output_dir, "summary.csv")
             new = not os.path.exists(fn)
             with open(fn, "a") as f:
@@ -838,10 +897,10 @@ def main(argv=None, transform=None):
             optim = {"exp_avg": eng.arena.m, "exp_avg_sq": eng.arena.v, "step": eng.t}
             if eval_metric in eval_metrics:
                 save_metric, name = eval_metrics[eval_metric], "eval " + eval_metric          # train.py:970-973
-            elif eval_metric in knn_names + probe_names or (not eval_metrics and (monitor is not None or probe is not None)):
-                save_metric, name = None, "eval " + eval_metric                               # not evaluated this epoch (--knn-rate / --linprobe-rate)
+            elif eval_metric in knn_names + probe_names + mil_names or (not eval_metrics and any_monitor):
+                save_metric, name = None, "eval " + eval_metric                               # not evaluated this epoch (--knn-rate / --linprobe-rate / --mil-rate)
             elif eval_metrics:
-                who = "the monitors of this run report" if probe is not None else "the k-NN monitor reports" if monitor is not None else "validate() reports"
+                who = "the monitors of this run report" if (probe is not None or mil is not None) else "the k-NN monitor reports" if monitor is not None else "validate() reports"
                 raise SystemExit(f"--eval-metric {eval_metric}: {who} {list(eval_metrics)}")
             else:
                 save_metric, name = train_metrics["loss"], "train loss"
