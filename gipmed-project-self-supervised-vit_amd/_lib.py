@@ -175,6 +175,12 @@ gv_mil_predict_args = _struct("gv_mil_predict_args", [
     ("params", vp), ("x", vp), ("bag_ptr", vp), ("labels", vp), ("bags", vp), ("prob", vp), ("loss", vp), ("attn", vp), ("score", vp),
     ("workspace", vp), ("workspace_bytes", i64), ("ldx", i64), ("N", i32), ("F", i32), ("L", i32), ("C", i32), ("n_all_bags", i32), ("n_bags", i32),
     ("max_bag", i32), ("accumulate", i32)])
+gv_sinkhorn_args = _struct("gv_sinkhorn_args", [
+    ("teacher", vp), ("shift", vp), ("a", vp), ("b", vp), ("colsum", vp), ("sk_center", vp), ("workspace", vp), ("workspace_bytes", i64),
+    ("hyper", vp), ("R", i32), ("K", i32), ("first", i32), ("teacher_temp", f32)])
+gv_koleo_args = _struct("gv_koleo_args", [
+    ("feats", vp), ("dfeats", vp), ("workspace", vp), ("workspace_bytes", i64), ("nn", vp), ("koleo", vp), ("loss_scale", vp), ("ld", i64),
+    ("G", i32), ("B", i32), ("D", i32), ("weight", f32)])
 
 # entry point -> argument struct (every `int gv_*(const args*, void* stream)` of the header)
 ENTRY_POINTS = {
@@ -201,9 +207,12 @@ ENTRY_POINTS = {
     "gv_knn_vote": gv_knn_vote_args, "gv_linprobe_train": gv_linprobe_train_args, "gv_linprobe_predict": gv_linprobe_predict_args,
     "gv_mil_train": gv_mil_train_args, "gv_mil_predict": gv_mil_predict_args,
     "gv_token_mean_fwd": gv_token_mean_fwd_args, "gv_token_mean_bwd": gv_token_mean_bwd_args, "gv_token_mean_bwd_f32": gv_token_mean_bwd_args,
+    "gv_sinkhorn_shift": gv_sinkhorn_args, "gv_sinkhorn_cols": gv_sinkhorn_args, "gv_sinkhorn_rows": gv_sinkhorn_args, "gv_sinkhorn_finish": gv_sinkhorn_args,
+    "gv_koleo_fwd": gv_koleo_args, "gv_koleo_bwd": gv_koleo_args, "gv_koleo_fwd_f32": gv_koleo_args, "gv_koleo_bwd_f32": gv_koleo_args,
 }
 PLAIN_SYMBOLS = ("gv_version", "gv_last_error", "gv_target", "gv_act_format", "gv_linear_workspace_bytes", "gv_workspace_bytes", "gv_linear_timing", "gv_linear_timing_read",
-                 "gv_linear_ln_blocks", "gv_knn_workspace_bytes", "gv_linprobe_workspace_bytes", "gv_mil_workspace_bytes")
+                 "gv_linear_ln_blocks", "gv_knn_workspace_bytes", "gv_linprobe_workspace_bytes", "gv_mil_workspace_bytes",
+                 "gv_sinkhorn_workspace_bytes", "gv_koleo_workspace_bytes")
 
 
 class gv_linear_timing_row(C.Structure):
@@ -250,6 +259,10 @@ def _load():
     lib.gv_linprobe_workspace_bytes.restype = C.c_int64
     lib.gv_mil_workspace_bytes.argtypes = [C.c_int32] * 5
     lib.gv_mil_workspace_bytes.restype = C.c_int64
+    lib.gv_sinkhorn_workspace_bytes.argtypes = [C.c_int32] * 2
+    lib.gv_sinkhorn_workspace_bytes.restype = C.c_int64
+    lib.gv_koleo_workspace_bytes.argtypes = [C.c_int32] * 3
+    lib.gv_koleo_workspace_bytes.restype = C.c_int64
     return lib
 
 

@@ -70,6 +70,10 @@ class RcclReducer:
     def reduce_tensor(self, t: torch.Tensor):
         self._pending.append(dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
 
+    def reduce_max(self, t: torch.Tensor):
+        """Element-wise maximum over the ranks (the Sinkhorn-Knopp shift): queued like the sums, joined by ``finish()``."""
+        self._pending.append(dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group, async_op=True))
+
     def finish(self):
         for w in self._pending:
             w.wait()            # current stream waits for the communication stream

@@ -956,8 +956,19 @@ class NoReducer:
     def reduce_tensor(self, t):
         pass
 
+    def reduce_max(self, t):
+        pass
+
     def finish(self):
         pass
+
+
+def _ws_bytes(query: str, *shape) -> int:
+    """A workspace query of the library (gv_*_workspace_bytes); the shape it refuses is a ValueError with the library's words."""
+    n = getattr(L.lib, query)(*shape)
+    if n < 0:
+        raise ValueError(L.lib.gv_last_error().decode())
+    return n
 
 
 def operand_mode(precision: str):
@@ -1015,10 +1026,23 @@ class DinoEngine(TrainEngine):
     def __init__(self, arch="vit_small", img_size=224, out_dim=65536, batch=64, tile=256, n_global=2, n_local=8,
                  gsize=224, lsize=96, hidden=2048, bottleneck=256, lr=5e-4, weight_decay=0.04, betas=(0.9, 0.999), eps=1e-8,
                  momentum_teacher=0.996, student_temp=0.1, teacher_temp=0.04, center_momentum=0.9, clip_grad: float = 0.0,
-                 mean=MEAN_RON, std=STD_RON, windows=None, device="cuda:0", reducer=None, precision: str = "bf16", clip_mode: str = "norm"):
+                 mean=MEAN_RON, std=STD_RON, windows=None, device="cuda:0", reducer=None, precision: str = "bf16", clip_mode: str = "norm",
+                 centering: str = "center", sinkhorn_iters: int = 3, koleo_weight: float = 0.0):
         """``precision``: "bf16" (the training path) or "fp32" (every GEMM / attention operand, the head activations, the
         weight-normalised prototype matrix and the logit gradient in f32 -- the verification mode of SURVEY 8d's fp32 column).
-        ``clip_mode``: "norm" (global norm, the reference default) or "value" (element-wise clamp), train.py:1072-1077."""
+        ``clip_mode``: "norm" (global norm, the reference default) or "value" (element-wise clamp), train.py:1072-1077.
+        ``centering``: "center" (the EMA centre of DINO) or "sinkhorn_knopp" (DINOv2: ``sinkhorn_iters`` Sinkhorn-Knopp iterations
+        over the teacher logits of all ranks, handed to the loss as ``sk_center``; the EMA centre keeps running beside it).
+        ``koleo_weight`` > 0 adds that multiple of the KoLeo regulariser on the student's features of every global crop (DINOv2 uses
+        0.1): ``koleo`` is its unweighted value, local to the rank, ``loss`` stays the DINO term."""
+        if centering not in ("center", "sinkhorn_knopp"):
+            raise ValueError(f"centering {centering!r}: 'center' or 'sinkhorn_knopp'")
+        if not 1 <= int(sinkhorn_iters) <= 8:
+            raise ValueError(f"sinkhorn_iters {sinkhorn_iters}: 1..8")
+        if not (math.isfinite(koleo_weight) and koleo_weight >= 0):
+            raise ValueError(f"koleo_weight {koleo_weight}: finite and >= 0")
+        if koleo_weight > 0 and batch < 2:
+            raise ValueError("koleo_weight > 0 needs a batch of at least 2: the nearest neighbour is taken among the other tiles of the crop")
         dev = torch.device(device)
         fp32, act = self._set_modes(precision, clip_mode, ("norm", "value"), dev)
         self.dev, self.arch, self.B, self.tile = dev, arch, batch, tile
@@ -1051,6 +1075,19 @@ class DinoEngine(TrainEngine):
         self.center_sum = torch.zeros(out_dim, dtype=f32, device=dev)
         self.loss = torch.zeros(1, dtype=f32, device=dev)
         self.loss_ws = _empty((2 * (self.V + self.G) * B,), f32, dev)
+        self.centering, self.sinkhorn_iters, self.koleo_weight = centering, int(sinkhorn_iters), float(koleo_weight)
+        self.sk_center = self.koleo = self.koleo_nn = None
+        if centering == "sinkhorn_knopp":       # written by every step's _sinkhorn before the loss reads sk_center
+            R = n_global * B
+            self.sk_center, self.sk_a, self.sk_colsum = (_empty((out_dim,), f32, dev) for _ in range(3))
+            self.sk_b, self.sk_shift = _empty((R,), f32, dev), _empty((1,), f32, dev)
+            self.sk_ws = _empty((_ws_bytes("gv_sinkhorn_workspace_bytes", R, out_dim) // 4,), f32, dev)
+        if koleo_weight > 0:
+            self.koleo = _empty((1,), f32, dev)           # written by every forward's gv_koleo_fwd
+            # an index table: _empty refuses wide integers (all-ones poison would be a wild index).  gv_koleo_fwd writes every entry
+            # before gv_koleo_bwd reads one, and the backward clamps what it reads into the crop
+            self.koleo_nn = torch.zeros(n_global * B, dtype=torch.int32, device=dev)
+            self.koleo_ws = _empty((_ws_bytes("gv_koleo_workspace_bytes", n_global, B, D) // 4,), f32, dev)
         self.gnorm_sq = torch.zeros(1, dtype=f32, device=dev)
         self.red_ws = _empty((1024,), f32, dev)
         self.hyper = torch.zeros(L.HYP_COUNT, dtype=f32, device=dev)
@@ -1190,9 +1227,12 @@ class DinoEngine(TrainEngine):
         ev_zero = sx.run(fills)
         ev_teacher = sx.run(teacher) if t_side else teacher()
         self.vit.forward(self.sW, self.g_stu, s_src, s_win, self.mean, self.std, self.hb_s.feats, fill=fill)
+        if self.koleo_weight > 0:
+            ops.koleo_fwd(self.hb_s.feats, self.koleo_ws, self.koleo_nn, self.koleo, G, B, self.D)
         self.head.forward(self.sH, self.wn_s, self.hb_s)
         sx.join(ev_teacher)
-        ops.dino_loss(self.hb_s.logits, self.hb_t.logits, self.center, self.hb_s.dlogits, self.loss, self.center_sum,
+        center = self.center if self.centering == "center" else self._sinkhorn()
+        ops.dino_loss(self.hb_s.logits, self.hb_t.logits, center, self.hb_s.dlogits, self.loss, self.center_sum,
                       self.loss_ws, B, V, G, self.K, self.ts, self.tt, hyper=self.hyper,
                       loss_scale=self.scaler.scale if self.scaler is not None else None)
         if mn > 1:
@@ -1202,10 +1242,17 @@ class DinoEngine(TrainEngine):
                 self._loss_acc += self.loss; self._center_acc += self.center_sum
             if last:
                 self.loss.copy_(self._loss_acc / mn); self.center_sum.copy_(self._center_acc)
+            if self.koleo_weight > 0:       # the mean over the micro-batches, like the loss
+                self._koleo_acc = self.koleo.clone() if first else self._koleo_acc + self.koleo
+                if last:
+                    self.koleo.copy_(self._koleo_acc / mn)
         if last:
             self.reducer.reduce_tensor(self.center_sum)
         sx.join(ev_zero)
         self.head.backward(self.sH, self.wn_s, self.hb_s, self.train_last_layer, sx)
+        if self.koleo_weight > 0:       # into the global crops' rows of the feature gradient, under the loss scale the DINO term carries
+            ops.koleo_bwd(self.hb_s.dfeats, self.koleo_ws, self.koleo_nn, G, B, self.D, self.koleo_weight,
+                          loss_scale=self.scaler.scale if self.scaler is not None else None)
         if not last:        # more micro-batches follow: gradients keep accumulating locally
             self.vit.backward(self.sW, self.g_stu, self.hb_s.dfeats)
             return
@@ -1225,6 +1272,23 @@ class DinoEngine(TrainEngine):
         self.vit.backward(self.sW, self.g_stu, self.hb_s.dfeats, on_block_done=release)
         release("end")
         self.reducer.finish()
+
+    def _sinkhorn(self) -> torch.Tensor:
+        """Sinkhorn-Knopp centring of this step's teacher logits (include/gipvit.h), 2 n + 1 calls (4 n + 1 kernel launches) on the
+        main stream: the shift is the maximum and every column pass the sum over all ranks.  -> ``sk_center``, the loss's centre."""
+        R, n = self.G * self.B, self.sinkhorn_iters
+        state = (self.hb_t.logits, self.sk_shift, self.sk_a, self.sk_b, self.sk_colsum, self.sk_ws)
+        ops.sinkhorn_shift(*state, R, self.K, self.tt, hyper=self.hyper)
+        self.reducer.reduce_max(self.sk_shift)
+        self.reducer.finish()
+        for it in range(n):
+            ops.sinkhorn_cols(*state, R, self.K, self.tt, hyper=self.hyper, first=it == 0)
+            self.reducer.reduce_tensor(self.sk_colsum)
+            self.reducer.finish()
+            if it < n - 1:
+                ops.sinkhorn_rows(*state, R, self.K, self.tt, hyper=self.hyper, first=it == 0)
+        ops.sinkhorn_finish(*state, self.sk_center, R, self.K, self.tt, hyper=self.hyper, first=n == 1)
+        return self.sk_center
 
     def _reduction_plan(self):
         if self._plan is None:

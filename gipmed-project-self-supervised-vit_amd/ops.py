@@ -652,6 +652,50 @@ def center_update(center, center_sum, K: int, momentum: float, inv_rows: float):
     L.call("gv_center_update", L.gv_center_update_args(center.data_ptr(), center_sum.data_ptr(), K, momentum, inv_rows), _stream())
 
 
+def _sinkhorn(entry: str, teacher, shift, a, b, colsum, workspace, R: int, K: int, teacher_temp: float, hyper, first: bool, sk_center=None):
+    args = L.gv_sinkhorn_args(teacher.data_ptr(), shift.data_ptr(), a.data_ptr(), b.data_ptr(), colsum.data_ptr(), _p(sk_center), workspace.data_ptr(),
+                              workspace.numel() * workspace.element_size(), _p(hyper), R, K, int(first), teacher_temp)
+    L.call(entry, args, _stream())
+
+
+def sinkhorn_shift(teacher, shift, a, b, colsum, workspace, R: int, K: int, teacher_temp: float, hyper=None):
+    """Sinkhorn-Knopp centring of the teacher logits f32 [R, K] (include/gipvit.h), first of its 2 n + 1 calls: shift f32 [1] =
+    this rank's largest logit / tau (the caller takes the maximum over the ranks).  a / colsum f32 [K], b f32 [R] and the
+    workspace (gv_sinkhorn_workspace_bytes) are the state all four functions share; ``hyper`` carries tau as for dino_loss."""
+    _sinkhorn("gv_sinkhorn_shift", teacher, shift, a, b, colsum, workspace, R, K, teacher_temp, hyper, False)
+
+
+def sinkhorn_cols(teacher, shift, a, b, colsum, workspace, R: int, K: int, teacher_temp: float, hyper=None, first: bool = False):
+    """colsum[k] = this rank's sum_r exp(T_rk / tau - shift + a_k + b_r) (the caller adds the ranks' sums); ``first``: a = b = 0."""
+    _sinkhorn("gv_sinkhorn_cols", teacher, shift, a, b, colsum, workspace, R, K, teacher_temp, hyper, first)
+
+
+def sinkhorn_rows(teacher, shift, a, b, colsum, workspace, R: int, K: int, teacher_temp: float, hyper=None, first: bool = False):
+    """a_k -= log colsum[k] (``first``: from a = 0), then b_r = -log sum_k exp(T_rk / tau - shift + a_k)."""
+    _sinkhorn("gv_sinkhorn_rows", teacher, shift, a, b, colsum, workspace, R, K, teacher_temp, hyper, first)
+
+
+def sinkhorn_finish(teacher, shift, a, b, colsum, workspace, sk_center, R: int, K: int, teacher_temp: float, hyper=None, first: bool = False):
+    """The fold of the last column sums, and sk_center f32 [K] = -tau a: dino_loss's ``center`` under Sinkhorn-Knopp centring."""
+    _sinkhorn("gv_sinkhorn_finish", teacher, shift, a, b, colsum, workspace, R, K, teacher_temp, hyper, first, sk_center)
+
+
+def koleo_fwd(feats, workspace, nn, koleo, G: int, B: int, D: int):
+    """KoLeo on rows [0, G * B) of feats [>= G * B, D] (16-bit, or f32 in the fp32 operand mode), per crop of B rows: koleo f32 [1]
+    = sum_g L_g, nn int32 [G * B] = every row's nearest neighbour within its crop; y, norms and distances stay in the workspace
+    (gv_koleo_workspace_bytes) for koleo_bwd."""
+    a = L.gv_koleo_args(feats.data_ptr(), None, workspace.data_ptr(), workspace.numel() * workspace.element_size(), nn.data_ptr(), koleo.data_ptr(),
+                        None, feats.stride(0), G, B, D, 0.0)
+    L.call("gv_koleo_fwd" + _sfx(feats), a, _stream())
+
+
+def koleo_bwd(dfeats, workspace, nn, G: int, B: int, D: int, weight: float, loss_scale=None):
+    """dfeats[0 : G * B] += weight [* loss_scale] * d koleo / d feats, in place, from the workspace and nn koleo_fwd left."""
+    a = L.gv_koleo_args(None, dfeats.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(), nn.data_ptr(), None,
+                        _p(loss_scale), dfeats.stride(0), G, B, D, weight)
+    L.call("gv_koleo_bwd" + _sfx(dfeats), a, _stream())
+
+
 def softmax_lsce(logits, target, loss, dlogits, prob, B: int, C: int, smoothing: float, loss_scale=None):
     a = L.gv_softmax_lsce_args(logits.data_ptr(), target.data_ptr(), loss.data_ptr(), dlogits.data_ptr(), _p(prob), B, C, smoothing,
                                _p(loss_scale))

@@ -975,6 +975,74 @@ int gv_mil_predict(const gv_mil_predict_args* a, void* stream);
  * call would refuse.  Touches no GPU.                                                                                          */
 int64_t gv_mil_workspace_bytes(int32_t batch, int32_t max_bag, int32_t L, int32_t C, int32_t F);
 
+/* ---- DINOv2 loss options (csrc/dinov2_terms.hip): Sinkhorn-Knopp centring of the teacher and the KoLeo regulariser.
+ *
+ * Sinkhorn-Knopp over the teacher logits T f32 [R, K] (R = G * B local rows), in the log domain: a [K] (= log u) and b [R] start
+ * at 0, tau is hyper[GV_HYP_TEACHER_TEMP] when hyper is given (teacher_temp otherwise), shift = max(T / tau) over all ranks' rows;
+ * for it = 0 .. n-1:   s_k = sum_r exp(T_rk / tau - shift + a_k + b_r) over all ranks' rows;  a_k -= log(max(s_k, FLT_MIN));
+ *                      unless it is the last:  b_r = -log sum_k exp(T_rk / tau - shift + a_k)
+ * and sk_center[k] = -tau a_k: gv_dino_loss with sk_center in place of its centre computes softmax((t - c) / tau), which is
+ * the Sinkhorn-Knopp assignment (its per-sample normalisation is the softmax's).  One entry point per dependency between rows and
+ * columns, so that the caller can all-reduce between them -- 2 n + 1 calls:
+ *     gv_sinkhorn_shift    shift[0] = the LOCAL maximum (the caller takes the maximum over the ranks)
+ *     gv_sinkhorn_cols     colsum[k] = the LOCAL s_k (the caller adds the ranks' sums); first != 0: a and b are read as 0
+ *     gv_sinkhorn_rows     a_k -= log(max(colsum[k], FLT_MIN)) (first != 0: a is read as 0), then b
+ *     gv_sinkhorn_finish   the same fold of the last colsum, and sk_center
+ * Each call but the last is two kernel launches (partial maxima + their fold; row-sliced partial sums + their combination, one launch
+ * when there is a single slice; the fold of a + the rows): 4 n + 1 launches for n iterations, 13 at n = 3.
+ * No atomics and every sum in an order fixed by (R, K): bitwise the same run to run.  Every dependency between workgroups is a
+ * launch boundary.  expf / logf, 16-byte loads.  Limits: 1 <= R <= 65535, K a positive multiple of 4, teacher_temp > 0; teacher, a,
+ * colsum, sk_center and workspace 16-byte aligned; workspace of gv_sinkhorn_workspace_bytes(R, K) bytes.  A refused call
+ * returns GV_E_* before any launch.                                                                                          */
+typedef struct {
+    const float* teacher;    /* f32 [R, K]                                                               */
+    float*       shift;      /* f32 [1]                                                                  */
+    float*       a;          /* f32 [K]                                                                  */
+    float*       b;          /* f32 [R]                                                                  */
+    float*       colsum;     /* f32 [K]                                                                  */
+    float*       sk_center;  /* f32 [K]; gv_sinkhorn_finish only, may be NULL elsewhere                  */
+    void*        workspace; int64_t workspace_bytes;
+    const float* hyper;      /* optional device vector (see gv_adamw_ema_args): the teacher temperature  */
+    int32_t R, K;
+    int32_t first;           /* != 0: a and b hold nothing yet (the first column pass and the fold after it) */
+    float   teacher_temp;
+} gv_sinkhorn_args;
+int gv_sinkhorn_shift(const gv_sinkhorn_args* a, void* stream);
+int gv_sinkhorn_cols(const gv_sinkhorn_args* a, void* stream);
+int gv_sinkhorn_rows(const gv_sinkhorn_args* a, void* stream);
+int gv_sinkhorn_finish(const gv_sinkhorn_args* a, void* stream);
+/* scratch bytes of the four calls; -1 with gv_last_error() set for a shape they would refuse.  Touches no GPU. */
+int64_t gv_sinkhorn_workspace_bytes(int32_t R, int32_t K);
+
+/* KoLeo (Sablayrolles et al. 2019, as DINOv2 applies it) on the rows x_i of feats [>= G * B, D], 16-bit activations (f32 for the
+ * _f32 entry points), crop g = rows g B .. g B + B - 1, computed in f32 with eps = 1e-8:
+ *     y_i = x_i / max(||x_i||, eps);  I_i = argmax_{j != i} y_i . y_j within the crop (the lowest index wins a tie)
+ *     delta_i = y_i - y_I + eps;  d_i = ||delta_i||;  koleo = sum_g -(1 / B) sum_i log(d_i + eps)
+ * gv_koleo_fwd writes koleo[0], nn[i] = I_i (index within the crop) and y, 1 / max(||x||, eps), d into the workspace.
+ * gv_koleo_bwd, from that workspace and nn, with I held constant and w_i = 1 / (B d_i (d_i + eps)):
+ *     gy_i = -w_i delta_i + sum_{i': I_i' = i} w_i' delta_i';  gx_i = (gy_i - y_i (y_i . gy_i)) / max(||x_i||, eps)
+ *     dfeats_i = round(float(dfeats_i) + weight [* loss_scale[0]] * gx_i) in place for the rows [0, G * B); no other row is touched.
+ * The backward gathers (row i scans its crop for I_i' == i): no atomics, bitwise the same run to run.
+ * Limits: 1 <= G <= 4, 2 <= B <= 1024, D a multiple of 64 up to 768, ld >= D, weight finite and >= 0, workspace 16-byte aligned
+ * and of gv_koleo_workspace_bytes(G, B, D) bytes.  A refused call returns GV_E_* before any launch.                          */
+typedef struct {
+    const void*  feats;      /* [>= G * B, D], row stride ld (forward)                                   */
+    void*        dfeats;     /* [>= G * B, D], row stride ld (backward)                                  */
+    void*        workspace; int64_t workspace_bytes;
+    int32_t*     nn;         /* i32 [G * B]                                                              */
+    float*       koleo;      /* f32 [1] (forward)                                                        */
+    const float* loss_scale; /* optional DEVICE scalar that multiplies the gradient (fp16 loss scaling)  */
+    int64_t ld;
+    int32_t G, B, D;
+    float   weight;          /* koleo_weight (backward)                                                  */
+} gv_koleo_args;
+int gv_koleo_fwd(const gv_koleo_args* a, void* stream);
+int gv_koleo_bwd(const gv_koleo_args* a, void* stream);
+int gv_koleo_fwd_f32(const gv_koleo_args* a, void* stream);
+int gv_koleo_bwd_f32(const gv_koleo_args* a, void* stream);
+/* scratch bytes of gv_koleo_fwd / _bwd; -1 with gv_last_error() set for a shape they would refuse.  Touches no GPU. */
+int64_t gv_koleo_workspace_bytes(int32_t G, int32_t B, int32_t D);
+
 #ifdef __cplusplus
 }
 #endif

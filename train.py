@@ -96,6 +96,11 @@ def build_parser():
     g.add_argument("--warmup-teacher-temp-epochs", type=int, default=0)
     g.add_argument("--weight-decay-end", type=float, default=0.4)
     g.add_argument("--freeze-last-layer", type=int, default=1, help="epochs during which the head's last layer is not updated")
+    g.add_argument("--centering", default="center", choices=("center", "sinkhorn_knopp"), help="DINO: how the teacher's logits are centred -- the "
+                   "EMA centre of DINO, or DINOv2's Sinkhorn-Knopp iterations over the step's teacher logits of all ranks (gv_sinkhorn_*)")
+    g.add_argument("--sinkhorn-iters", type=int, default=3, help="--centering sinkhorn_knopp: iterations (1..8)")
+    g.add_argument("--koleo-weight", type=float, default=0.0, help="DINO: weight of the KoLeo regulariser on the student's CLS features of "
+                   "every global crop (gv_koleo_fwd / gv_koleo_bwd); 0 = off, DINOv2 uses 0.1")
     g.add_argument("--knn-monitor", action="store_true", help="DINO: weighted k-NN classifier on the teacher's frozen features as the training "
                    "monitor (bank = training-fold slides, queries = evaluation fold; gv_knn_vote): eval_knn_top1 / eval_knn_auc_per_patch / "
                    "eval_knn_auc_per_slide in summary.csv, checkpoints chosen on --eval-metric among them")
@@ -159,6 +164,11 @@ def parse_args(argv=None):
 
 SUPPORTED_OPTS = ("sgd", "adam", "adamw", "lamb")  # modes of gv_adamw_ema (sgd = momentum + nesterov, timm's default for 'sgd') + gv_lamb
 SUPPORTED_SCHEDS = ("cosine", "step")               # gipvit/sched.py
+
+
+def dino_loss_options(args) -> dict:
+    """The DINOv2 loss options of the command line as DinoEngine's keyword arguments."""
+    return dict(centering=args.centering, sinkhorn_iters=args.sinkhorn_iters, koleo_weight=args.koleo_weight)
 
 
 def check_supported(args, log=_logger.warning):
@@ -319,6 +329,16 @@ def check_supported(args, log=_logger.warning):
         if resolve_eval_metric(args.eval_metric, bool(args.knn_monitor), bool(args.linear_probe), True) not in names:
             raise SystemExit(f"--eval-metric {args.eval_metric}: the monitors of this run report {names} (a bare name is the k-NN monitor's "
                              "when that is on, else the linear probe's, else the MIL probe's)")
+    # the DINOv2 loss options belong to the DINO step
+    if not args.dino and (args.centering != "center" or args.koleo_weight != 0):
+        raise SystemExit("--centering sinkhorn_knopp / --koleo-weight change the DINO step's loss: they need --dino")
+    if not (math.isfinite(args.koleo_weight) and args.koleo_weight >= 0):
+        raise SystemExit(f"--koleo-weight {args.koleo_weight}: a finite weight >= 0")
+    if not 1 <= args.sinkhorn_iters <= 8:
+        raise SystemExit(f"--sinkhorn-iters {args.sinkhorn_iters}: 1 .. 8 iterations")
+    if args.koleo_weight > 0 and args.batch_size < 2:
+        raise SystemExit(f"--koleo-weight {args.koleo_weight} with --batch-size {args.batch_size}: KoLeo takes every tile's nearest neighbour among "
+                         "the other tiles of its crop on this GPU, it needs at least 2")
     if args.supervised and args.dino:
         raise SystemExit("--supervised (fine-tune with labels, train.py:715-717) and --dino (self-supervised) exclude each other")
     # mixup / cutmix / BCE (train.py:752-771, 828-846): the supervised step's batch, target and loss
@@ -639,7 +659,8 @@ def main(argv=None, transform=None):
         eng = DinoEngine(arch=arch, img_size=img, out_dim=args.out_dim, batch=B, tile=tile, n_local=args.local_crops_number,
                          gsize=args.global_crop_size, lsize=args.local_crop_size, lr=lr, weight_decay=args.weight_decay, betas=betas, eps=eps,
                          momentum_teacher=args.momentum_teacher, teacher_temp=args.teacher_temp, clip_grad=args.clip_grad or 0.0,
-                         mean=mean, std=std, device=dev, reducer=reducer, precision=args.precision, clip_mode=args.clip_mode)
+                         mean=mean, std=std, device=dev, reducer=reducer, precision=args.precision, clip_mode=args.clip_mode,
+                         **dino_loss_options(args))
         bb = (M.load_encoder_checkpoint(args.initial_checkpoint, arch, img) if args.initial_checkpoint
               else M.init_vit_state(arch, img, 0, seed=args.seed))
         eng.load_state(bb, M.init_dino_head_state(eng.D, args.out_dim, seed=args.seed + 1))
@@ -846,7 +867,8 @@ def main(argv=None, transform=None):
                                  "LR: {:.3e}  Data: {:.3f} ({:.3f})".format(
                                      epoch, batch_idx, updates_per_epoch, 100.0 * batch_idx / max(last_idx, 1), losses.val, losses.avg,
                                      batch_time.val, B * world / batch_time.val, batch_time.avg, B * world / batch_time.avg, logged_lr(cur_lr),
-                                     data_time.val, data_time.avg))
+                                     data_time.val, data_time.avg)
+                                 + ("  KoLeo: {:#.4g}".format(float(eng.koleo)) if args.dino and args.koleo_weight > 0 else ""))
                 if saver is not None and args.recovery_interval and (batch_idx + 1) % args.recovery_interval == 0:
                     saver.save_recovery(epoch, batch_idx, eng.arena.state_dict(), extra=extra_state())
             end = time.time()
