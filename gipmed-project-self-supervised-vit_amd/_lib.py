@@ -181,6 +181,20 @@ gv_sinkhorn_args = _struct("gv_sinkhorn_args", [
 gv_koleo_args = _struct("gv_koleo_args", [
     ("feats", vp), ("dfeats", vp), ("workspace", vp), ("workspace_bytes", i64), ("nn", vp), ("koleo", vp), ("loss_scale", vp), ("ld", i64),
     ("G", i32), ("B", i32), ("D", i32), ("weight", f32)])
+gv_mask_tokens_fwd_args = _struct("gv_mask_tokens_fwd_args", [
+    ("x", vp), ("mask_token", vp), ("pos", vp), ("rows", vp), ("M", i32), ("N", i32), ("D", i32), ("n_rows", i32)])
+gv_mask_tokens_bwd_args = _struct("gv_mask_tokens_bwd_args", [
+    ("g", vp), ("gpatch", vp), ("dmask_token", vp), ("rows", vp), ("workspace", vp), ("workspace_bytes", i64), ("M", i32), ("N", i32), ("D", i32),
+    ("n_rows", i32), ("accumulate", i32)])
+gv_rows_gather_args = _struct("gv_rows_gather_args", [
+    ("x", vp), ("x_stride", i64), ("rows", vp), ("out", vp), ("scale", vp), ("scale_out", vp), ("M", i32), ("D", i32), ("n_rows", i32)])
+gv_rows_scatter_args = _struct("gv_rows_scatter_args", [
+    ("g_src", vp), ("g", vp), ("g_stride", i64), ("gb_src", vp), ("gb", vp), ("gb_stride", i64), ("rows", vp), ("M", i32), ("D", i32), ("n_rows", i32)])
+gv_ibot_loss_args = _struct("gv_ibot_loss_args", [
+    ("student", vp), ("teacher", vp), ("center", vp), ("weight", vp), ("dstudent", vp), ("loss", vp), ("center_sum", vp), ("workspace", vp),
+    ("workspace_bytes", i64), ("M", i32), ("K", i32), ("student_temp", f32), ("teacher_temp", f32), ("ibot_weight", f32), ("grad_scale", f32),
+    ("hyper", vp), ("loss_scale", vp)])
+gv_patch_center_update_args = _struct("gv_patch_center_update_args", [("center", vp), ("center_sum", vp), ("K", i32), ("momentum", f32)])
 
 # entry point -> argument struct (every `int gv_*(const args*, void* stream)` of the header)
 ENTRY_POINTS = {
@@ -209,10 +223,13 @@ ENTRY_POINTS = {
     "gv_token_mean_fwd": gv_token_mean_fwd_args, "gv_token_mean_bwd": gv_token_mean_bwd_args, "gv_token_mean_bwd_f32": gv_token_mean_bwd_args,
     "gv_sinkhorn_shift": gv_sinkhorn_args, "gv_sinkhorn_cols": gv_sinkhorn_args, "gv_sinkhorn_rows": gv_sinkhorn_args, "gv_sinkhorn_finish": gv_sinkhorn_args,
     "gv_koleo_fwd": gv_koleo_args, "gv_koleo_bwd": gv_koleo_args, "gv_koleo_fwd_f32": gv_koleo_args, "gv_koleo_bwd_f32": gv_koleo_args,
+    "gv_mask_tokens_fwd": gv_mask_tokens_fwd_args, "gv_mask_tokens_bwd": gv_mask_tokens_bwd_args, "gv_mask_tokens_bwd_f32": gv_mask_tokens_bwd_args,
+    "gv_rows_gather": gv_rows_gather_args, "gv_rows_scatter": gv_rows_scatter_args, "gv_rows_scatter_f32": gv_rows_scatter_args,
+    "gv_ibot_loss": gv_ibot_loss_args, "gv_ibot_loss_f32": gv_ibot_loss_args, "gv_patch_center_update": gv_patch_center_update_args,
 }
 PLAIN_SYMBOLS = ("gv_version", "gv_last_error", "gv_target", "gv_act_format", "gv_linear_workspace_bytes", "gv_workspace_bytes", "gv_linear_timing", "gv_linear_timing_read",
                  "gv_linear_ln_blocks", "gv_knn_workspace_bytes", "gv_linprobe_workspace_bytes", "gv_mil_workspace_bytes",
-                 "gv_sinkhorn_workspace_bytes", "gv_koleo_workspace_bytes")
+                 "gv_sinkhorn_workspace_bytes", "gv_koleo_workspace_bytes", "gv_mask_tokens_workspace_bytes", "gv_ibot_loss_workspace_bytes")
 
 
 class gv_linear_timing_row(C.Structure):
@@ -263,6 +280,10 @@ def _load():
     lib.gv_sinkhorn_workspace_bytes.restype = C.c_int64
     lib.gv_koleo_workspace_bytes.argtypes = [C.c_int32] * 3
     lib.gv_koleo_workspace_bytes.restype = C.c_int64
+    lib.gv_mask_tokens_workspace_bytes.argtypes = [C.c_int32] * 2
+    lib.gv_mask_tokens_workspace_bytes.restype = C.c_int64
+    lib.gv_ibot_loss_workspace_bytes.argtypes = [C.c_int32] * 2
+    lib.gv_ibot_loss_workspace_bytes.restype = C.c_int64
     return lib
 
 

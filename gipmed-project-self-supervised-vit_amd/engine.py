@@ -229,9 +229,10 @@ def dino_head_specs(in_dim: int, out_dim: int, hidden: int = 2048, bottleneck: i
 
 
 def no_weight_decay(name: str, shape) -> bool:
-    """timm create_optimizer_v2 filter: 1-D, *.bias, pos_embed, cls_token."""
+    """timm create_optimizer_v2 filter: 1-D, *.bias, pos_embed, cls_token -- and iBOT's mask_token (DINOv2 lists it
+    with them)."""
     base = name.split(".", 1)[1] if name.startswith(("backbone.", "head.")) else name
-    return len(shape) <= 1 or name.endswith(".bias") or base in ("pos_embed", "cls_token") or name.endswith("weight_g")
+    return len(shape) <= 1 or name.endswith(".bias") or base in ("pos_embed", "cls_token", "mask_token") or name.endswith("weight_g")
 
 
 class Arena:
@@ -387,6 +388,7 @@ class VitGroup:
         self.prepared = False     # VitRunner.prepare_backward has zeroed this group's backward scratch for the coming backward
         self.dropout, self.tmp = None, None   # --drop: (p, step seed) and the f32 branch-output buffer of the unfused residual adds (set_dropout)
         self.rs = None            # stochastic depth: f32 [depth, 2, T] row factors of the attention / MLP branch (set_drop)
+        self.all_tokens = False   # iBOT: patch rows of the last block reach the head, so the CLS-only tail is off (VitRunner._cls_tail)
         self.drop_img = None      # ... and the per-image factors they were expanded from
         self._row_img = None
 
@@ -504,7 +506,7 @@ class VitRunner:
 
     # ---- forward: tiles -> CLS features written into feats[row_off + seg.img0 ...]
     def forward(self, W: Weights, G: VitGroup, tiles_u8, windows, mean, std, feats, row_off: int = 0, fill=None, on_side: bool = False,
-                capture: Optional[Capture] = None, mix: Optional[torch.Tensor] = None, erase=None):
+                capture: Optional[Capture] = None, mix: Optional[torch.Tensor] = None, erase=None, masks=None, patch=None):
         """windows: one list of (y0, x0) crop origins per segment; tiles_u8: one NHWC u8 tensor for all
         segments, or one per segment (pre-cut crops: each with the single window (0, 0)).  A float32 NCHW source (already
         normalised, engine.input_form) goes through gv_patchify_nchw instead, without mean / std.  ``fill``: per-tile normalised
@@ -514,8 +516,15 @@ class VitRunner:
         ``mix``: a device mix table (gipvit.mixup.MixPlan.table) -- the single-segment, single-window batch is mixed inside the
         patchify pass (gv_patchify_mix / gv_patchify_nchw_mix); None issues exactly the default launches.
         ``erase``: (device erase table, seed) of a gipvit.erasing.ErasePlan -- random erasing in that same pass, after ``fill`` and
-        ``mix`` (gv_patchify_erase / gv_patchify_nchw_erase); None issues exactly the default launches."""
+        ``mix`` (gv_patchify_erase / gv_patchify_nchw_erase); None issues exactly the default launches.
+        ``masks``: a gipvit.masking.MaskPlan over the images of the FIRST segment (iBOT: the student's global crops) -- the marked
+        patch embeddings are replaced by ``mask_token`` (+ pos) behind the patch-embedding product (gv_mask_tokens_fwd).
+        ``patch``: (MaskPlan, PatchRows) -- the final norm also runs on the plan's rows of the first segment, into
+        ``PatchRows.hb.feats`` (gv_rows_gather + gv_layernorm_fwd); the group must have ``all_tokens`` set.  Either None, or a
+        plan without a marked patch, issues exactly the default launches."""
         D, T, H = self.D, G.T, self.H
+        if (masks is not None or patch is not None) and not G.all_tokens:
+            raise ValueError("masks / patch: the group must run its last block on every token (VitGroup.all_tokens)")
         cap = capture
         if mix is not None and (len(G.segs) != 1 or len(windows[0]) != 1):
             raise ValueError("mix: the supervised step's one window of one segment only")
@@ -555,6 +564,9 @@ class VitRunner:
             ops.cls_rows(xs, W.f("cls_token").view(-1), pos, sg.n_img, sg.N, D)
             ops.linear(sg.patches, W.w("patch_embed.proj.weight").view(D, 768), xs, sg.n_img * sg.P, D, 768,
                        epilogue=E.EPI_BIAS | E.EPI_POS, bias=W.f("patch_embed.proj.bias"), pos=pos, P=sg.P)
+            if masks is not None and k == 0 and masks.M > 0:
+                masks_fit(masks, sg)
+                ops.mask_tokens_fwd(xs, W.f("mask_token").view(-1), pos, masks.rows, masks.M, sg.N, D)
         # --drop: counter-based masks at the four nn.Dropout sites (gv_dropout / gv_dropout_add); the residual adds then run unfused
         dp = G.dropout
         dseed = (lambda layer, site: ops.dropout_site_seed(dp[1], layer, site)) if dp else None
@@ -642,6 +654,14 @@ class VitRunner:
             else:
                 ops.layernorm_fwd(sg.rows(xl), W.f("norm.weight"), W.f("norm.bias"), sg.n_img, D, x_stride=sg.N * D,
                                   y=feats[r0:r0 + sg.n_img], mean=sg.fstats[0], rstd=sg.fstats[1])
+        if patch is not None and patch[0].M > 0:
+            # iBOT: the final norm on the marked rows of the first segment, compact and in table order, for the head's second pass
+            plan, pr = patch
+            sg, M = G.segs[0], plan.M
+            masks_fit(plan, sg, pr)
+            rs_last = G.rs[self.depth - 1, 1] if (G.rs is not None and G.save) else None
+            ops.rows_gather(sg.rows(xl), plan.rows, pr.x, M, D, sg.T, scale=rs_last, scale_out=pr.scale if rs_last is not None else None)
+            ops.layernorm_fwd(pr.x, W.f("norm.weight"), W.f("norm.bias"), M, D, y=pr.hb.feats, mean=pr.mean, rstd=pr.rstd)
 
     @staticmethod
     def require_trainable(G: VitGroup):
@@ -665,7 +685,7 @@ class VitRunner:
         """Does this group run the last block's projection / MLP on the CLS rows only?  (Training groups: on the grouped
         weight-gradient path and without --drop, whose backward this build restates for that case.)  Never for a mean-pooled
         group: every token of the last block reaches the feature."""
-        return G.pool != "avg" and self.cls_last and G.dropout is None and (not G.save or self.group_dw)
+        return G.pool != "avg" and not G.all_tokens and self.cls_last and G.dropout is None and (not G.save or self.group_dw)
 
     def _last_block_tail_fwd(self, W: Weights, G: VitGroup, i: int, xa: torch.Tensor, on_side: bool):
         """x + proj(attention) -> norm2 -> MLP -> residual of block i for the CLS rows only (vit.pyc@L146-152 on the rows that
@@ -702,10 +722,14 @@ class VitRunner:
         G.prepared = True
 
     # ---- backward from d(CLS features) bf16 [G.n_img, D]; gradients ACCUMULATE into the arena
-    def backward(self, W: Weights, G: VitGroup, dfeat: torch.Tensor, on_block_done=None):
+    def backward(self, W: Weights, G: VitGroup, dfeat: torch.Tensor, on_block_done=None, patch=None):
         """``on_block_done(i)`` is called once block i's parameter gradients are complete
-        (data-parallel engines start that block's all-reduce there)."""
+        (data-parallel engines start that block's all-reduce there).  ``patch``: the (MaskPlan, PatchRows) the forward was given --
+        the head's gradient of the marked rows (``PatchRows.hb.dfeats``) goes back through the final norm into those rows of the
+        residual gradient and of the last block's MLP-half dY, and ``mask_token`` gets its gradient behind gv_tokens_bwd."""
         self.require_trainable(G)
+        if patch is not None and patch[0].M == 0:
+            patch = None
         D, T, H = self.D, G.T, self.H
         E = L
         ACC = E.EPI_ACCUM
@@ -751,6 +775,16 @@ class VitRunner:
                                   gb_scale=None if rs is None else G.drop_img[self.depth - 1, 1, im])
             ops.ln_finalize(ring[0], L.LN_PARTIAL_BLOCKS, D, W.g("norm.weight"), W.g("norm.bias"),
                             None if dp else W.g(f"blocks.{self.depth - 1}.mlp.fc2.bias"))
+        if patch is not None:
+            # the marked rows (unique, never a CLS row): the norm's backward on the compact copy, its three column sums next to the
+            # CLS rows' share, then a plain store into the rows prepare_backward left at zero
+            assert not cls_tail and G.pool != "avg" and dp is None
+            plan, pr = patch
+            sg, M = G.segs[0], plan.M
+            ops.layernorm_bwd(pr.hb.dfeats, pr.x, pr.mean, pr.rstd, W.f("norm.weight"), pr.g, pr.gb, ring[0], M, D, g_init=True,
+                              gb_scale=None if rs is None else pr.scale)
+            ops.ln_finalize(ring[0], L.LN_PARTIAL_BLOCKS, D, W.g("norm.weight"), W.g("norm.bias"), W.g(f"blocks.{self.depth - 1}.mlp.fc2.bias"))
+            ops.rows_scatter(pr.g, sg.rows(G.g), plan.rows, M, D, sg.T, gb_src=pr.gb, gb=sg.rows(gb_first))
         # The weight-gradient GEMMs are off the critical path (nothing in backward consumes dW):
         # they run on a side stream beside the dX chain, so their tiles fill the tail of every
         # main-stream kernel (a 345 x 3-tile GEMM occupies 2.02 rounds of the 512 workgroup slots).
@@ -861,8 +895,15 @@ class VitRunner:
             ops.dropout(G.g, dseed(0, 0), dp[0], n=T * D)                                 # pos_drop's mask on the token gradient
         # token assembly + patch embedding, per segment
         gpos = W.g("pos_embed").view(-1, D)
-        for sg in G.segs:
+        for k, sg in enumerate(G.segs):
             ops.tokens_bwd(sg.rows(G.g), sg.gpatch, sg.dpos, None, sg.n_img, sg.N, D, accumulate=False)
+            if patch is not None and k == 0:
+                # a masked patch's token is mask_token + pos: its gradient goes to mask_token (and stays in dpos), the patch embedding
+                # gets nothing from it -- zero rows of gpatch for the weight, and its share taken back out of the bias's column sum
+                pr = patch[1]
+                ops.mask_tokens_bwd(sg.rows(G.g), sg.gpatch, pr.dmask, patch[0].rows, pr.mt_ws, patch[0].M, sg.N, D, accumulate=False)
+                ops.small_matmul(self.one, pr.dmask, W.g("mask_token").view(1, D), 1, D, 1, sam=0, sak=0, sbk=0, sbn=1, accumulate=True)
+                ops.small_matmul(pr.minus_one, pr.dmask, W.g("patch_embed.proj.bias").view(1, D), 1, D, 1, sam=0, sak=0, sbk=0, sbn=1, accumulate=True)
             # d cls_token = sum over images of the CLS-row gradient = dpos row 0
             ops.small_matmul(self.one, sg.dpos, W.g("cls_token").view(1, D), 1, D, 1, sam=0, sak=0, sbk=0, sbn=1, accumulate=True)
             ops.linear(sg.gpatch, sg.patches, W.g("patch_embed.proj.weight").view(D, 768), D, 768, sg.n_img * sg.P,
@@ -896,6 +937,31 @@ class HeadBuffers:
             self.dwn = e((K, bott), f32)
 
 
+class PatchRows:
+    """Buffers of iBOT's marked rows for one network: the head buffers of up to ``R`` rows (``hb``), the compact f32 copy of the
+    rows in front of the final norm with its statistics and -- for the student (``save``) -- the norm's backward outputs, the rows'
+    stochastic-depth factors and the scratch of gv_mask_tokens_bwd."""
+
+    def __init__(self, R: int, D: int, K: int, hidden: int, bott: int, device, save: bool, act=bf16):
+        e = lambda shape, dt: _empty(shape, dt, device)
+        self.R = R
+        self.hb = HeadBuffers(R, D, K, hidden, bott, device, save, act)
+        self.x, self.mean, self.rstd = e((R, D), f32), e((R,), f32), e((R,), f32)
+        if save:
+            self.g, self.gb, self.scale = e((R, D), f32), e((R, D), act), e((R,), f32)
+            self.dmask = e((D,), f32)
+            self.mt_ws = e((_ws_bytes("gv_mask_tokens_workspace_bytes", R, D) // 4,), f32)
+            self.minus_one = torch.full((1,), -1.0, dtype=f32, device=device)
+
+
+def masks_fit(plan, sg: Segment, pr: Optional["PatchRows"] = None):
+    """A MaskPlan against the segment it indexes (and the buffers its rows go to): a ValueError before anything is launched."""
+    if plan.J != sg.n_img or plan.P != sg.P:
+        raise ValueError(f"masks: a plan for {plan.J} images of {plan.P} patches, the global crops are {sg.n_img} images of {sg.P}")
+    if pr is not None and plan.M > pr.R:
+        raise ValueError(f"masks: {plan.M} marked patches, the iBOT head buffers hold {pr.R} rows (ibot_mask_ratio / ibot_mask_prob size them)")
+
+
 class HeadRunner:
     def __init__(self, D: int, K: int, hidden: int, bott: int, device):
         self.D, self.K, self.hidden, self.bott = D, K, hidden, bott
@@ -904,10 +970,11 @@ class HeadRunner:
         self.ws_main = _empty((L.lib.gv_linear_workspace_bytes() // 4,), f32, device)
         self.ws_side = _empty((L.lib.gv_linear_workspace_bytes() // 4,), f32, device)
 
-    def forward(self, W: Weights, wn: torch.Tensor, hb: HeadBuffers, on_side: bool = False):
+    def forward(self, W: Weights, wn: torch.Tensor, hb: HeadBuffers, on_side: bool = False, rows: Optional[int] = None):
         """``on_side``: the call is queued on the engine's side stream (the teacher's head beside the student's forward): its
-        split-K products then take the side stream's scratch."""
-        R, D, Hd, Bt, K, E = hb.R, self.D, self.hidden, self.bott, self.K, L
+        split-K products then take the side stream's scratch.  ``rows``: the first so many rows of the buffers only (iBOT's marked
+        rows: the buffers are sized once, every step has its own count)."""
+        R, D, Hd, Bt, K, E = (hb.R if rows is None else rows), self.D, self.hidden, self.bott, self.K, L
         ws = self.ws_side if on_side else self.ws_main
         ops.linear(hb.feats, W.w("mlp.0.weight"), hb.h1, R, Hd, D, epilogue=E.EPI_BIAS | E.EPI_GELU | E.EPI_SAVE_PRE,
                    bias=W.f("mlp.0.bias"), aux_out=hb.h1p)
@@ -917,10 +984,10 @@ class HeadRunner:
         ops.l2norm_fwd(hb.z, hb.zn, hb.inv, R, Bt)
         ops.linear(hb.zn, wn, hb.logits, R, K, Bt)
 
-    def backward(self, W: Weights, wn: torch.Tensor, hb: HeadBuffers, train_last_layer: bool, sx: SideStream):
+    def backward(self, W: Weights, wn: torch.Tensor, hb: HeadBuffers, train_last_layer: bool, sx: SideStream, rows: Optional[int] = None):
         """The weight-gradient products (they feed nothing in backward) go through ``sx``, the engine's side stream: each is
-        queued there once its operands are ready, with the scratch of the stream it runs on."""
-        R, D, Hd, Bt, K, E = hb.R, self.D, self.hidden, self.bott, self.K, L
+        queued there once its operands are ready, with the scratch of the stream it runs on.  ``rows``: as in ``forward``."""
+        R, D, Hd, Bt, K, E = (hb.R if rows is None else rows), self.D, self.hidden, self.bott, self.K, L
         ACC = E.EPI_ACCUM
         ws = self.ws_side if sx.side is not None else self.ws_main
 
@@ -985,6 +1052,23 @@ def _prefixed(backbone: Dict[str, torch.Tensor], head: Dict[str, torch.Tensor]) 
     return st
 
 
+def _check_ibot(weight, ratio, prob, gsize: int, drop: float, centering: str) -> float:
+    """The iBOT options an engine is built with (the driver's check_supported says the same before any GPU work) -> the weight."""
+    from .masking import check_mask_options
+    if not (isinstance(weight, (int, float)) and math.isfinite(weight) and weight >= 0):
+        raise ValueError(f"ibot_weight {weight}: finite and >= 0")
+    check_mask_options(ratio, prob)
+    if weight > 0:
+        if gsize < 64:
+            raise ValueError(f"ibot_weight > 0 needs global crops of at least 64 px (a 4 x 4 patch grid), got {gsize}")
+        if drop and drop > 0:
+            raise ValueError("ibot_weight > 0 with drop > 0 is not built (the dropout path has no all-token last block with a row table)")
+        if centering == "sinkhorn_knopp":
+            raise ValueError("ibot_weight > 0 with centering 'sinkhorn_knopp' is not built: Sinkhorn-Knopp over a patch-row count that varies per "
+                             "rank is missing, and the EMA patch centre in its place would be a silent substitution")
+    return float(weight)
+
+
 class TrainEngine:
     """What the two training engines share: the precision / clip-mode arguments and the loss scaler, the gradients handed out,
     and the clip / loss-scale part of the optimizer's arguments."""
@@ -1027,14 +1111,22 @@ class DinoEngine(TrainEngine):
                  gsize=224, lsize=96, hidden=2048, bottleneck=256, lr=5e-4, weight_decay=0.04, betas=(0.9, 0.999), eps=1e-8,
                  momentum_teacher=0.996, student_temp=0.1, teacher_temp=0.04, center_momentum=0.9, clip_grad: float = 0.0,
                  mean=MEAN_RON, std=STD_RON, windows=None, device="cuda:0", reducer=None, precision: str = "bf16", clip_mode: str = "norm",
-                 centering: str = "center", sinkhorn_iters: int = 3, koleo_weight: float = 0.0):
+                 centering: str = "center", sinkhorn_iters: int = 3, koleo_weight: float = 0.0, ibot_weight: float = 0.0,
+                 ibot_mask_ratio: Tuple[float, float] = (0.1, 0.5), ibot_mask_prob: float = 0.5, drop: float = 0.0):
         """``precision``: "bf16" (the training path) or "fp32" (every GEMM / attention operand, the head activations, the
         weight-normalised prototype matrix and the logit gradient in f32 -- the verification mode of SURVEY 8d's fp32 column).
         ``clip_mode``: "norm" (global norm, the reference default) or "value" (element-wise clamp), train.py:1072-1077.
         ``centering``: "center" (the EMA centre of DINO) or "sinkhorn_knopp" (DINOv2: ``sinkhorn_iters`` Sinkhorn-Knopp iterations
         over the teacher logits of all ranks, handed to the loss as ``sk_center``; the EMA centre keeps running beside it).
         ``koleo_weight`` > 0 adds that multiple of the KoLeo regulariser on the student's features of every global crop (DINOv2 uses
-        0.1): ``koleo`` is its unweighted value, local to the rank, ``loss`` stays the DINO term."""
+        0.1): ``koleo`` is its unweighted value, local to the rank, ``loss`` stays the DINO term.
+        ``ibot_weight`` > 0 adds that multiple of the iBOT masked-patch term (DINOv2 uses 1.0): every step then takes a
+        gipvit.masking.MaskPlan (``masks=``) over its global crops, the student sees ``backbone.mask_token`` in place of the marked
+        patches, both networks run their last block on every token and the marked rows go through the same head a second time
+        against the second EMA centre ``patch_center``.  ``ibot`` is the term's unweighted value, ``loss`` stays the DINO term.
+        ``ibot_mask_ratio`` / ``ibot_mask_prob`` size the patch-row buffers (masking.max_rows).  ``drop``: the run's --drop, only
+        so that the combination is refused here."""
+        self.ibot_weight = _check_ibot(ibot_weight, ibot_mask_ratio, ibot_mask_prob, gsize, drop, centering)
         if centering not in ("center", "sinkhorn_knopp"):
             raise ValueError(f"centering {centering!r}: 'center' or 'sinkhorn_knopp'")
         if not 1 <= int(sinkhorn_iters) <= 8:
@@ -1056,6 +1148,8 @@ class DinoEngine(TrainEngine):
         self.gwins, self.lwins = list(windows[:n_global]), list(windows[n_global:])
         specs = OrderedDict(("backbone." + k, v) for k, v in vit_param_specs(arch, img_size, 0).items())
         specs.update(("head." + k, v) for k, v in dino_head_specs(D, out_dim, hidden, bottleneck).items())
+        if self.ibot_weight > 0:      # last of the no-decay part of the arena (every other offset is that of a run without iBOT)
+            specs["backbone.mask_token"] = (1, D)
         self.arena = Arena(specs, dev, teacher=True)
         self.sW, self.tW = Weights(self.arena, "backbone.", fp32=fp32), Weights(self.arena, "backbone.", teacher=True, fp32=fp32)
         self.sH, self.tH = Weights(self.arena, "head.", fp32=fp32), Weights(self.arena, "head.", teacher=True, fp32=fp32)
@@ -1088,6 +1182,21 @@ class DinoEngine(TrainEngine):
             # before gv_koleo_bwd reads one, and the backward clamps what it reads into the crop
             self.koleo_nn = torch.zeros(n_global * B, dtype=torch.int32, device=dev)
             self.koleo_ws = _empty((_ws_bytes("gv_koleo_workspace_bytes", n_global, B, D) // 4,), f32, dev)
+        self.ibot = self.patch_center = self.patch_center_sum = self.pr_s = self.pr_t = None
+        if self.ibot_weight > 0:
+            from .masking import max_rows
+            if L.ACT_FORMAT == "f16" and not fp32:
+                raise ValueError("ibot_weight > 0 is not built for the float16 library (--amp needs --amp-dtype bfloat16)")
+            self.g_stu.all_tokens = self.g_teach.all_tokens = True
+            R = max(1, max_rows(n_global * B, (gsize // 16) ** 2, ibot_mask_ratio, ibot_mask_prob))
+            self.ibot_rows = R
+            self.pr_s = PatchRows(R, D, out_dim, hidden, bottleneck, dev, save=True, act=act)
+            self.pr_t = PatchRows(R, D, out_dim, hidden, bottleneck, dev, save=False, act=act)
+            self.ibot = torch.zeros(1, dtype=f32, device=dev)
+            self.patch_center = torch.zeros(out_dim, dtype=f32, device=dev)
+            # [K + 1]: the teacher's column sums and, in the last slot, the row count -- one vector through the all-reduce
+            self.patch_center_sum = torch.zeros(out_dim + 1, dtype=f32, device=dev)
+            self.ibot_ws = _empty((_ws_bytes("gv_ibot_loss_workspace_bytes", R, out_dim) // 4,), f32, dev)
         self.gnorm_sq = torch.zeros(1, dtype=f32, device=dev)
         self.red_ws = _empty((1024,), f32, dev)
         self.hyper = torch.zeros(L.HYP_COUNT, dtype=f32, device=dev)
@@ -1106,7 +1215,17 @@ class DinoEngine(TrainEngine):
             self._block_range[i] = (min(lo for lo, _ in spans), max(hi for _, hi in spans))
 
     # ---- parameters ----------------------------------------------------------------
+    def _with_mask_token(self, backbone: Dict[str, torch.Tensor], what: str) -> Dict[str, torch.Tensor]:
+        """iBOT on, and a state from a run without it: ``mask_token`` starts at zeros (DINOv2's initial value), and says so."""
+        if self.ibot_weight > 0 and "mask_token" not in backbone:
+            print(f"ibot: the {what} state has no mask_token: it starts at zeros", flush=True)
+            backbone = dict(backbone, mask_token=torch.zeros(1, self.D))
+        elif self.ibot_weight == 0 and "mask_token" in backbone:
+            print(f"the {what} state holds iBOT's mask_token, this run has no iBOT term (ibot_weight 0): mask_token is dropped", flush=True)
+        return backbone
+
     def load_state(self, backbone: Dict[str, torch.Tensor], head: Dict[str, torch.Tensor]):
+        backbone = self._with_mask_token(backbone, "student")
         self.arena.load(_prefixed(backbone, head))
         self.arena.t.copy_(self.arena.p)            # teacher starts as a copy of the student
         self.refresh_bf16()
@@ -1114,7 +1233,7 @@ class DinoEngine(TrainEngine):
     def load_teacher_state(self, backbone: Dict[str, torch.Tensor], head: Dict[str, torch.Tensor], center: Optional[torch.Tensor] = None):
         """Restore the EMA teacher (and the centre) of a saved run: without it a resumed run would restart the
         teacher from the student while the momentum schedule is already near 1."""
-        self.arena.load(_prefixed(backbone, head), self.arena.t)
+        self.arena.load(_prefixed(self._with_mask_token(backbone, "teacher"), head), self.arena.t)
         if center is not None:
             self.center.copy_(center.to(self.center.device, f32).view(-1))
         self.refresh_bf16()
@@ -1144,6 +1263,8 @@ class DinoEngine(TrainEngine):
     def set_dropout(self, p: float, seed: int = 0):
         """--drop for the STUDENT's next step (the teacher runs in eval mode): probability and this step's 32-bit seed; p = 0 switches it off.
         Under gradient accumulation every micro-batch of the step derives its own seed from this one (forward_backward)."""
+        if p and self.ibot_weight > 0:
+            raise ValueError("--drop with the iBOT term is not built (ibot_weight > 0)")
         self._drop = (float(p), int(seed) & 0xFFFFFFFF) if p else None
         self.g_stu.set_dropout(p, seed)
 
@@ -1163,7 +1284,7 @@ class DinoEngine(TrainEngine):
         vals[L.HYP_STUDENT_TEMP] = self.ts
         ops.store_f32(self.hyper, vals)
 
-    def forward_backward(self, tiles_u8: torch.Tensor, micro: Tuple[int, int] = (0, 1), boxes=None, fill=None, views=None):
+    def forward_backward(self, tiles_u8: torch.Tensor, micro: Tuple[int, int] = (0, 1), boxes=None, fill=None, views=None, masks=None):
         """teacher fwd (global crops) -> student fwd (all crops) -> loss -> backward.
         Leaves gradients in arena.g, loss in self.loss, center_sum.  ``micro = (j, n)``: this is
         micro-batch j of n (gradient accumulation): gradients, loss and centre sums add up over
@@ -1171,9 +1292,20 @@ class DinoEngine(TrainEngine):
         ``views``: (global, local) packed per-crop records of multicrop.ViewAugmentSampler.sample -- with ``boxes``, every crop
         gets its own colour jitter / grayscale / blur / solarisation in the pass that cuts it (gv_crop_augment).
         ``tiles_u8``: uint8 [B, tile, tile, 3] or float32 NCHW [B, 3, tile, tile] already normalised (engine.input_form): float
-        input runs the fixed crop windows only (no ``boxes`` / ``views`` / ``fill``)."""
+        input runs the fixed crop windows only (no ``boxes`` / ``views`` / ``fill``).
+        ``masks``: this micro-batch's gipvit.masking.MaskPlan over the G * B global crops (crop-major, like the feature rows) --
+        given exactly when ``ibot_weight`` > 0."""
         B, G, V = self.B, self.G, self.V
         self.vit.require_trainable(self.g_stu)
+        if (masks is not None) != (self.ibot_weight > 0):
+            raise ValueError("masks= goes with ibot_weight > 0: " + ("this engine was built without the iBOT term" if masks is not None else
+                                                                       "an engine with the iBOT term needs a MaskPlan for every micro-batch"))
+        # (keywords of the iBOT term exist for a step with a plan only: without one every call below is the one it always was)
+        ikw_t = {} if masks is None else dict(patch=(masks, self.pr_t))
+        ikw_s = {} if masks is None else dict(masks=masks, patch=(masks, self.pr_s))
+        M = 0 if masks is None else masks.M
+        if masks is not None:
+            masks_fit(masks, self.g_stu.segs[0], self.pr_s)
         input_form(tiles_u8, B, (self.tile, self.tile), (("fill", fill), ("boxes", boxes), ("views", views)))
         a = self.arena
         mj, mn = micro
@@ -1222,19 +1354,37 @@ class DinoEngine(TrainEngine):
         t_side = sx.side is not None and self.sw.teacher_side
 
         def teacher():
-            self.vit.forward(self.tW, self.g_teach, t_src, t_win, self.mean, self.std, self.hb_t.feats, fill=fill, on_side=t_side)
+            self.vit.forward(self.tW, self.g_teach, t_src, t_win, self.mean, self.std, self.hb_t.feats, fill=fill, on_side=t_side, **ikw_t)
             self.head.forward(self.tH, self.wn_t, self.hb_t, on_side=t_side)
+            if M > 0:
+                self.head.forward(self.tH, self.wn_t, self.pr_t.hb, on_side=t_side, rows=M)
         ev_zero = sx.run(fills)
         ev_teacher = sx.run(teacher) if t_side else teacher()
-        self.vit.forward(self.sW, self.g_stu, s_src, s_win, self.mean, self.std, self.hb_s.feats, fill=fill)
+        self.vit.forward(self.sW, self.g_stu, s_src, s_win, self.mean, self.std, self.hb_s.feats, fill=fill, **ikw_s)
         if self.koleo_weight > 0:
             ops.koleo_fwd(self.hb_s.feats, self.koleo_ws, self.koleo_nn, self.koleo, G, B, self.D)
         self.head.forward(self.sH, self.wn_s, self.hb_s)
+        if M > 0:
+            self.head.forward(self.sH, self.wn_s, self.pr_s.hb, rows=M)
         sx.join(ev_teacher)
         center = self.center if self.centering == "center" else self._sinkhorn()
         ops.dino_loss(self.hb_s.logits, self.hb_t.logits, center, self.hb_s.dlogits, self.loss, self.center_sum,
                       self.loss_ws, B, V, G, self.K, self.ts, self.tt, hyper=self.hyper,
                       loss_scale=self.scaler.scale if self.scaler is not None else None)
+        if masks is not None:
+            if M > 0:
+                ops.ibot_loss(self.pr_s.hb.logits, self.pr_t.hb.logits, self.patch_center, masks.weight, self.pr_s.hb.dlogits, self.ibot,
+                              self.patch_center_sum, self.ibot_ws, M, self.K, self.ts, self.tt, self.ibot_weight, hyper=self.hyper,
+                              loss_scale=self.scaler.scale if self.scaler is not None else None)
+            else:       # no marked patch on this rank: no patch launch, the term is 0 and the rank adds nothing to the centre
+                self.ibot.zero_(); self.patch_center_sum.zero_()
+            if mn > 1:  # the mean over the micro-batches like the loss; sums and count add up like the CLS centre's
+                self._ibot_acc = self.ibot.clone() if first else self._ibot_acc + self.ibot
+                self._pcenter_acc = self.patch_center_sum.clone() if first else self._pcenter_acc + self.patch_center_sum
+                if last:
+                    self.ibot.copy_(self._ibot_acc / mn); self.patch_center_sum.copy_(self._pcenter_acc)
+            if last:
+                self.reducer.reduce_tensor(self.patch_center_sum)
         if mn > 1:
             if first:
                 self._loss_acc, self._center_acc = self.loss.clone(), self.center_sum.clone()
@@ -1250,11 +1400,13 @@ class DinoEngine(TrainEngine):
             self.reducer.reduce_tensor(self.center_sum)
         sx.join(ev_zero)
         self.head.backward(self.sH, self.wn_s, self.hb_s, self.train_last_layer, sx)
+        if M > 0:       # the marked rows through the same head: its weight gradients accumulate behind the CLS rows'
+            self.head.backward(self.sH, self.wn_s, self.pr_s.hb, self.train_last_layer, sx, rows=M)
         if self.koleo_weight > 0:       # into the global crops' rows of the feature gradient, under the loss scale the DINO term carries
             ops.koleo_bwd(self.hb_s.dfeats, self.koleo_ws, self.koleo_nn, G, B, self.D, self.koleo_weight,
                           loss_scale=self.scaler.scale if self.scaler is not None else None)
         if not last:        # more micro-batches follow: gradients keep accumulating locally
-            self.vit.backward(self.sW, self.g_stu, self.hb_s.dfeats)
+            self.vit.backward(self.sW, self.g_stu, self.hb_s.dfeats, **({} if masks is None else dict(patch=(masks, self.pr_s))))
             return
         # The gradient all-reduce goes out as a few contiguous arena ranges, each as soon as it is final (dist.reduction_plan):
         # the head's matrices when the head backward ends, then coalesced block ranges of >= 25 MB from the side stream (the
@@ -1269,7 +1421,7 @@ class DinoEngine(TrainEngine):
                     if trg == trigger:
                         self.reducer.reduce_range(a.g, lo, hi)
         sx.then(lambda: release("head"))     # behind the head's weight gradients, which were queued on the side stream
-        self.vit.backward(self.sW, self.g_stu, self.hb_s.dfeats, on_block_done=release)
+        self.vit.backward(self.sW, self.g_stu, self.hb_s.dfeats, on_block_done=release, **({} if masks is None else dict(patch=(masks, self.pr_s))))
         release("end")
         self.reducer.finish()
 
@@ -1321,17 +1473,21 @@ class DinoEngine(TrainEngine):
             self.scaler.update(self.gnorm_sq)
         self._refresh_wn()
         ops.center_update(self.center, self.center_sum, self.K, self.cm, 1.0 / (self.G * self.B * self.reducer.world * self._n_micro))
+        if self.ibot_weight > 0:      # the patch centre, where the CLS centre is updated; the count comes with the sums
+            ops.patch_center_update(self.patch_center, self.patch_center_sum, self.K, self.cm)
 
-    def step_micro(self, tile_batches: Sequence[torch.Tensor], **sched) -> torch.Tensor:
+    def step_micro(self, tile_batches: Sequence[torch.Tensor], masks=None, **sched) -> torch.Tensor:
         """One optimizer step over ``len(tile_batches)`` micro-batches of B tiles each (gradient
         accumulation; BASELINE config 5 reaches 512 tiles per GPU this way).  Equals ``step`` on the
         concatenated batch up to summation order."""
         n = len(tile_batches)
+        if masks is not None and len(masks) != n:
+            raise ValueError(f"masks: one MaskPlan per micro-batch ({n}), got {len(masks)}")
         self.set_hyper(n_micro=n, **sched)
         for j, tb in enumerate(tile_batches):
             if input_form(tb, self.B, (self.tile, self.tile)) == "u8":
                 assert tb.shape == (self.B, self.tile, self.tile, 3)
-            self.forward_backward(tb, micro=(j, n))
+            self.forward_backward(tb, micro=(j, n), **({} if masks is None else dict(masks=masks[j])))
         self._n_micro = n
         try:
             self.optimizer_step()
@@ -1339,14 +1495,14 @@ class DinoEngine(TrainEngine):
             self._n_micro = 1
         return self.loss
 
-    def step(self, tiles_u8: torch.Tensor, boxes=None, fill=None, views=None, **sched) -> torch.Tensor:
+    def step(self, tiles_u8: torch.Tensor, boxes=None, fill=None, views=None, masks=None, **sched) -> torch.Tensor:
         """One full training step on [B, tile, tile, 3] uint8 NHWC tiles (or float32 NCHW [B, 3, tile, tile] already normalised,
         on the fixed windows).  Returns the (device, un-synchronised) loss tensor.  ``boxes``: (global, local) int32 device tensors
         from multicrop.MultiCropSampler.sample -- random-resized crops instead of the fixed parity windows."""
         if input_form(tiles_u8, self.B, (self.tile, self.tile), (("fill", fill), ("boxes", boxes), ("views", views))) == "u8":
             assert tiles_u8.shape == (self.B, self.tile, self.tile, 3)
         self.set_hyper(**sched)
-        self.forward_backward(tiles_u8, boxes=boxes, fill=fill, views=views)
+        self.forward_backward(tiles_u8, boxes=boxes, fill=fill, views=views, **({} if masks is None else dict(masks=masks)))
         self.optimizer_step()
         return self.loss
 
@@ -1618,6 +1774,8 @@ class FeatureExtractor:
         self._tok_stats = None                             # f32 [2, T]: LayerNorm statistics of captured tokens
 
     def load_state(self, state: Dict[str, torch.Tensor]):
+        if "mask_token" in state:       # an iBOT student / teacher: the token stands in for masked patches in training only
+            print("FeatureExtractor: the state holds iBOT's mask_token; inference masks nothing: mask_token is dropped", flush=True)
         self.arena.load(state)
         ops.cast_bf16(self.arena.p, self.arena.pb)
 

@@ -77,13 +77,16 @@ def resize_pos_embed(pos: torch.Tensor, new_tokens: int) -> torch.Tensor:
     return torch.cat([cls, grid.permute(0, 2, 3, 1).reshape(1, s1 * s1, -1)], dim=1)
 
 
-def load_encoder_checkpoint(path: str, arch: str, img_size: int, num_classes: int = 0, global_pool: str = "token") -> Dict[str, torch.Tensor]:
+def load_encoder_checkpoint(path: str, arch: str, img_size: int, num_classes: int = 0, global_pool: str = "token",
+                            mask_token: bool = False) -> Dict[str, torch.Tensor]:
     """Read an encoder ``state_dict`` from a timm-style ``*.pth.tar`` / DINO checkpoint with a
     loader that executes nothing from the file, strip 'module.' / 'backbone.' prefixes, resize
     the pos-embed if the grid differs and fill a missing / mismatched classifier head.
     ``global_pool`` "avg": ``fc_norm.*`` is loaded when the file has it; from a token-style file (a DINO or supervised CLS
     checkpoint -- the fine-tuning case) ``norm.*`` is dropped and ``fc_norm`` starts at (1, 0), with one printed notice.  A
-    "token" model given a mean-pooled file (``fc_norm.*`` and no ``norm.*``) raises KeyError: there is no final norm to load."""
+    "token" model given a mean-pooled file (``fc_norm.*`` and no ``norm.*``) raises KeyError: there is no final norm to load.
+    ``mask_token``: keep iBOT's ``mask_token`` when the file has one (a run with the iBOT term); otherwise it is dropped, with one
+    printed notice."""
     ck = torch.load(path, map_location="cpu", weights_only=True)
     for key in ("state_dict", "model", "teacher", "student"):
         if isinstance(ck, dict) and key in ck and isinstance(ck[key], dict):
@@ -111,6 +114,11 @@ def load_encoder_checkpoint(path: str, arch: str, img_size: int, num_classes: in
         if t is None or tuple(t.shape) != tuple(shape):
             t = fresh[name]
         out[name] = t.float()
+    if "mask_token" in sd:
+        if mask_token and tuple(sd["mask_token"].shape) == (1, want["cls_token"][-1]):
+            out["mask_token"] = sd["mask_token"].float()
+        else:
+            print(f"load_encoder_checkpoint: {path} holds iBOT's mask_token; this model has no iBOT term: mask_token is dropped")
     return out
 
 

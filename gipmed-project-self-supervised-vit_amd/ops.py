@@ -696,6 +696,84 @@ def koleo_bwd(dfeats, workspace, nn, G: int, B: int, D: int, weight: float, loss
     L.call("gv_koleo_bwd" + _sfx(dfeats), a, _stream())
 
 
+def _row_table(who: str, rows, M: int):
+    if rows.dtype != torch.int32 or rows.numel() < M or not rows.is_contiguous() or M < 1:
+        raise ValueError(f"{who}: rows must be a contiguous int32 tensor of at least M = {M} >= 1 entries, got {rows.dtype} {tuple(rows.shape)}")
+
+
+def mask_tokens_fwd(x, mask_token, pos, rows, M: int, N: int, D: int):
+    """x[rows[i]] = mask_token + pos[rows[i] mod N] for the first M entries of the int32 row table (iBOT's masked student input);
+    x f32 [n_img * N, D] contiguous, behind the patch-embedding product and cls_rows; see gv_mask_tokens_fwd."""
+    _row_table("mask_tokens_fwd", rows, M)
+    if x.dtype != f32 or not x.is_contiguous() or x.numel() % (N * D) or mask_token.numel() != D or pos.numel() < N * D:
+        raise ValueError(f"mask_tokens_fwd: need contiguous f32 x [n_img * {N}, {D}], mask_token [{D}] and pos [{N}, {D}], got {tuple(x.shape)}, "
+                         f"{tuple(mask_token.shape)}, {tuple(pos.shape)}")
+    a = L.gv_mask_tokens_fwd_args(x.data_ptr(), mask_token.data_ptr(), pos.data_ptr(), rows.data_ptr(), M, N, D, x.numel() // D)
+    L.call("gv_mask_tokens_fwd", a, _stream())
+
+
+def mask_tokens_bwd(g, gpatch, dmask_token, rows, workspace, M: int, N: int, D: int, accumulate: bool):
+    """dmask_token (+)= sum_i g[rows[i]] in a fixed order, and the marked rows of the compact patch gradient set to exact zeros;
+    behind tokens_bwd (dpos keeps the rows' share).  workspace: f32, gv_mask_tokens_workspace_bytes(M, D); see gv_mask_tokens_bwd."""
+    _row_table("mask_tokens_bwd", rows, M)
+    n_rows = g.numel() // D
+    if g.dtype != f32 or not (g.is_contiguous() and gpatch.is_contiguous()) or n_rows % N or gpatch.numel() < n_rows // N * (N - 1) * D:
+        raise ValueError(f"mask_tokens_bwd: need contiguous f32 g [n_img * {N}, {D}] and gpatch [n_img * {N - 1}, {D}], got {tuple(g.shape)}, {tuple(gpatch.shape)}")
+    a = L.gv_mask_tokens_bwd_args(g.data_ptr(), gpatch.data_ptr(), dmask_token.data_ptr(), rows.data_ptr(), workspace.data_ptr(),
+                                  workspace.numel() * workspace.element_size(), M, N, D, n_rows, int(accumulate))
+    L.call("gv_mask_tokens_bwd" + _sfx(gpatch), a, _stream())
+
+
+def rows_gather(x, rows, out, M: int, D: int, n_rows: int, x_stride: Optional[int] = None, scale=None, scale_out=None):
+    """out[i] = x[rows[i]] (f32 [M, D] compact) and, with ``scale`` f32 [n_rows], scale_out[i] = scale[rows[i]]: the front half of
+    the final norm on a row table (layernorm_fwd on ``out`` is the norm of those rows); see gv_rows_gather."""
+    _row_table("rows_gather", rows, M)
+    xs = D if x_stride is None else x_stride
+    if x.dtype != f32 or out.dtype != f32 or out.numel() < M * D or x.numel() < (n_rows - 1) * xs + D or (scale is None) != (scale_out is None):
+        raise ValueError(f"rows_gather: need f32 x of {n_rows} rows (stride {xs}) and f32 out [{M}, {D}], scale and scale_out together; got "
+                         f"{tuple(x.shape)} {x.dtype}, {tuple(out.shape)} {out.dtype}")
+    if scale is not None and (scale.dtype != f32 or scale.numel() < n_rows or scale_out.dtype != f32 or scale_out.numel() < M):
+        raise ValueError(f"rows_gather: scale f32 [{n_rows}] and scale_out f32 [{M}], got {tuple(scale.shape)} and {tuple(scale_out.shape)}")
+    L.call("gv_rows_gather", L.gv_rows_gather_args(x.data_ptr(), xs, rows.data_ptr(), out.data_ptr(), _p(scale), _p(scale_out), M, D, n_rows), _stream())
+
+
+def rows_scatter(g_src, g, rows, M: int, D: int, n_rows: int, g_stride: Optional[int] = None, gb_src=None, gb=None, gb_stride: Optional[int] = None):
+    """g[rows[i]] = g_src[i] (f32) and, when given, gb[rows[i]] = gb_src[i] (the build's 16-bit format, or f32 in the fp32 operand
+    mode): the back half of the final norm's backward on a row table; see gv_rows_scatter."""
+    _row_table("rows_scatter", rows, M)
+    gs, gbs = D if g_stride is None else g_stride, D if gb_stride is None else gb_stride
+    if g_src.dtype != f32 or g.dtype != f32 or g_src.numel() < M * D or g.numel() < (n_rows - 1) * gs + D or (gb is None) != (gb_src is None):
+        raise ValueError(f"rows_scatter: need f32 g_src [{M}, {D}] and f32 g of {n_rows} rows (stride {gs}), gb and gb_src together")
+    if gb is not None and (gb.dtype != gb_src.dtype or gb_src.numel() < M * D or gb.numel() < (n_rows - 1) * gbs + D):
+        raise ValueError(f"rows_scatter: gb_src [{M}, {D}] and gb of {n_rows} rows (stride {gbs}) in one format, got {gb_src.dtype} and {gb.dtype}")
+    a = L.gv_rows_scatter_args(g_src.data_ptr(), g.data_ptr(), gs, _p(gb_src), _p(gb), gbs, rows.data_ptr(), M, D, n_rows)
+    L.call("gv_rows_scatter" + ("" if gb is None else _sfx(gb)), a, _stream())
+
+
+def ibot_loss(student, teacher, center, weight, dstudent, loss, center_sum, workspace, M: int, K: int, student_temp: float, teacher_temp: float,
+              ibot_weight: float, grad_scale: float = 1.0, hyper=None, loss_scale=None):
+    """The iBOT masked-patch term on the first M rows of student / teacher f32 [>= M, K]: loss f32 [1] (unweighted by
+    ``ibot_weight``), dstudent [>= M, K] (16-bit, or f32 in the fp32 operand mode) and center_sum f32 [K + 1] = the raw teacher
+    column sums with M in the last slot; ``weight`` f32 [M] holds 1 / (n_j J) per row.  See gv_ibot_loss."""
+    for t, nm in ((student, "student"), (teacher, "teacher"), (dstudent, "dstudent")):
+        if t.numel() < M * K or not t.is_contiguous():
+            raise ValueError(f"ibot_loss: {nm} must be contiguous and hold [{M}, {K}], got {tuple(t.shape)}")
+    if student.dtype != f32 or teacher.dtype != f32 or weight.dtype != f32 or weight.numel() < M or center.numel() < K or center_sum.numel() < K + 1:
+        raise ValueError(f"ibot_loss: need f32 logits, weight [{M}], center [{K}] and center_sum [{K + 1}], got {student.dtype}, {tuple(weight.shape)}, "
+                         f"{tuple(center.shape)}, {tuple(center_sum.shape)}")
+    a = L.gv_ibot_loss_args(student.data_ptr(), teacher.data_ptr(), center.data_ptr(), weight.data_ptr(), dstudent.data_ptr(), loss.data_ptr(),
+                            center_sum.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(), M, K, student_temp, teacher_temp,
+                            ibot_weight, grad_scale, _p(hyper), _p(loss_scale))
+    L.call("gv_ibot_loss" + _sfx(dstudent), a, _stream())
+
+
+def patch_center_update(center, center_sum, K: int, momentum: float):
+    """center <- m center + (1 - m) center_sum[:K] / center_sum[K]; the count is read on the device, 0 leaves the centre as it is."""
+    if center.numel() < K or center_sum.numel() < K + 1:
+        raise ValueError(f"patch_center_update: center [{K}] and center_sum [{K + 1}], got {tuple(center.shape)} and {tuple(center_sum.shape)}")
+    L.call("gv_patch_center_update", L.gv_patch_center_update_args(center.data_ptr(), center_sum.data_ptr(), K, momentum), _stream())
+
+
 def softmax_lsce(logits, target, loss, dlogits, prob, B: int, C: int, smoothing: float, loss_scale=None):
     a = L.gv_softmax_lsce_args(logits.data_ptr(), target.data_ptr(), loss.data_ptr(), dlogits.data_ptr(), _p(prob), B, C, smoothing,
                                _p(loss_scale))

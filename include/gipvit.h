@@ -1043,6 +1043,100 @@ int gv_koleo_bwd_f32(const gv_koleo_args* a, void* stream);
 /* scratch bytes of gv_koleo_fwd / _bwd; -1 with gv_last_error() set for a shape they would refuse.  Touches no GPU. */
 int64_t gv_koleo_workspace_bytes(int32_t G, int32_t B, int32_t D);
 
+/* ---- iBOT masked-patch term (csrc/ibot.hip; DINOv2's iBOTPatchLoss.forward_masked and the mask token of its student).
+ *
+ * A ROW TABLE is an int32 device vector of M token rows of a [n_rows, D] token buffer, row = image * N + token (N tokens per
+ * image, token 0 the CLS row).  It is device data, so no call can check it: every kernel skips an entry outside [0, n_rows)
+ * -- and, in the two mask-token calls, a CLS row -- instead of following it.  The entries must be unique (each call writes a row
+ * once per entry, in no order between entries).  Every sum over rows is stored per slice and added in slice order by a second
+ * launch: no atomics, bitwise the same run to run.  Every refused call returns GV_E_* before any launch.
+ *
+ * gv_mask_tokens_fwd: x[rows[i], :] = mask_token[:] + pos[rows[i] mod N, :], f32 (one addition: exact to the bit against any
+ * other f32 evaluation).  Runs behind the patch-embedding product and gv_cls_rows; no other row of x is touched.
+ * gv_mask_tokens_bwd (behind gv_tokens_bwd, which has already added the rows into dpos):
+ *     dmask_token[:] (+)= sum_i g[rows[i], :]        64 entries per workgroup in table order, then the workgroups' sums in order
+ *     gpatch[image * (N - 1) + token - 1, :] = 0     for every entry: the patch embedding gets nothing from a masked patch
+ * Limits: M >= 1, N >= 2, n_rows a multiple of N, D a multiple of 4 (up to 1024 in the backward); x, g, mask_token, pos,
+ * dmask_token and workspace 16-byte aligned; workspace of gv_mask_tokens_workspace_bytes(M, D) bytes.                          */
+typedef struct {
+    float*         x;           /* f32 [n_rows, D]                                                          */
+    const float*   mask_token;  /* f32 [D]                                                                  */
+    const float*   pos;         /* f32 [N, D]                                                               */
+    const int32_t* rows;        /* i32 [M]                                                                  */
+    int32_t M, N, D, n_rows;
+} gv_mask_tokens_fwd_args;
+int gv_mask_tokens_fwd(const gv_mask_tokens_fwd_args* a, void* stream);
+typedef struct {
+    const float*   g;           /* f32 [n_rows, D]: the gradient of the token buffer                        */
+    void*          gpatch;      /* [n_rows / N * (N - 1), D] compact patch rows, as gv_tokens_bwd wrote them */
+    float*         dmask_token; /* f32 [D]                                                                  */
+    const int32_t* rows;        /* i32 [M]                                                                  */
+    float*         workspace; int64_t workspace_bytes;
+    int32_t M, N, D, n_rows;
+    int32_t accumulate;         /* != 0: dmask_token += the sum                                             */
+} gv_mask_tokens_bwd_args;
+int gv_mask_tokens_bwd(const gv_mask_tokens_bwd_args* a, void* stream);
+int gv_mask_tokens_bwd_f32(const gv_mask_tokens_bwd_args* a, void* stream);   /* gpatch as f32 */
+/* scratch bytes of gv_mask_tokens_bwd; -1 with gv_last_error() set for a shape it would refuse.  Touches no GPU. */
+int64_t gv_mask_tokens_workspace_bytes(int32_t M, int32_t D);
+
+/* The final norm on a row table is gv_layernorm_fwd / _bwd between a gather and a scatter (the same kernels on the same values:
+ * bit-equal to the norm of the rows taken on their own):
+ *   gv_rows_gather    out[i, :] = x[rows[i], :] (f32, row stride x_stride; zeros for a skipped entry) and, with scale given,
+ *                     scale_out[i] = scale[rows[i]] (the rows' stochastic-depth factors, gv_layernorm_bwd's gb_scale)
+ *   gv_rows_scatter   g[rows[i], :] = g_src[i, :] (f32) and, with gb given, gb[rows[i], :] = gb_src[i, :] (16-bit; f32 for _f32):
+ *                     the residual gradient and the last block's MLP-half dY at the marked rows; a plain store, the rows are unique
+ * Limits: M >= 1, D a positive multiple of 4, strides multiples of 4 and >= D, the f32 buffers 16-byte aligned.               */
+typedef struct {
+    const float*   x; int64_t x_stride;
+    const int32_t* rows;        /* i32 [M]                                                                  */
+    float*         out;         /* f32 [M, D]                                                               */
+    const float*   scale;       /* optional f32 [n_rows]                                                    */
+    float*         scale_out;   /* f32 [M], given exactly when scale is                                     */
+    int32_t M, D, n_rows;
+} gv_rows_gather_args;
+int gv_rows_gather(const gv_rows_gather_args* a, void* stream);
+typedef struct {
+    const float*   g_src;       /* f32 [M, D]                                                               */
+    float*         g; int64_t g_stride;
+    const void*    gb_src;      /* optional [M, D]                                                          */
+    void*          gb; int64_t gb_stride;   /* given exactly when gb_src is                                 */
+    const int32_t* rows;        /* i32 [M]                                                                  */
+    int32_t M, D, n_rows;
+} gv_rows_scatter_args;
+int gv_rows_scatter(const gv_rows_scatter_args* a, void* stream);
+int gv_rows_scatter_f32(const gv_rows_scatter_args* a, void* stream);         /* gb_src / gb as f32 */
+
+/* gv_ibot_loss on the head's logits of the M marked rows, student and teacher f32 [M, K] in table order, with the patch centre
+ * c [K], the rows' weights w [M] (1 / (n_j J) for a row of image j) and tau_s / tau_t as gv_dino_loss takes them (hyper included):
+ *     p_i = softmax((t_i - c) / tau_t);  loss[0] = -sum_i w_i sum_k p_ik log_softmax(s_i / tau_s)_k     (ibot_weight NOT applied)
+ *     dstudent[i, :] = w_i (softmax(s_i / tau_s) - p_i) / tau_s * ibot_weight * grad_scale [* loss_scale[0]]   (16-bit; f32 for _f32)
+ *     center_sum[k] = sum_i t_ik for k < K (raw logits, every row whatever its weight);  center_sum[K] = (float)M
+ * so that one [K + 1] vector carries sums and count through the all-reduce.  A row of weight 0 adds nothing to the loss and gets a
+ * gradient row of exact zeros, whatever its logits hold.  Two passes, each reading every logit once (16-byte loads when K is a
+ * multiple of 4, 4-byte loads otherwise): row maxima and log-sum-exps; then column tiles x row slices, which write the gradient
+ * and store their loss and column-sum partials, added in a fixed order by a last small launch.  grad_scale 0 reads as 1.
+ * Limits: 1 <= M, K <= 2^20, temperatures > 0, ibot_weight finite and >= 0; workspace 16-byte aligned and of
+ * gv_ibot_loss_workspace_bytes(M, K) bytes; student, teacher, center and center_sum 16-byte aligned when K is a multiple of 4. */
+typedef struct {
+    const float* student; const float* teacher; const float* center; const float* weight;
+    void* dstudent; float* loss; float* center_sum;
+    float* workspace; int64_t workspace_bytes;
+    int32_t M, K;
+    float student_temp, teacher_temp, ibot_weight, grad_scale;
+    const float* hyper;      /* optional device vector (see gv_adamw_ema_args): temps                       */
+    const float* loss_scale; /* optional DEVICE scalar that multiplies the gradient (fp16 loss scaling)     */
+} gv_ibot_loss_args;
+int gv_ibot_loss(const gv_ibot_loss_args* a, void* stream);
+int gv_ibot_loss_f32(const gv_ibot_loss_args* a, void* stream);
+/* scratch bytes of gv_ibot_loss; -1 with gv_last_error() set for a shape it would refuse.  Touches no GPU. */
+int64_t gv_ibot_loss_workspace_bytes(int32_t M, int32_t K);
+
+/* center[k] <- m center[k] + (1 - m) center_sum[k] / center_sum[K] for k < K, with the (all-reduced) row count read from the
+ * device vector's last slot: no host synchronisation.  A count that is not > 0 leaves the centre unchanged.                   */
+typedef struct { float* center; const float* center_sum; int32_t K; float momentum; } gv_patch_center_update_args;
+int gv_patch_center_update(const gv_patch_center_update_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,13 @@ def build_parser():
     g.add_argument("--centering", default="center", choices=("center", "sinkhorn_knopp"), help="DINO: how the teacher's logits are centred -- the "
                    "EMA centre of DINO, or DINOv2's Sinkhorn-Knopp iterations over the step's teacher logits of all ranks (gv_sinkhorn_*)")
     g.add_argument("--sinkhorn-iters", type=int, default=3, help="--centering sinkhorn_knopp: iterations (1..8)")
+    g.add_argument("--ibot-weight", type=float, default=0.0, help="DINO: weight of the iBOT masked-patch term (gv_mask_tokens_* / gv_ibot_loss): the "
+                   "student sees a learned mask token in place of the marked patches of its global crops and the marked rows go through the "
+                   "head a second time; 0 = off, DINOv2 uses 1.0")
+    g.add_argument("--ibot-mask-ratio", type=float, nargs=2, default=[0.1, 0.5], metavar=("LO", "HI"), help="--ibot-weight: share of a masked "
+                   "image's patches that is marked, 0 < LO <= HI < 1 (DINOv2 mask_ratio_min_max)")
+    g.add_argument("--ibot-mask-prob", type=float, default=0.5, help="--ibot-weight: share of the global crops that is masked, 0 < P <= 1 "
+                   "(DINOv2 mask_sample_probability)")
     g.add_argument("--koleo-weight", type=float, default=0.0, help="DINO: weight of the KoLeo regulariser on the student's CLS features of "
                    "every global crop (gv_koleo_fwd / gv_koleo_bwd); 0 = off, DINOv2 uses 0.1")
     g.add_argument("--knn-monitor", action="store_true", help="DINO: weighted k-NN classifier on the teacher's frozen features as the training "
@@ -169,6 +176,36 @@ SUPPORTED_SCHEDS = ("cosine", "step")               # gipvit/sched.py
 def dino_loss_options(args) -> dict:
     """The DINOv2 loss options of the command line as DinoEngine's keyword arguments."""
     return dict(centering=args.centering, sinkhorn_iters=args.sinkhorn_iters, koleo_weight=args.koleo_weight)
+
+
+def ibot_options(args) -> dict:
+    """The iBOT flags of the command line as DinoEngine's keyword arguments."""
+    return dict(ibot_weight=args.ibot_weight, ibot_mask_ratio=tuple(args.ibot_mask_ratio), ibot_mask_prob=args.ibot_mask_prob, drop=args.drop or 0.0)
+
+
+def check_ibot(args):
+    """--ibot-weight / --ibot-mask-ratio / --ibot-mask-prob: refused before any GPU work (DinoEngine's constructor says the same)."""
+    lo, hi = args.ibot_mask_ratio
+    given = [f for f, on in (("--ibot-weight", args.ibot_weight != 0), ("--ibot-mask-ratio", [lo, hi] != [0.1, 0.5]),
+                             ("--ibot-mask-prob", args.ibot_mask_prob != 0.5)) if on]
+    if given and not args.dino:
+        raise SystemExit(f"{' / '.join(given)}: the iBOT term belongs to the DINO step, it needs --dino")
+    if not (math.isfinite(args.ibot_weight) and args.ibot_weight >= 0):
+        raise SystemExit(f"--ibot-weight {args.ibot_weight}: a finite weight >= 0")
+    if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi < 1.0):
+        raise SystemExit(f"--ibot-mask-ratio {lo} {hi}: need 0 < LO <= HI < 1")
+    if not (math.isfinite(args.ibot_mask_prob) and 0.0 < args.ibot_mask_prob <= 1.0):
+        raise SystemExit(f"--ibot-mask-prob {args.ibot_mask_prob}: need 0 < P <= 1")
+    if args.ibot_weight > 0:
+        if args.global_crop_size < 64:
+            raise SystemExit(f"--ibot-weight with --global-crop-size {args.global_crop_size}: the mask blocks need a 4 x 4 patch grid, 64 px at least")
+        if args.drop:
+            raise SystemExit("--ibot-weight with --drop: the dropout path has no all-token last block with a row table; not built")
+        if args.amp and args.amp_dtype != "bfloat16":
+            raise SystemExit("--ibot-weight with --amp --amp-dtype float16: the iBOT term is not built for the float16 library; pass --amp-dtype bfloat16")
+        if args.centering == "sinkhorn_knopp":
+            raise SystemExit("--ibot-weight with --centering sinkhorn_knopp: Sinkhorn-Knopp over a patch-row count that varies per rank is not built, "
+                             "and the EMA patch centre in its place would be a silent substitution")
 
 
 def check_supported(args, log=_logger.warning):
@@ -329,6 +366,7 @@ def check_supported(args, log=_logger.warning):
         if resolve_eval_metric(args.eval_metric, bool(args.knn_monitor), bool(args.linear_probe), True) not in names:
             raise SystemExit(f"--eval-metric {args.eval_metric}: the monitors of this run report {names} (a bare name is the k-NN monitor's "
                              "when that is on, else the linear probe's, else the MIL probe's)")
+    check_ibot(args)
     # the DINOv2 loss options belong to the DINO step
     if not args.dino and (args.centering != "center" or args.koleo_weight != 0):
         raise SystemExit("--centering sinkhorn_knopp / --koleo-weight change the DINO step's loss: they need --dino")
@@ -660,8 +698,8 @@ def main(argv=None, transform=None):
                          gsize=args.global_crop_size, lsize=args.local_crop_size, lr=lr, weight_decay=args.weight_decay, betas=betas, eps=eps,
                          momentum_teacher=args.momentum_teacher, teacher_temp=args.teacher_temp, clip_grad=args.clip_grad or 0.0,
                          mean=mean, std=std, device=dev, reducer=reducer, precision=args.precision, clip_mode=args.clip_mode,
-                         **dino_loss_options(args))
-        bb = (M.load_encoder_checkpoint(args.initial_checkpoint, arch, img) if args.initial_checkpoint
+                         **dino_loss_options(args), **ibot_options(args))
+        bb = (M.load_encoder_checkpoint(args.initial_checkpoint, arch, img, mask_token=args.ibot_weight > 0) if args.initial_checkpoint
               else M.init_vit_state(arch, img, 0, seed=args.seed))
         eng.load_state(bb, M.init_dino_head_state(eng.D, args.out_dim, seed=args.seed + 1))
         nc = 0
@@ -688,6 +726,8 @@ def main(argv=None, transform=None):
             if "state_dict_ema" in ck:        # the teacher + centre: without them the run would restart the EMA from the student
                 te = strip(ck["state_dict_ema"])
                 eng.load_teacher_state(sub(te, "backbone."), sub(te, "head."), ck.get("dino_center"))
+                if args.ibot_weight > 0 and ck.get("ibot_center") is not None:
+                    eng.patch_center.copy_(ck["ibot_center"].to(dev, torch.float32).view(-1))
             elif primary:
                 _logger.warning("--resume: %s holds no teacher ('state_dict_ema'); the teacher restarts as a copy of the student", args.resume)
         else:
@@ -769,6 +809,10 @@ def main(argv=None, transform=None):
     if erase_sampler is not None and primary:
         _logger.info("random erasing on the device: reprob %.3g remode %s recount %d (training steps only, after mixup / cutmix)",
                      args.reprob, args.remode, args.recount)
+    mask_sampler = None
+    if args.dino and args.ibot_weight > 0:      # iBOT: which patches of which global crop the student does not see, drawn per rank
+        from gipvit.masking import MaskSampler
+        mask_sampler = MaskSampler(args.global_crop_size // 16, 2 * B, tuple(args.ibot_mask_ratio), args.ibot_mask_prob, seed=args.seed + 101 * rank + 3)
     view_sampler = None
     if args.view_augment:
         from gipvit.multicrop import ViewAugmentSampler
@@ -780,6 +824,8 @@ def main(argv=None, transform=None):
         if args.dino:       # teacher (the EMA model) + centre: a DINO run cannot be resumed (or evaluated) without them
             ex["state_dict_ema"] = eng.arena.state_dict(eng.arena.t)
             ex["dino_center"] = eng.center.detach().cpu()
+            if eng.ibot_weight > 0:
+                ex["ibot_center"] = eng.patch_center.detach().cpu()
         elif ema_decay is not None:
             ex["state_dict_ema"] = eng.state_dict(ema=True)     # timm CheckpointSaver key
         if drop_sampler is not None:
@@ -787,7 +833,7 @@ def main(argv=None, transform=None):
         # ... and the other host-side draw streams (--drop step seeds, random-resized-crop boxes, view augmentation), as JSON
         # strings of numpy's bit-generator state: plain str, loads with weights_only=True
         streams = {"drop": drop_rng, "crops": getattr(sampler, "rng", None), "views": getattr(view_sampler, "rng", None),
-                   "mix": getattr(mix_sampler, "rng", None), "erase": getattr(erase_sampler, "rng", None)}
+                   "mix": getattr(mix_sampler, "rng", None), "erase": getattr(erase_sampler, "rng", None), "ibot": getattr(mask_sampler, "rng", None)}
         ex["host_rng"] = {k: json.dumps(g.bit_generator.state) for k, g in streams.items() if g is not None}
         if eng.scaler is not None:
             ex["amp_scaler"] = eng.scaler.state_dict()          # timm CheckpointSaver(amp_scaler=loss_scaler) key, train.py:585-602
@@ -814,7 +860,8 @@ def main(argv=None, transform=None):
         drop_rng = np.random.default_rng(args.seed + 7919 * rank + 11)
     if args.resume and isinstance(ck.get("host_rng"), dict):     # continue the draw streams where the saved run left them
         for k, g in (("drop", drop_rng), ("crops", getattr(sampler, "rng", None)), ("views", getattr(view_sampler, "rng", None)),
-                     ("mix", getattr(mix_sampler, "rng", None)), ("erase", getattr(erase_sampler, "rng", None))):
+                     ("mix", getattr(mix_sampler, "rng", None)), ("erase", getattr(erase_sampler, "rng", None)),
+                     ("ibot", getattr(mask_sampler, "rng", None))):
             if g is not None and k in ck["host_rng"]:
                 g.bit_generator.state = json.loads(ck["host_rng"][k])
     cur_lr = lr
@@ -848,7 +895,8 @@ def main(argv=None, transform=None):
                            momentum_teacher=S.cosine_between(args.momentum_teacher, 1.0, it, total_updates),
                            teacher_temp=teacher_temp_at(args, epoch))
                 loss_t = eng.step(data, boxes=sampler.sample(dev) if sampler is not None else None, fill=fill if sampler is None else None,
-                                  views=view_sampler.sample(dev) if view_sampler is not None else None, **sch)
+                                  views=view_sampler.sample(dev) if view_sampler is not None else None,
+                                  **({"masks": mask_sampler.sample(dev)} if mask_sampler is not None else {}), **sch)
             else:
                 ekw = {"erase": erase_sampler.sample(dev)} if erase_sampler is not None else {}
                 loss_t = eng.step(data, target, lr=cur_lr, fill=fill, mix=mix_sampler.sample(dev) if mix_sampler is not None else None, **ekw)
@@ -868,7 +916,8 @@ def main(argv=None, transform=None):
                                      epoch, batch_idx, updates_per_epoch, 100.0 * batch_idx / max(last_idx, 1), losses.val, losses.avg,
                                      batch_time.val, B * world / batch_time.val, batch_time.avg, B * world / batch_time.avg, logged_lr(cur_lr),
                                      data_time.val, data_time.avg)
-                                 + ("  KoLeo: {:#.4g}".format(float(eng.koleo)) if args.dino and args.koleo_weight > 0 else ""))
+                                 + ("  KoLeo: {:#.4g}".format(float(eng.koleo)) if args.dino and args.koleo_weight > 0 else "")
+                                 + ("  iBOT: {:#.4g}".format(float(eng.ibot)) if args.dino and args.ibot_weight > 0 else ""))
                 if saver is not None and args.recovery_interval and (batch_idx + 1) % args.recovery_interval == 0:
                     saver.save_recovery(epoch, batch_idx, eng.arena.state_dict(), extra=extra_state())
             end = time.time()
