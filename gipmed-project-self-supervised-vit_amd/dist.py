@@ -29,13 +29,25 @@ def comm_setup(world: int, backend: str = "nccl") -> dict:
     info = {"comm_cus": 0, "cu_budget": int(os.environ.get("GIPVIT_CU_BUDGET", "256"))}
     if world <= 1 or backend != "nccl":
         return info
-    c = int(os.environ.get("GIPVIT_COMM_CUS", "0"))
+    raw = os.environ.get("GIPVIT_COMM_CUS", "0")
+    try:
+        c = int(raw)
+    except ValueError:
+        c = -1
+    if not 0 <= c <= 192:
+        # (the library falls back to the whole chip, 256, below a budget of 64 CUs -- the log would report a budget nobody got)
+        raise ValueError(f"GIPVIT_COMM_CUS={raw!r}: an integer from 0 to 192 (the kernel library needs a budget of at least 64 of the 256 CUs)")
     if c > 0:
         if "gipvit._lib" in sys.modules and "GIPVIT_CU_BUDGET" not in os.environ:
             raise RuntimeError("comm_setup() must run before the kernel library is loaded (the CU budget is read once at load)")
         os.environ.setdefault("GIPVIT_CU_BUDGET", str(256 - c))
         os.environ.setdefault("NCCL_MAX_NCHANNELS", str(c))
-        os.environ.setdefault("NCCL_MIN_NCHANNELS", str(min(c, 4)))
+        lo = min(c, 4)
+        try:                # a minimum above the maximum in force (ours or the caller's) is a contradiction RCCL resolves its own way
+            lo = min(lo, max(int(os.environ["NCCL_MAX_NCHANNELS"]), 1))
+        except ValueError:
+            pass
+        os.environ.setdefault("NCCL_MIN_NCHANNELS", str(lo))
     info.update(comm_cus=c, cu_budget=int(os.environ.get("GIPVIT_CU_BUDGET", "256")), nccl_max_nchannels=os.environ.get("NCCL_MAX_NCHANNELS"))
     return info
 
@@ -95,12 +107,17 @@ def reduction_plan(head_span, block_spans, n_total: int, bucket_bytes: int = 25 
     The ranges tile [0, n_total) exactly once, in release order."""
     plan, lo = [], 0
     if head_span is not None:
+        # the head range is issued from 0: a tensor laid out ahead of the head would go out with it, before it is final
+        assert head_span[0] == 0, "the head's matrices open the arena (backward-completion order)"
         plan.append(("head", 0, head_span[1]))
         lo = head_span[1]
     order = sorted(block_spans, reverse=True)
+    prev = lo
+    for i in order:         # every span, the last block's included, lies behind the one released before it
+        assert block_spans[i][0] >= prev, "block spans must follow the arena's backward-completion order"
+        prev = block_spans[i][1]
     for i in order:
         b_lo, b_hi = block_spans[i]
-        assert b_lo >= lo, "block spans must follow the arena's backward-completion order"
         if i == order[-1]:
             break
         if (b_hi - lo) * elt >= bucket_bytes or (len(order) > 1 and i == order[-2]):

@@ -331,6 +331,17 @@ def test_comm_setup_environment_contract(monkeypatch):
     monkeypatch.delenv("NCCL_MIN_NCHANNELS")
     info = comm_setup(2, "nccl")
     assert info["nccl_max_nchannels"] == "12" and os.environ["NCCL_MIN_NCHANNELS"] == "2"
+    # the minimum never exceeds the maximum in force: a caller's NCCL_MAX_NCHANNELS below min(C, 4) caps it
+    monkeypatch.setenv("GIPVIT_COMM_CUS", "16")
+    monkeypatch.setenv("NCCL_MAX_NCHANNELS", "2")
+    monkeypatch.delenv("NCCL_MIN_NCHANNELS")
+    info = comm_setup(2, "nccl")
+    assert info["nccl_max_nchannels"] == "2" and os.environ["NCCL_MIN_NCHANNELS"] == "2"
+    monkeypatch.setenv("NCCL_MIN_NCHANNELS", "3")              # ... but a value of the caller's own stays
+    assert comm_setup(2, "nccl")["comm_cus"] == 16 and os.environ["NCCL_MIN_NCHANNELS"] == "3"
+    monkeypatch.setenv("GIPVIT_COMM_CUS", "200")               # the library would size for 256 below a budget of 64
+    with pytest.raises(ValueError, match="GIPVIT_COMM_CUS"):
+        comm_setup(2, "nccl")
 
 
 def test_train_cli_keeps_reference_surface(tmp_path):

@@ -611,7 +611,7 @@ def main(argv=None, transform=None):
 
     from gipvit import models as M, sched as S, data as D, transformations as T
     from gipvit.engine import ARCHS, DinoEngine, SupervisedEngine, FeatureExtractor, Weights
-    from gipvit.checkpoint import CheckpointSaver, load_checkpoint_file
+    from gipvit.checkpoint import CheckpointSaver, load_checkpoint_file, pack_host_rng, restore_host_rng
     from gipvit.validate import validate
     arch = M.resolve_arch(args.model)
     B = args.batch_size
@@ -819,8 +819,21 @@ def main(argv=None, transform=None):
         view_sampler = ViewAugmentSampler(B, 2, args.local_crops_number, jitter_p=args.color_jitter_p, gray_p=args.gray_p, blur_p=tuple(args.blur_p),
                                           solar_p=(0.0, args.solarize_p, 0.0), seed=args.seed + 53 * rank + 5)
 
-    def extra_state():
-        ex = {}
+    def host_streams():
+        return {"drop": drop_rng, "crops": getattr(sampler, "rng", None), "views": getattr(view_sampler, "rng", None),
+                "mix": getattr(mix_sampler, "rng", None), "erase": getattr(erase_sampler, "rng", None), "ibot": getattr(mask_sampler, "rng", None)}
+
+    def gather_ranks(obj):
+        if world == 1:
+            return [obj]
+        out = [None] * world
+        torch.distributed.all_gather_object(out, obj)
+        return out
+
+    def extra_state(rng_state):
+        """``rng_state``: pack_host_rng's entries -- every rank's host-side draw streams (--drop step seeds, random-resized-crop
+        boxes, view augmentation, mixup, erasing, iBOT masks, --drop-path), gathered by ALL ranks at the save point."""
+        ex = dict(rng_state)
         if args.dino:       # teacher (the EMA model) + centre: a DINO run cannot be resumed (or evaluated) without them
             ex["state_dict_ema"] = eng.arena.state_dict(eng.arena.t)
             ex["dino_center"] = eng.center.detach().cpu()
@@ -828,13 +841,6 @@ def main(argv=None, transform=None):
                 ex["ibot_center"] = eng.patch_center.detach().cpu()
         elif ema_decay is not None:
             ex["state_dict_ema"] = eng.state_dict(ema=True)     # timm CheckpointSaver key
-        if drop_sampler is not None:
-            ex["drop_path_rng"] = drop_sampler.state_dict()     # a resumed run continues the mask stream
-        # ... and the other host-side draw streams (--drop step seeds, random-resized-crop boxes, view augmentation), as JSON
-        # strings of numpy's bit-generator state: plain str, loads with weights_only=True
-        streams = {"drop": drop_rng, "crops": getattr(sampler, "rng", None), "views": getattr(view_sampler, "rng", None),
-                   "mix": getattr(mix_sampler, "rng", None), "erase": getattr(erase_sampler, "rng", None), "ibot": getattr(mask_sampler, "rng", None)}
-        ex["host_rng"] = {k: json.dumps(g.bit_generator.state) for k, g in streams.items() if g is not None}
         if eng.scaler is not None:
             ex["amp_scaler"] = eng.scaler.state_dict()          # timm CheckpointSaver(amp_scaler=loss_scaler) key, train.py:585-602
         return ex
@@ -851,19 +857,16 @@ def main(argv=None, transform=None):
     if args.drop_path:
         from gipvit.droppath import DropPathSampler
         drop_sampler = DropPathSampler(ARCHS[arch]["depth"], (eng.V * B) if args.dino else B, args.drop_path, args.seed + 17 * rank, dev)
-        if args.resume and isinstance(ck.get("drop_path_rng"), dict):
-            drop_sampler.load_state_dict(ck["drop_path_rng"])
     # --drop (train.py:283-284): nn.Dropout at the four sites of the encoder, a fresh 32-bit seed per step (counter-based masks)
     drop_rng = None
     if args.drop:
         import numpy as np
         drop_rng = np.random.default_rng(args.seed + 7919 * rank + 11)
-    if args.resume and isinstance(ck.get("host_rng"), dict):     # continue the draw streams where the saved run left them
-        for k, g in (("drop", drop_rng), ("crops", getattr(sampler, "rng", None)), ("views", getattr(view_sampler, "rng", None)),
-                     ("mix", getattr(mix_sampler, "rng", None)), ("erase", getattr(erase_sampler, "rng", None)),
-                     ("ibot", getattr(mask_sampler, "rng", None))):
-            if g is not None and k in ck["host_rng"]:
-                g.bit_generator.state = json.loads(ck["host_rng"][k])
+    if args.resume:     # continue every rank's draw streams where the saved run left them (or, across a change of world size, restart them apart)
+        restore_host_rng(ck, host_streams(), drop_sampler, rank, world, start_epoch, warn=_logger.warning,
+                         seeds={"drop": args.seed + 7919 * rank + 11, "crops": args.seed + rank, "views": args.seed + 53 * rank + 5,
+                                "mix": args.seed + 101 * rank + 23, "erase": args.seed + 211 * rank + 37, "ibot": args.seed + 101 * rank + 3,
+                                "drop_path": args.seed + 17 * rank})
     cur_lr = lr
     # the reference logs the MEAN rate over the optimizer's parameter groups (train.py:1088-1089, 959-965): with --layer-decay
     # that is cur_lr x the mean group scale, without it cur_lr itself
@@ -918,8 +921,10 @@ def main(argv=None, transform=None):
                                      data_time.val, data_time.avg)
                                  + ("  KoLeo: {:#.4g}".format(float(eng.koleo)) if args.dino and args.koleo_weight > 0 else "")
                                  + ("  iBOT: {:#.4g}".format(float(eng.ibot)) if args.dino and args.ibot_weight > 0 else ""))
-                if saver is not None and args.recovery_interval and (batch_idx + 1) % args.recovery_interval == 0:
-                    saver.save_recovery(epoch, batch_idx, eng.arena.state_dict(), extra=extra_state())
+                if args.recovery_interval and (batch_idx + 1) % args.recovery_interval == 0:
+                    rng_state = pack_host_rng(host_streams(), drop_sampler, gather_ranks)       # a collective: every rank, only the write is the primary's
+                    if saver is not None:
+                        saver.save_recovery(epoch, batch_idx, eng.arena.state_dict(), extra=extra_state(rng_state))
             end = time.time()
         # ---- end of epoch: train metrics, slide-level validation (train.py:932-955), summary.csv, checkpoint (958-973)
         train_metrics = OrderedDict(loss=losses.avg)
@@ -953,6 +958,7 @@ def main(argv=None, transform=None):
             if primary:
                 _logger.info(f"*** features of {int(eval_metrics.get('slides', 0))} slides written to {args.features_dir}")
             break
+        rng_state = pack_host_rng(host_streams(), drop_sampler, gather_ranks)       # every rank: the checkpoint holds each rank's streams
         if primary:
             # the monitors' columns stay in one order, empty for a monitor that did not run this epoch
             row = summary_row(epoch, train_metrics, eval_metrics, knn_names + probe_names + mil_names, logged_lr(cur_lr))
@@ -975,7 +981,7 @@ def main(argv=None, transform=None):
                 raise SystemExit(f"--eval-metric {eval_metric}: {who} {list(eval_metrics)}")
             else:
                 save_metric, name = train_metrics["loss"], "train loss"
-            best, best_ep = saver.save_checkpoint(epoch, eng.arena.state_dict(), optim, metric=save_metric, extra=extra_state())
+            best, best_ep = saver.save_checkpoint(epoch, eng.arena.state_dict(), optim, metric=save_metric, extra=extra_state(rng_state))
             _logger.info(f"*** epoch {epoch}: " + "  ".join(f"{k} {v:.4f}" for k, v in list(train_metrics.items()) + [("eval_" + k, v) for k, v in eval_metrics.items()])
                          + (f"  (best {name} {best:.4f} @ {best_ep})" if best is not None else f"  (no {name} yet)"))
     if world > 1:
