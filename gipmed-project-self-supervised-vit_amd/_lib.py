@@ -59,6 +59,9 @@ gv_view_params = _struct("gv_view_params", [
 gv_crop_augment_args = _struct("gv_crop_augment_args", [
     ("tiles", vp), ("out", vp), ("boxes", vp), ("params", vp), ("stats", vp), ("n_crops", i32), ("n_tiles", i32), ("tile_h", i32), ("tile_w", i32),
     ("out_size", i32)])
+# one crop's folded H&E stain draw (gipvit.stain packs them) and gv_crop_augment with the table of them
+gv_stain_params = _struct("gv_stain_params", [("on", i32), ("A", f32 * 9), ("b", f32 * 3)])
+gv_crop_augment_stain_args = _struct("gv_crop_augment_stain_args", [("v", gv_crop_augment_args), ("stain", vp)])
 gv_crop_resize_args = _struct("gv_crop_resize_args", [
     ("tiles", vp), ("out", vp), ("boxes", vp), ("n_crops", i32), ("n_tiles", i32), ("tile_h", i32), ("tile_w", i32), ("out_size", i32)])
 gv_layernorm_fwd_args = _struct("gv_layernorm_fwd_args", [
@@ -198,7 +201,7 @@ gv_patch_center_update_args = _struct("gv_patch_center_update_args", [("center",
 
 # entry point -> argument struct (every `int gv_*(const args*, void* stream)` of the header)
 ENTRY_POINTS = {
-    "gv_patchify": gv_patchify_args, "gv_patchify_nchw": gv_patchify_nchw_args, "gv_crop_resize": gv_crop_resize_args, "gv_crop_augment": gv_crop_augment_args, "gv_augment": gv_augment_args, "gv_layernorm_fwd": gv_layernorm_fwd_args, "gv_layernorm_bwd": gv_layernorm_bwd_args,
+    "gv_patchify": gv_patchify_args, "gv_patchify_nchw": gv_patchify_nchw_args, "gv_crop_resize": gv_crop_resize_args, "gv_crop_augment": gv_crop_augment_args, "gv_crop_augment_stain": gv_crop_augment_stain_args, "gv_augment": gv_augment_args, "gv_layernorm_fwd": gv_layernorm_fwd_args, "gv_layernorm_bwd": gv_layernorm_bwd_args,
     "gv_colsum_finalize": gv_colsum_finalize_args, "gv_ln_finalize": gv_ln_finalize_args, "gv_colsum": gv_colsum_args, "gv_linear": gv_linear_args,
     "gv_linear_ln_fwd": gv_linear_ln_fwd_args, "gv_mlp_ln_fwd": gv_mlp_ln_fwd_args, "gv_linear_ln_bwd": gv_linear_ln_bwd_args, "gv_expand_rows": gv_expand_rows_args, "gv_linear_dw_group": gv_linear_dw_group_args,
     "gv_attention_fwd": gv_attention_fwd_args, "gv_attention_fwd_stream": gv_attention_fwd_args, "gv_attention_fwd_varlen": gv_attention_fwd_varlen_args, "gv_attention_bwd": gv_attention_bwd_args, "gv_attention_bwd_varlen": gv_attention_bwd_varlen_args,

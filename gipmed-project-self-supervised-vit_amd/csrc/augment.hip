@@ -14,6 +14,7 @@
 // blends with the MEAN grey level of the image as it is when the operation runs (after the operations drawn before it): a
 // first kernel takes that mean per tile (integer sum of PIL's "L" values, exact).
 #include "gv_common.h"
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -170,6 +171,7 @@ __global__ __launch_bounds__(256) void augment_kernel(gv_augment_args a) {
 // ---------------------------------------------------------------------------------------------------------------------
 // gv_crop_augment: DINO views.  view[y, x] = solarise( blur3( gray( jitter( resized_crop[y, x] ) ) ) ), the resized crop taken
 // straight from the tile (gv_crop_resize's float32 bilinear arithmetic, byte for byte) -- it is never stored.
+// gv_crop_augment_stain: the same with jitter( stain( resized_crop[y, x] ) ), the crop's H&E stain jitter.
 // ---------------------------------------------------------------------------------------------------------------------
 struct Box { const uint8_t* src; int y0, x0, h, w, flip, W, out; float sy, sx; };
 
@@ -213,8 +215,50 @@ __device__ __forceinline__ Px jitter_gray(Px p, const gv_view_params& q, int mea
     return p;
 }
 
-// per-crop sum of "L" over the view as it is just before the contrast operation
-__global__ __launch_bounds__(256) void view_stats_kernel(gv_crop_augment_args a) {
+// gv_crop_augment_stain: the H&E stain jitter of a crop's pixel, directly behind resample() in both kernels (formula:
+// include/gipvit.h).  od comes from `odt`, the block's 256-entry table of -ln((v + 1) / 256) (fp64, rounded once); od' is
+// summed left to right without contraction, exp is the accurate library function: a result is off the fp64 one by less than
+// 1e-4 of a grey level, so the rounded byte differs only within that distance of a tie.
+__device__ __forceinline__ Px stain_px(const Px p, const gv_stain_params& s, const float* odt) {
+    const float od[3] = {odt[p.r], odt[p.g], odt[p.b]};
+    int c3[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float t = od[0] * s.A[c] + od[1] * s.A[3 + c] + od[2] * s.A[6 + c] + s.b[c];
+        c3[c] = (int)fminf(fmaxf(rintf(256.0f * expf(-t) - 1.0f), 0.f), 255.f);
+    }
+    return Px{c3[0], c3[1], c3[2]};
+}
+
+// the kernels below exist once without the stain transform (gv_crop_augment: argument record, LDS and code as before it
+// existed) and once with it
+template <bool STAIN> using ViewArgs = std::conditional_t<STAIN, gv_crop_augment_stain_args, gv_crop_augment_args>;
+__device__ __forceinline__ const gv_crop_augment_args& view_args(const gv_crop_augment_args& a) { return a; }
+__device__ __forceinline__ const gv_crop_augment_args& view_args(const gv_crop_augment_stain_args& a) { return a.v; }
+
+// crop n's record (on = 0 without the transform); the 256 threads of a jittered crop's block fill its od table, one entry each
+template <bool STAIN>
+__device__ __forceinline__ gv_stain_params load_stain(const ViewArgs<STAIN>& va, int n, float* odt) {
+    gv_stain_params st;
+    st.on = 0;
+    if constexpr (STAIN) {
+        st = va.stain[n];
+        if (st.on) odt[threadIdx.x] = (float)(-log((double)(threadIdx.x + 1) * (1.0 / 256.0)));
+        __syncthreads();
+    }
+    return st;
+}
+
+template <bool STAIN>
+__device__ __forceinline__ Px stained(const Px p, const gv_stain_params& st, const float* odt) {
+    if constexpr (STAIN) { if (st.on) return stain_px(p, st, odt); }
+    return p;
+}
+
+// per-crop sum of "L" over the (stained) view as it is just before the contrast operation
+template <bool STAIN>
+__global__ __launch_bounds__(256) void view_stats_kernel(ViewArgs<STAIN> va) {
+    const gv_crop_augment_args& a = view_args(va);
     const int n = blockIdx.y;
     const gv_view_params q = a.params[n];
     int kc = -1;
@@ -223,9 +267,11 @@ __global__ __launch_bounds__(256) void view_stats_kernel(gv_crop_augment_args a)
     const Box b = load_box(a, n);
     const int npx = a.out_size * a.out_size;
     unsigned long long s = 0;
+    __shared__ float odt[STAIN ? 256 : 1];
+    const gv_stain_params st = load_stain<STAIN>(va, n, odt);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < npx; i += gridDim.x * 256) {
         const int y = i / a.out_size, x = i - y * a.out_size;
-        s += (unsigned long long)lum(colour(resample(b, y, x), q, 0, kc, 0));
+        s += (unsigned long long)lum(colour(stained<STAIN>(resample(b, y, x), st, odt), q, 0, kc, 0));
     }
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     __shared__ unsigned long long red[4];
@@ -239,10 +285,14 @@ __global__ __launch_bounds__(256) void view_stats_kernel(gv_crop_augment_args a)
 // 4 adjacent pixels of a row -- the 3x3 taps summed in the oracle's raster order, solarise -- and stores 12 bytes as three
 // dwords.  (Evaluating the chain per tap cost 9 evaluations per blurred pixel: +2.5 ms per B = 64 step.)
 constexpr int VT = 32;
-__global__ __launch_bounds__(256) void crop_augment_kernel(gv_crop_augment_args a) {
+template <bool STAIN>
+__global__ __launch_bounds__(256) void crop_augment_kernel(ViewArgs<STAIN> va) {
+    const gv_crop_augment_args& a = view_args(va);
     __shared__ uint32_t win[(VT + 2) * (VT + 2)];
+    __shared__ float odt[STAIN ? 256 : 1];
     const int out = a.out_size;
     const int n = blockIdx.z, ty0 = blockIdx.y * VT, tx0 = blockIdx.x * VT;
+    const gv_stain_params st = load_stain<STAIN>(va, n, odt);
     const gv_view_params q = a.params[n];
     const Box b = load_box(a, n);
     const int mean = (int)((double)a.stats[n] / (double)(out * out) + 0.5);
@@ -254,7 +304,7 @@ __global__ __launch_bounds__(256) void crop_augment_kernel(gv_crop_augment_args 
         yy = yy < 0 ? -yy : (yy >= out ? 2 * out - 2 - yy : yy);                   // reflect padding (positions past a ragged region's
         xx = xx < 0 ? -xx : (xx >= out ? 2 * out - 2 - xx : xx);                   //  edge stay inside the crop: never stored)
         yy = yy < 0 ? 0 : yy; xx = xx < 0 ? 0 : xx;
-        const Px c = jitter_gray(resample(b, yy, xx), q, mean);
+        const Px c = jitter_gray(stained<STAIN>(resample(b, yy, xx), st, odt), q, mean);
         win[i] = (uint32_t)c.r | ((uint32_t)c.g << 8) | ((uint32_t)c.b << 16);
     }
     __syncthreads();
@@ -295,8 +345,10 @@ __global__ __launch_bounds__(256) void crop_augment_kernel(gv_crop_augment_args 
 
 }  // namespace
 
-extern "C" int gv_crop_augment(const gv_crop_augment_args* a, void* stream) {
-    GV_REQUIRE(a && a->tiles && a->out && a->boxes && a->params && a->stats, GV_E_NULL, "gv_crop_augment: null pointer");
+// argument checks and the three launches (zero, stats, main) of gv_crop_augment (va = a) and gv_crop_augment_stain (a = &va->v)
+template <bool STAIN>
+static int crop_augment_launch(const ViewArgs<STAIN>* va, const gv_crop_augment_args* a, void* stream) {
+    GV_REQUIRE(a->tiles && a->out && a->boxes && a->params && a->stats, GV_E_NULL, "gv_crop_augment: null pointer");
     GV_REQUIRE(a->n_crops > 0 && a->n_tiles > 0 && a->tile_h > 0 && a->tile_w > 0, GV_E_SHAPE, "gv_crop_augment: bad shape");
     GV_REQUIRE(a->out_size > 1 && a->out_size % 4 == 0, GV_E_SHAPE, "gv_crop_augment: out_size=%d must be a multiple of 4 (> 1)", a->out_size);
     GV_REQUIRE(a->n_crops <= 65535, GV_E_SHAPE, "gv_crop_augment: at most 65535 crops per call (got %d)", a->n_crops);
@@ -304,12 +356,23 @@ extern "C" int gv_crop_augment(const gv_crop_augment_args* a, void* stream) {
                "gv_crop_augment: out / boxes / params / stats misaligned");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(augment_zero_kernel, dim3((a->n_crops + 255) / 256), dim3(256), 0, s, (unsigned long long*)a->stats, a->n_crops);
-    hipLaunchKernelGGL(view_stats_kernel, dim3(8, a->n_crops), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL(view_stats_kernel<STAIN>, dim3(8, a->n_crops), dim3(256), 0, s, *va);
     GV_LAUNCH_CHECK("gv_crop_augment(stats)");
     const int nt = (a->out_size + VT - 1) / VT;
-    hipLaunchKernelGGL(crop_augment_kernel, dim3(nt, nt, a->n_crops), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL(crop_augment_kernel<STAIN>, dim3(nt, nt, a->n_crops), dim3(256), 0, s, *va);
     GV_LAUNCH_CHECK("gv_crop_augment");
     return GV_OK;
+}
+
+extern "C" int gv_crop_augment(const gv_crop_augment_args* a, void* stream) {
+    GV_REQUIRE(a, GV_E_NULL, "gv_crop_augment: null pointer");
+    return crop_augment_launch<false>(a, a, stream);
+}
+
+extern "C" int gv_crop_augment_stain(const gv_crop_augment_stain_args* a, void* stream) {
+    GV_REQUIRE(a && a->stain, GV_E_NULL, "gv_crop_augment_stain: null pointer");
+    GV_REQUIRE(gv_aligned(a->stain, 4), GV_E_ALIGN, "gv_crop_augment_stain: stain misaligned");
+    return crop_augment_launch<true>(a, &a->v, stream);
 }
 
 extern "C" int gv_augment(const gv_augment_args* a, void* stream) {

@@ -1284,15 +1284,17 @@ class DinoEngine(TrainEngine):
         vals[L.HYP_STUDENT_TEMP] = self.ts
         ops.store_f32(self.hyper, vals)
 
-    def forward_backward(self, tiles_u8: torch.Tensor, micro: Tuple[int, int] = (0, 1), boxes=None, fill=None, views=None, masks=None):
+    def forward_backward(self, tiles_u8: torch.Tensor, micro: Tuple[int, int] = (0, 1), boxes=None, fill=None, views=None, masks=None, stains=None):
         """teacher fwd (global crops) -> student fwd (all crops) -> loss -> backward.
         Leaves gradients in arena.g, loss in self.loss, center_sum.  ``micro = (j, n)``: this is
         micro-batch j of n (gradient accumulation): gradients, loss and centre sums add up over
         the n calls and the data-parallel reduction is issued from the last one only.
         ``views``: (global, local) packed per-crop records of multicrop.ViewAugmentSampler.sample -- with ``boxes``, every crop
         gets its own colour jitter / grayscale / blur / solarisation in the pass that cuts it (gv_crop_augment).
+        ``stains``: (global, local) packed per-crop records of stain.StainJitterSampler.sample -- with ``views``, every crop's
+        H&E stain jitter is applied in that same pass, ahead of the view chain (gv_crop_augment_stain).
         ``tiles_u8``: uint8 [B, tile, tile, 3] or float32 NCHW [B, 3, tile, tile] already normalised (engine.input_form): float
-        input runs the fixed crop windows only (no ``boxes`` / ``views`` / ``fill``).
+        input runs the fixed crop windows only (no ``boxes`` / ``views`` / ``stains`` / ``fill``).
         ``masks``: this micro-batch's gipvit.masking.MaskPlan over the G * B global crops (crop-major, like the feature rows) --
         given exactly when ``ibot_weight`` > 0."""
         B, G, V = self.B, self.G, self.V
@@ -1306,7 +1308,7 @@ class DinoEngine(TrainEngine):
         M = 0 if masks is None else masks.M
         if masks is not None:
             masks_fit(masks, self.g_stu.segs[0], self.pr_s)
-        input_form(tiles_u8, B, (self.tile, self.tile), (("fill", fill), ("boxes", boxes), ("views", views)))
+        input_form(tiles_u8, B, (self.tile, self.tile), (("fill", fill), ("boxes", boxes), ("views", views), ("stains", stains)))
         a = self.arena
         mj, mn = micro
         first, last = mj == 0, mj == mn - 1
@@ -1317,6 +1319,8 @@ class DinoEngine(TrainEngine):
             raise ValueError("fill boxes are tile coordinates: they cannot be combined with re-cut random crops (boxes)")
         if views is not None and boxes is None:
             raise ValueError("views (per-crop augmentation draws) need boxes: the views are produced by the pass that cuts the crops")
+        if stains is not None and views is None:
+            raise ValueError("stains (per-crop stain jitter draws) need views: the jitter runs inside the view-augmentation pass")
         if boxes is not None:
             # random-resized crops (multicrop.MultiCropSampler): cut on the device, then every crop is its own
             # "tile" with the single window (0, 0); rows stay crop-major like the fixed windows
@@ -1329,15 +1333,19 @@ class DinoEngine(TrainEngine):
                 self._vstats = torch.zeros(max(self.G, self.V - self.G) * B, dtype=torch.int64, device=self.dev)
             if views is None:
                 ops.crop_resize(tiles_u8, bg, self.gsize, out=self._gcrops)
-            else:
+            elif stains is None:
                 ops.crop_augment(tiles_u8, bg, views[0], self._vstats, self.gsize, out=self._gcrops)
+            else:
+                ops.crop_augment_stain(tiles_u8, bg, views[0], stains[0], self._vstats, self.gsize, out=self._gcrops)
             t_src, t_win = self._gcrops, [[(0, 0)]]
             s_src, s_win = [self._gcrops], [[(0, 0)]]
             if self.V > self.G:
                 if views is None:
                     ops.crop_resize(tiles_u8, bl, self.lsize, out=self._lcrops)
-                else:
+                elif stains is None:
                     ops.crop_augment(tiles_u8, bl, views[1], self._vstats, self.lsize, out=self._lcrops)
+                else:
+                    ops.crop_augment_stain(tiles_u8, bl, views[1], stains[1], self._vstats, self.lsize, out=self._lcrops)
                 s_src.append(self._lcrops); s_win.append([(0, 0)])
         sx = SideStream(self.vit.side if tiles_u8.is_cuda else None, self._events)
 
@@ -1495,14 +1503,16 @@ class DinoEngine(TrainEngine):
             self._n_micro = 1
         return self.loss
 
-    def step(self, tiles_u8: torch.Tensor, boxes=None, fill=None, views=None, masks=None, **sched) -> torch.Tensor:
+    def step(self, tiles_u8: torch.Tensor, boxes=None, fill=None, views=None, masks=None, stains=None, **sched) -> torch.Tensor:
         """One full training step on [B, tile, tile, 3] uint8 NHWC tiles (or float32 NCHW [B, 3, tile, tile] already normalised,
         on the fixed windows).  Returns the (device, un-synchronised) loss tensor.  ``boxes``: (global, local) int32 device tensors
-        from multicrop.MultiCropSampler.sample -- random-resized crops instead of the fixed parity windows."""
-        if input_form(tiles_u8, self.B, (self.tile, self.tile), (("fill", fill), ("boxes", boxes), ("views", views))) == "u8":
+        from multicrop.MultiCropSampler.sample -- random-resized crops instead of the fixed parity windows; ``views`` / ``stains``:
+        the per-crop augmentation records of forward_backward."""
+        if input_form(tiles_u8, self.B, (self.tile, self.tile), (("fill", fill), ("boxes", boxes), ("views", views), ("stains", stains))) == "u8":
             assert tiles_u8.shape == (self.B, self.tile, self.tile, 3)
         self.set_hyper(**sched)
-        self.forward_backward(tiles_u8, boxes=boxes, fill=fill, views=views, **({} if masks is None else dict(masks=masks)))
+        self.forward_backward(tiles_u8, boxes=boxes, fill=fill, views=views, **({} if masks is None else dict(masks=masks)),
+                              **({} if stains is None else dict(stains=stains)))
         self.optimizer_step()
         return self.loss
 

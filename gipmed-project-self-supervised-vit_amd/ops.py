@@ -186,6 +186,29 @@ def crop_augment(tiles_u8: torch.Tensor, boxes: torch.Tensor, params: torch.Tens
     return out
 
 
+_STAIN_PARAMS_BYTES = __import__("ctypes").sizeof(L.gv_stain_params)    # one packed gv_stain_params record
+
+
+def crop_augment_stain(tiles_u8: torch.Tensor, boxes: torch.Tensor, params: torch.Tensor, stains: torch.Tensor, stats: torch.Tensor,
+                       out_size: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``crop_augment`` with each crop's H&E stain jitter applied to the resized crop before the view chain, in the same pass.
+    ``stains``: uint8 device tensor holding n packed gv_stain_params records (stain.StainJitterSampler.pack); see
+    gv_crop_augment_stain."""
+    _chk(tiles_u8, torch.uint8, "tiles")
+    assert tiles_u8.dim() == 4 and tiles_u8.shape[-1] == 3 and tiles_u8.is_contiguous()
+    assert boxes.dtype == torch.int32 and boxes.dim() == 2 and boxes.shape[1] == 6 and boxes.is_contiguous() and boxes.device == tiles_u8.device
+    n = boxes.shape[0]
+    assert params.dtype == torch.uint8 and params.numel() == n * _VIEW_PARAMS_BYTES and params.device == tiles_u8.device
+    assert stains.dtype == torch.uint8 and stains.numel() == n * _STAIN_PARAMS_BYTES and stains.device == tiles_u8.device
+    assert stats.dtype == torch.int64 and stats.numel() >= n and stats.device == tiles_u8.device
+    if out is None:
+        out = torch.empty(n, out_size, out_size, 3, dtype=torch.uint8, device=tiles_u8.device)
+    a = L.gv_crop_augment_args(tiles_u8.data_ptr(), out.data_ptr(), boxes.data_ptr(), params.data_ptr(), stats.data_ptr(), n, tiles_u8.shape[0],
+                               tiles_u8.shape[1], tiles_u8.shape[2], out_size)
+    L.call("gv_crop_augment_stain", L.gv_crop_augment_stain_args(a, stains.data_ptr()), _stream())
+    return out
+
+
 def layernorm_fwd(x, gamma, beta, rows: int, D: int, x_stride: Optional[int] = None, eps: float = 1e-6,
                   y=None, mean=None, rstd=None):
     _chk(x, f32, "x")

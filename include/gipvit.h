@@ -207,6 +207,31 @@ typedef struct {
 } gv_crop_augment_args;
 int gv_crop_augment(const gv_crop_augment_args* a, void* stream);
 
+/* ---- gv_crop_augment with an H&E stain jitter (Tellez et al. 2018 / 2019, "HED" augmentation; absent from the reference) in
+ * the same pass.  Per crop: random-resized crop + flip (exactly gv_crop_resize's arithmetic)  ->  stain transform  ->  the
+ * chain of gv_crop_augment (colour ops in `order`, grayscale, blur, solarise); contrast blends with the mean grey of the
+ * STAINED view.  With M the stain matrix (rows H, E, D: Ruifrok & Johnston's vectors, each normalised to unit length), a
+ * pixel with bytes v_c goes through
+ *     od_c  = -ln((v_c + 1) / 256)                        (>= 0, finite for v = 0)
+ *     s     = od . M^-1                                   (stain concentrations, not clamped)
+ *     s'_k  = alpha_k * s_k + beta_k                      (k = H, E, D)
+ *     od'   = s' . M
+ *     v'_c  = clamp(rint(256 * exp(-od'_c) - 1), 0, 255)  (round half to even)
+ * The map is affine in od, so the host (gipvit.stain.stain_record) folds a crop's draw into A = M^-1 diag(alpha) M and
+ * b = beta M, both taken in fp64 and rounded to f32, and the kernel evaluates od'_c = sum_k od_k * A[k][c] + b[c] in f32
+ * (od from a 256-entry table of the fp64 values rounded once, the accurate expf).  on = 0: the crop's pixels pass through
+ * untouched; alpha = 1, beta = 0 is the identity on every byte.  Checks, launches and `stats` as gv_crop_augment.          */
+typedef struct {
+    int32_t on;                  /* 0: no stain transform for this crop                                         */
+    float A[9];                  /* row-major [k][c]                                                            */
+    float b[3];
+} gv_stain_params;
+typedef struct {
+    gv_crop_augment_args v;
+    const gv_stain_params* stain; /* device [v.n_crops], 4-byte aligned                                         */
+} gv_crop_augment_stain_args;
+int gv_crop_augment_stain(const gv_crop_augment_stain_args* a, void* stream);
+
 /* ---- tile augmentation on the device (replaces the CPU / PIL recipes of transformations.py:131-197 on tiles that are
  * already in HBM).  One parameter record per tile, drawn on the host; operations in reference order:
  *   colour ops in `order` (0 brightness, 1 contrast, 2 saturation, 3 hue: torchvision ColorJitter on PIL images, PIL's

@@ -88,6 +88,10 @@ def build_parser():
     g.add_argument("--gray-p", type=float, default=0.2, help="--view-augment: probability of a grayscale view")
     g.add_argument("--blur-p", type=float, nargs=3, default=(1.0, 0.1, 0.5), help="--view-augment: blur probability of global crop 1 / 2 / the local crops")
     g.add_argument("--solarize-p", type=float, default=0.2, help="--view-augment: solarisation probability of global crop 2")
+    g.add_argument("--stain-jitter", type=float, default=0.0, metavar="SIGMA", help="DINO, with --random-crops --view-augment: H&E stain jitter "
+                   "in optical-density space on every crop, in the same pass (gv_crop_augment_stain): per stain (haematoxylin, eosin, residual) "
+                   "alpha ~ U(1 - SIGMA, 1 + SIGMA), beta ~ U(-SIGMA, SIGMA); 0 = off, Tellez et al. use 0.05 (light) and 0.2 (strong)")
+    g.add_argument("--stain-prob", type=float, default=1.0, metavar="P", help="--stain-jitter: probability that a crop is jittered, 0 < P <= 1")
     g.add_argument("--global-crops-scale", type=float, nargs=2, default=(0.4, 1.0))
     g.add_argument("--local-crops-scale", type=float, nargs=2, default=(0.05, 0.4))
     g.add_argument("--momentum-teacher", type=float, default=0.996)
@@ -275,6 +279,13 @@ def check_supported(args, log=_logger.warning):
         raise SystemExit("--amp asks for mixed precision, --precision fp32 for f32 operands throughout: pick one")
     if args.view_augment and not (args.dino and args.random_crops):
         raise SystemExit("--view-augment augments the crops that --dino --random-crops cuts on the device: pass both")
+    if not (math.isfinite(args.stain_jitter) and 0 <= args.stain_jitter < 1):
+        raise SystemExit(f"--stain-jitter {args.stain_jitter}: sigma must be finite and in [0, 1) (alpha ~ U(1 - sigma, 1 + sigma) has to stay positive)")
+    if not 0 < args.stain_prob <= 1:
+        raise SystemExit(f"--stain-prob {args.stain_prob}: the share of jittered crops, 0 < P <= 1")
+    if args.stain_jitter > 0 and not (args.dino and args.random_crops and args.view_augment):
+        raise SystemExit("--stain-jitter runs inside the view-augmentation pass of the crops (gv_crop_augment_stain): "
+                         "pass --dino --random-crops --view-augment with it")
     if args.extract_attention and not args.extract_features:
         raise SystemExit("--extract-attention writes <slide>_attention.pt next to the features: it needs --extract_features")
     if args.knn_monitor:
@@ -818,9 +829,15 @@ def main(argv=None, transform=None):
         from gipvit.multicrop import ViewAugmentSampler
         view_sampler = ViewAugmentSampler(B, 2, args.local_crops_number, jitter_p=args.color_jitter_p, gray_p=args.gray_p, blur_p=tuple(args.blur_p),
                                           solar_p=(0.0, args.solarize_p, 0.0), seed=args.seed + 53 * rank + 5)
+    stain_sampler = None
+    if args.stain_jitter > 0:       # H&E stain jitter: folded per-crop records drawn per rank, applied in the view-augmentation pass
+        from gipvit.stain import StainJitterSampler
+        stain_sampler = StainJitterSampler(B, 2, args.local_crops_number, args.stain_jitter, prob=args.stain_prob, seed=args.seed + 313 * rank + 41)
+        if primary:
+            _logger.info("H&E stain jitter on the device: sigma %.3g prob %.3g (every crop, ahead of the view augmentation)", args.stain_jitter, args.stain_prob)
 
     def host_streams():
-        return {"drop": drop_rng, "crops": getattr(sampler, "rng", None), "views": getattr(view_sampler, "rng", None),
+        return {"drop": drop_rng, "crops": getattr(sampler, "rng", None), "views": getattr(view_sampler, "rng", None), "stain": getattr(stain_sampler, "rng", None),
                 "mix": getattr(mix_sampler, "rng", None), "erase": getattr(erase_sampler, "rng", None), "ibot": getattr(mask_sampler, "rng", None)}
 
     def gather_ranks(obj):
@@ -832,7 +849,7 @@ def main(argv=None, transform=None):
 
     def extra_state(rng_state):
         """``rng_state``: pack_host_rng's entries -- every rank's host-side draw streams (--drop step seeds, random-resized-crop
-        boxes, view augmentation, mixup, erasing, iBOT masks, --drop-path), gathered by ALL ranks at the save point."""
+        boxes, view augmentation, stain jitter, mixup, erasing, iBOT masks, --drop-path), gathered by ALL ranks at the save point."""
         ex = dict(rng_state)
         if args.dino:       # teacher (the EMA model) + centre: a DINO run cannot be resumed (or evaluated) without them
             ex["state_dict_ema"] = eng.arena.state_dict(eng.arena.t)
@@ -865,7 +882,7 @@ def main(argv=None, transform=None):
     if args.resume:     # continue every rank's draw streams where the saved run left them (or, across a change of world size, restart them apart)
         restore_host_rng(ck, host_streams(), drop_sampler, rank, world, start_epoch, warn=_logger.warning,
                          seeds={"drop": args.seed + 7919 * rank + 11, "crops": args.seed + rank, "views": args.seed + 53 * rank + 5,
-                                "mix": args.seed + 101 * rank + 23, "erase": args.seed + 211 * rank + 37, "ibot": args.seed + 101 * rank + 3,
+                                "stain": args.seed + 313 * rank + 41, "mix": args.seed + 101 * rank + 23, "erase": args.seed + 211 * rank + 37, "ibot": args.seed + 101 * rank + 3,
                                 "drop_path": args.seed + 17 * rank})
     cur_lr = lr
     # the reference logs the MEAN rate over the optimizer's parameter groups (train.py:1088-1089, 959-965): with --layer-decay
@@ -899,7 +916,8 @@ def main(argv=None, transform=None):
                            teacher_temp=teacher_temp_at(args, epoch))
                 loss_t = eng.step(data, boxes=sampler.sample(dev) if sampler is not None else None, fill=fill if sampler is None else None,
                                   views=view_sampler.sample(dev) if view_sampler is not None else None,
-                                  **({"masks": mask_sampler.sample(dev)} if mask_sampler is not None else {}), **sch)
+                                  **({"masks": mask_sampler.sample(dev)} if mask_sampler is not None else {}),
+                                  **({"stains": stain_sampler.sample(dev)} if stain_sampler is not None else {}), **sch)
             else:
                 ekw = {"erase": erase_sampler.sample(dev)} if erase_sampler is not None else {}
                 loss_t = eng.step(data, target, lr=cur_lr, fill=fill, mix=mix_sampler.sample(dev) if mix_sampler is not None else None, **ekw)
