@@ -62,6 +62,16 @@ gv_crop_augment_args = _struct("gv_crop_augment_args", [
 # one crop's folded H&E stain draw (gipvit.stain packs them) and gv_crop_augment with the table of them
 gv_stain_params = _struct("gv_stain_params", [("on", i32), ("A", f32 * 9), ("b", f32 * 3)])
 gv_crop_augment_stain_args = _struct("gv_crop_augment_stain_args", [("v", gv_crop_augment_args), ("stain", vp)])
+# Macenko stain normalisation (gipvit.stainnorm): the three estimation passes, the u8 -> u8 map and patchify with the map inside
+f64 = C.c_double
+gv_stain_stats_args = _struct("gv_stain_stats_args", [
+    ("tiles", vp), ("img_stride", i64), ("n", i32), ("h", i32), ("w", i32), ("v_max", i32), ("workspace", vp), ("out", vp)])
+gv_stain_angle_hist_args = _struct("gv_stain_angle_hist_args", [
+    ("tiles", vp), ("img_stride", i64), ("n", i32), ("h", i32), ("w", i32), ("v_max", i32), ("n_bins", i32), ("V", f64 * 6), ("workspace", vp), ("out", vp)])
+gv_stain_conc_hist_args = _struct("gv_stain_conc_hist_args", [
+    ("tiles", vp), ("img_stride", i64), ("n", i32), ("h", i32), ("w", i32), ("n_bins", i32), ("pinv", f64 * 6), ("cmax", f64 * 2), ("workspace", vp), ("out", vp)])
+gv_stain_apply_args = _struct("gv_stain_apply_args", [("tiles", vp), ("out", vp), ("stain", vp), ("img_stride", i64), ("n", i32), ("h", i32), ("w", i32)])
+gv_patchify_stain_args = _struct("gv_patchify_stain_args", [("p", gv_patchify_args), ("stain", vp)])
 gv_crop_resize_args = _struct("gv_crop_resize_args", [
     ("tiles", vp), ("out", vp), ("boxes", vp), ("n_crops", i32), ("n_tiles", i32), ("tile_h", i32), ("tile_w", i32), ("out_size", i32)])
 gv_layernorm_fwd_args = _struct("gv_layernorm_fwd_args", [
@@ -213,6 +223,8 @@ ENTRY_POINTS = {
     "gv_patchify_mix_f32": gv_patchify_mix_args, "gv_patchify_nchw_mix_f32": gv_patchify_nchw_mix_args,
     "gv_patchify_erase": gv_patchify_erase_args, "gv_patchify_nchw_erase": gv_patchify_nchw_erase_args,
     "gv_patchify_erase_f32": gv_patchify_erase_args, "gv_patchify_nchw_erase_f32": gv_patchify_nchw_erase_args,
+    "gv_stain_stats": gv_stain_stats_args, "gv_stain_angle_hist": gv_stain_angle_hist_args, "gv_stain_conc_hist": gv_stain_conc_hist_args,
+    "gv_stain_apply": gv_stain_apply_args, "gv_patchify_stain": gv_patchify_stain_args, "gv_patchify_stain_f32": gv_patchify_stain_args,
     "gv_gather_cls": gv_gather_cls_args, "gv_cast_bf16": gv_cast_bf16_args, "gv_store_f32": gv_store_f32_args, "gv_sumsq": gv_sumsq_args,
     "gv_adamw_ema": gv_adamw_ema_args, "gv_adamw_ema_ranges": gv_adamw_ema_ranges_args, "gv_loss_scale_update": gv_loss_scale_update_args, "gv_lamb": gv_lamb_args, "gv_agc": gv_agc_args, "gv_dropout": gv_dropout_args, "gv_dropout_add": gv_dropout_add_args,
     # fp32 operand mode: the same structs with every bf16 buffer read / written as f32

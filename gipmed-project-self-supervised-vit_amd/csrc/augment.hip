@@ -14,13 +14,12 @@
 // blends with the MEAN grey level of the image as it is when the operation runs (after the operations drawn before it): a
 // first kernel takes that mean per tile (integer sum of PIL's "L" values, exact).
 #include "gv_common.h"
+#include "stain_px.h"
 #include <type_traits>
 
 #pragma clang fp contract(off)
 
 namespace {
-
-struct Px { int r, g, b; };
 
 __device__ __forceinline__ int lum(const Px p) { return (p.r * 19595 + p.g * 38470 + p.b * 7471 + 0x8000) >> 16; }
 
@@ -215,20 +214,8 @@ __device__ __forceinline__ Px jitter_gray(Px p, const gv_view_params& q, int mea
     return p;
 }
 
-// gv_crop_augment_stain: the H&E stain jitter of a crop's pixel, directly behind resample() in both kernels (formula:
-// include/gipvit.h).  od comes from `odt`, the block's 256-entry table of -ln((v + 1) / 256) (fp64, rounded once); od' is
-// summed left to right without contraction, exp is the accurate library function: a result is off the fp64 one by less than
-// 1e-4 of a grey level, so the rounded byte differs only within that distance of a tie.
-__device__ __forceinline__ Px stain_px(const Px p, const gv_stain_params& s, const float* odt) {
-    const float od[3] = {odt[p.r], odt[p.g], odt[p.b]};
-    int c3[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float t = od[0] * s.A[c] + od[1] * s.A[3 + c] + od[2] * s.A[6 + c] + s.b[c];
-        c3[c] = (int)fminf(fmaxf(rintf(256.0f * expf(-t) - 1.0f), 0.f), 255.f);
-    }
-    return Px{c3[0], c3[1], c3[2]};
-}
+// gv_crop_augment_stain: the H&E stain jitter of a crop's pixel is stain_px() (stain_px.h; formula: include/gipvit.h), directly
+// behind resample() in both kernels; od comes from `odt`, the block's 256-entry table.
 
 // the kernels below exist once without the stain transform (gv_crop_augment: argument record, LDS and code as before it
 // existed) and once with it
@@ -243,7 +230,7 @@ __device__ __forceinline__ gv_stain_params load_stain(const ViewArgs<STAIN>& va,
     st.on = 0;
     if constexpr (STAIN) {
         st = va.stain[n];
-        if (st.on) odt[threadIdx.x] = (float)(-log((double)(threadIdx.x + 1) * (1.0 / 256.0)));
+        if (st.on) odt[threadIdx.x] = stain_od_entry(threadIdx.x);
         __syncthreads();
     }
     return st;

@@ -10,14 +10,19 @@
 // rows: reads are 192-B contiguous per pixel row, writes 512-B contiguous per
 // (patch, channel).   algorithmic bytes / image: crop^2 * 3 in + (crop/16)^2 * 1536 out.
 #include "gv_common.h"
+#include "stain_px.h"
 
 namespace {
 
 struct norm_consts { float s0, s1, s2, o0, o1, o2; };
 
 // n(tile, y, x .. x + 15, c): the normalised f32 values of one 16-pixel run of a tile (with its fill box applied) -- the ONE
-// place the value is computed, for the plain and the mixing kernel alike, so both contract it the same way.
-__device__ __forceinline__ void norm_run(const gv_patchify_args& a, const norm_consts& k, int tile, int y, int x, float (&px)[3][16]) {
+// place the value is computed, for the plain, the mixing and the stain kernel alike, so all contract it the same way.
+// STAIN (gv_patchify_stain): a record `st` with on != 0 maps the run's 16 pixels byte to byte (stain_px, table `odt`) between the
+// load and the normalisation; the instantiation without it is the code as it was.
+template <bool STAIN = false>
+__device__ __forceinline__ void norm_run(const gv_patchify_args& a, const norm_consts& k, int tile, int y, int x, float (&px)[3][16],
+                                         const gv_stain_params* st = nullptr, const float* odt = nullptr) {
     const float s0 = k.s0, s1 = k.s1, s2 = k.s2, o0 = k.o0, o1 = k.o1, o2 = k.o2;
     const uint8_t* src = a.tiles + (long)tile * a.img_stride + ((long)y * a.tile_w + x) * 3;
 
@@ -41,6 +46,22 @@ __device__ __forceinline__ void norm_run(const gv_patchify_args& a, const norm_c
         const int sh = mis * 8;
 #pragma unroll
         for (int i = 0; i < 12; ++i) u[i] = (d[i] >> sh) | (d[i + 1] << (32 - sh));
+    }
+    if constexpr (STAIN) {
+        if (st->on) {
+            uint32_t v[12] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int j = 3 * i;
+                const Px q = stain_px(Px{(int)((u[j >> 2] >> (8 * (j & 3))) & 0xFF), (int)((u[(j + 1) >> 2] >> (8 * ((j + 1) & 3))) & 0xFF),
+                                         (int)((u[(j + 2) >> 2] >> (8 * ((j + 2) & 3))) & 0xFF)}, *st, odt);
+                v[j >> 2] |= (uint32_t)q.r << (8 * (j & 3));
+                v[(j + 1) >> 2] |= (uint32_t)q.g << (8 * ((j + 1) & 3));
+                v[(j + 2) >> 2] |= (uint32_t)q.b << (8 * ((j + 2) & 3));
+            }
+#pragma unroll
+            for (int i = 0; i < 12; ++i) u[i] = v[i];
+        }
     }
     // byte j of the run = pixel j/3, channel j%3
 #pragma unroll
@@ -167,6 +188,36 @@ __global__ __launch_bounds__(256) void patchify_kernel(gv_patchify_args a, int P
     } else {
         norm_run(a, k, tile, y, x, px);
     }
+    store_run<F32OUT>(a.patches, ip, py, px);
+}
+
+// ---- patchify_stain (gv_patchify_stain): patchify_kernel with tile t's bytes mapped through record stain[t] first.  Same thread
+// mapping and stores; the new work is 48 table look-ups and 48 expf per thread of a tile whose record is on.  The od table is the
+// same for every record, so a workgroup builds it once if any of its threads needs it (a workgroup may span tiles); one whose
+// tiles are all off takes the barrier and nothing else.
+template <bool F32OUT>
+__global__ __launch_bounds__(256) void patchify_stain_kernel(gv_patchify_args a, const gv_stain_params* stain, int P, int side, norm_consts k) {
+    __shared__ float odt[256];
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const long total = (long)a.n_img * P * 16;
+    const bool live = t < total;
+    const int py = (int)(t & 15);
+    const long ip = t >> 4;
+    const int patch = (int)(ip % P);
+    const int img = (int)(ip / P);
+    const int tile = img % a.n_tiles, win = img / a.n_tiles;
+    gv_stain_params st;
+    st.on = 0;
+    if (live) st = stain[tile];
+    if (__syncthreads_or(st.on != 0)) {
+        odt[threadIdx.x] = stain_od_entry(threadIdx.x);
+        __syncthreads();
+    }
+    if (!live) return;
+    const int prow = patch / side, pcol = patch - prow * side;
+    const int y = a.win_y[win] + prow * 16 + py, x = a.win_x[win] + pcol * 16;
+    float px[3][16];
+    norm_run<true>(a, k, tile, y, x, px, &st, odt);
     store_run<F32OUT>(a.patches, ip, py, px);
 }
 
@@ -454,9 +505,14 @@ static int erase_check(const char* name, const gv_mix_row* mix, const erase_in* 
 
 // mix == nullptr: gv_patchify; else gv_patchify_mix (has_mix says which was called: a NULL table is then an error).  er: the call
 // is gv_patchify_erase, with or without a mix table.
+// stain: the call is gv_patchify_stain (has_stain says so: a NULL table is then an error), without mix / erase tables.
 template <bool F32OUT> static int patchify_launch(const gv_patchify_args* a, void* stream, const gv_mix_row* mix = nullptr, bool has_mix = false,
-                                                  const erase_in* er = nullptr) {
+                                                  const erase_in* er = nullptr, const gv_stain_params* stain = nullptr, bool has_stain = false) {
     GV_REQUIRE(a && a->tiles && a->patches, GV_E_NULL, "gv_patchify: null pointer");
+    if (has_stain) {
+        GV_REQUIRE(stain, GV_E_NULL, "gv_patchify_stain: null stain table");
+        GV_REQUIRE(gv_aligned(stain, 4), GV_E_ALIGN, "gv_patchify_stain: the stain table must be 4-byte aligned");
+    }
     if (has_mix) {
         GV_REQUIRE(mix, GV_E_NULL, "gv_patchify_mix: null mix table");
         GV_REQUIRE(gv_aligned(mix, 4), GV_E_ALIGN, "gv_patchify_mix: the mix table must be 4-byte aligned");
@@ -476,6 +532,11 @@ template <bool F32OUT> static int patchify_launch(const gv_patchify_args* a, voi
     const float o0 = -a->mean[0] / a->std[0], o1 = -a->mean[1] / a->std[1], o2 = -a->mean[2] / a->std[2];
     const norm_consts k{s0, s1, s2, o0, o1, o2};
     const dim3 grid((unsigned)((total + 255) / 256));
+    if (has_stain) {
+        hipLaunchKernelGGL((patchify_stain_kernel<F32OUT>), grid, dim3(256), 0, (hipStream_t)stream, *a, stain, P, side, k);
+        GV_LAUNCH_CHECK("gv_patchify_stain");
+        return GV_OK;
+    }
     if (er) {
         if (const int rc = erase_check("gv_patchify_erase", mix, er, a->n_win, a->n_img, a->crop)) return rc;
         if (mix)
@@ -503,6 +564,14 @@ extern "C" int gv_patchify_erase_f32(const gv_patchify_erase_args* a, void* stre
     GV_REQUIRE(a, GV_E_NULL, "gv_patchify_erase_f32: null pointer");
     const erase_in er{a->erase, a->seed};
     return patchify_launch<true>(&a->p, stream, a->mix, false, &er);
+}
+extern "C" int gv_patchify_stain(const gv_patchify_stain_args* a, void* stream) {
+    GV_REQUIRE(a, GV_E_NULL, "gv_patchify_stain: null pointer");
+    return patchify_launch<false>(&a->p, stream, nullptr, false, nullptr, a->stain, true);
+}
+extern "C" int gv_patchify_stain_f32(const gv_patchify_stain_args* a, void* stream) {
+    GV_REQUIRE(a, GV_E_NULL, "gv_patchify_stain_f32: null pointer");
+    return patchify_launch<true>(&a->p, stream, nullptr, false, nullptr, a->stain, true);
 }
 extern "C" int gv_patchify(const gv_patchify_args* a, void* stream) { return patchify_launch<false>(a, stream); }
 extern "C" int gv_patchify_f32(const gv_patchify_args* a, void* stream) { return patchify_launch<true>(a, stream); }

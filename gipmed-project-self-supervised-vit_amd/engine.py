@@ -506,7 +506,7 @@ class VitRunner:
 
     # ---- forward: tiles -> CLS features written into feats[row_off + seg.img0 ...]
     def forward(self, W: Weights, G: VitGroup, tiles_u8, windows, mean, std, feats, row_off: int = 0, fill=None, on_side: bool = False,
-                capture: Optional[Capture] = None, mix: Optional[torch.Tensor] = None, erase=None, masks=None, patch=None):
+                capture: Optional[Capture] = None, mix: Optional[torch.Tensor] = None, erase=None, masks=None, patch=None, stain=None):
         """windows: one list of (y0, x0) crop origins per segment; tiles_u8: one NHWC u8 tensor for all
         segments, or one per segment (pre-cut crops: each with the single window (0, 0)).  A float32 NCHW source (already
         normalised, engine.input_form) goes through gv_patchify_nchw instead, without mean / std.  ``fill``: per-tile normalised
@@ -521,8 +521,14 @@ class VitRunner:
         patch embeddings are replaced by ``mask_token`` (+ pos) behind the patch-embedding product (gv_mask_tokens_fwd).
         ``patch``: (MaskPlan, PatchRows) -- the final norm also runs on the plan's rows of the first segment, into
         ``PatchRows.hb.feats`` (gv_rows_gather + gv_layernorm_fwd); the group must have ``all_tokens`` set.  Either None, or a
-        plan without a marked patch, issues exactly the default launches."""
+        plan without a marked patch, issues exactly the default launches.
+        ``stain``: one packed gv_stain_params record per tile on the device (gipvit.stainnorm: stain normalisation at inference) --
+        the uint8 tiles of a forward-only single-segment group go through it inside the patchify pass (gv_patchify_stain); None
+        issues exactly the default launches."""
         D, T, H = self.D, G.T, self.H
+        if stain is not None and (G.save or len(G.segs) != 1 or mix is not None or erase is not None):
+            raise ValueError("stain: inference only -- a forward-only single-segment group without mix / erase tables (training is never normalised)")
+        skw = {} if stain is None else {"stain": stain}        # the keyword exists for a pass with a record only
         if (masks is not None or patch is not None) and not G.all_tokens:
             raise ValueError("masks / patch: the group must run its last block on every token (VitGroup.all_tokens)")
         cap = capture
@@ -550,9 +556,11 @@ class VitRunner:
             if src.dtype == f32:
                 if fill is not None:
                     raise ValueError("fill= works on uint8 tiles: not with float32 NCHW input")
+                if stain is not None:
+                    raise ValueError("stain= works on uint8 tiles: float32 NCHW input is already normalised, its bytes are gone")
                 ops.patchify_nchw(src, wins, sg.crop, out=sg.patches, mix=mix, **ekw)
             else:
-                ops.patchify(src, wins, sg.crop, mean, std, out=sg.patches, fill=fill, mix=mix, **ekw)
+                ops.patchify(src, wins, sg.crop, mean, std, out=sg.patches, fill=fill, mix=mix, **ekw, **skw)
             if sg.pos is None:
                 pos = pos_full
             else:   # interpolate_pos_encoding: row 0 = cls pos, rows 1.. = M @ pos[1:]
@@ -1782,6 +1790,25 @@ class FeatureExtractor:
         self._pad = self._pad_f32 = None
         self._scratch: Dict[str, torch.Tensor] = {}      # capture buffers of a padded last batch (_out_or_scratch)
         self._tok_stats = None                             # f32 [2, T]: LayerNorm statistics of captured tokens
+        self._stain = self._stain_buf = None               # set_stain: B copies of the slide's gv_stain_params record, device
+
+    def set_stain(self, record) -> None:
+        """Stain normalisation of the current slide (gipvit.stainnorm): ``record`` is ONE gv_stain_params record (the structured
+        numpy array of ``stainnorm.normaliser_record`` / ``SlideStain.record``, or its 52 packed bytes as a uint8 tensor).  While
+        set, every pass of this extractor (``forward``, ``run``, ``run_with_attention``, ``last_selfattention``,
+        ``intermediate_layers``, ``probe_features``; padded last batches and precision="fp32" included) patchifies through
+        gv_patchify_stain with the record broadcast over the batch; float32 NCHW input then raises ValueError.  None: off."""
+        if record is None:
+            self._stain = None
+            return
+        from .stainnorm import pack_record
+        one = record if isinstance(record, torch.Tensor) else pack_record(record)
+        if one.dtype != torch.uint8 or one.numel() != ops._STAIN_PARAMS_BYTES:
+            raise ValueError(f"set_stain: expected one gv_stain_params record ({ops._STAIN_PARAMS_BYTES} bytes)")
+        if self._stain_buf is None:
+            self._stain_buf = torch.empty(self.B * ops._STAIN_PARAMS_BYTES, dtype=torch.uint8, device=self.dev)
+        self._stain_buf.view(self.B, -1).copy_(one.reshape(1, -1).to(self.dev))
+        self._stain = self._stain_buf
 
     def load_state(self, state: Dict[str, torch.Tensor]):
         if "mask_token" in state:       # an iBOT student / teacher: the token stands in for masked patches in training only
@@ -1794,7 +1821,10 @@ class FeatureExtractor:
         logits f32 [B, C] or None).  ``capture``: attention / token outputs of the same pass (``Capture``)."""
         if input_form(tiles_u8, self.B, (self.img, self.img)) == "u8":
             assert tiles_u8.shape == (self.B, self.img, self.img, 3)
-        self.vit.forward(self.W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats, capture=capture)
+        elif self._stain is not None:
+            raise ValueError("a stain record is set (set_stain): float32 NCHW input is already normalised and cannot be stain-normalised")
+        skw = {} if self._stain is None else {"stain": self._stain}
+        self.vit.forward(self.W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats, capture=capture, **skw)
         if self.C:
             ops.small_matmul(self.feats, self.W.f("head.weight"), self.logits, self.B, self.C, self.D, sam=self.D, sak=1, sbk=1, sbn=self.D,
                              bias=self.W.f("head.bias"))

@@ -65,15 +65,21 @@ def centred_window(data: torch.Tensor, img: int) -> torch.Tensor:
     return data
 
 
-def collect_features(loader, C: int, features, who: str):
+def collect_features(loader, C: int, features, who: str, normaliser=None):
     """-> (features f32 [N, D] device, labels int64 [N], slide ordinal int64 [N], slides left out) over the slides whose label
-    is inside [0, C); ``features(data)`` maps one chunk of tiles to its f32 [n, D] rows."""
+    is inside [0, C); ``features(data)`` maps one chunk of tiles to its f32 [n, D] rows.  ``normaliser``: a
+    gipvit.stainnorm.SlideNormaliser over the runner behind ``features`` -- every chunk is announced to it first (a slide begins
+    behind the previous ``Is Last Batch``), so the bank and the query pass see stain-normalised tiles; None: nothing changes."""
     if hasattr(loader, "reset_counter"):
         loader.reset_counter()
     feats, labels, slides, skipped, ordinal = [], [], [], 0, 0
+    first = True
     for mb in loader:
         y = int(mb["Label"].reshape(-1)[0])
         if 0 <= y < C:
+            if normaliser is not None:
+                normaliser.begin(mb["Data"], first)
+                first = False
             f = features(mb["Data"])
             feats.append(f)
             labels.append(np.full(f.shape[0], y, dtype=np.int64))
@@ -81,6 +87,9 @@ def collect_features(loader, C: int, features, who: str):
         if mb["Is Last Batch"]:
             skipped += not 0 <= y < C
             ordinal += 1
+            first = True
+    if normaliser is not None:
+        normaliser.end()
     if not feats:
         raise ValueError(f"{who}: no slide with a label in [0, {C}) in the loader")
     return torch.cat(feats), np.concatenate(labels), np.concatenate(slides), skipped
@@ -90,7 +99,8 @@ class KnnMonitor:
     """``runner``: an ``engine.FeatureExtractor`` (``run(tiles) -> (features f32 [n, D], logits)``).  ``build_bank(loader)`` then
     ``evaluate(loader)``; loaders are ``data.InferTiles`` / ``data.SyntheticSlides``."""
 
-    def __init__(self, runner, k: int = 20, temp: float = 0.07, num_classes: int = 2, primary: bool = True, log: Optional[logging.Logger] = None):
+    def __init__(self, runner, k: int = 20, temp: float = 0.07, num_classes: int = 2, primary: bool = True, log: Optional[logging.Logger] = None,
+                 normaliser=None):
         if not 1 <= k <= 64:
             raise ValueError(f"KnnMonitor: k must be in 1..64 (got {k})")
         if not temp > 0:
@@ -99,6 +109,7 @@ class KnnMonitor:
             raise ValueError(f"KnnMonitor: num_classes must be in 1..32 (got {num_classes})")
         self.runner, self.k, self.temp, self.C, self.primary, self.log = runner, k, temp, num_classes, primary, log or _logger
         self.bank = self.bank_labels = None
+        self.normaliser = normaliser                     # gipvit.stainnorm.SlideNormaliser over ``runner``, or None
 
     def _window(self, data: torch.Tensor) -> torch.Tensor:
         return centred_window(data, self.runner.img)
@@ -115,7 +126,7 @@ class KnnMonitor:
         return out
 
     def _collect(self, loader):
-        return collect_features(loader, self.C, self.features, "KnnMonitor")
+        return collect_features(loader, self.C, self.features, "KnnMonitor", normaliser=self.normaliser)
 
     def build_bank(self, loader) -> int:
         feats, labels, slides, skipped = self._collect(loader)

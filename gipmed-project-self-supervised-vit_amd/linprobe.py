@@ -85,7 +85,7 @@ class LinearProbe:
 
     def __init__(self, runner, num_classes: int = 2, lrs: Sequence[float] = (0.001,), weight_decay: float = 0.0, epochs: int = 100,
                  batch: int = 1024, n_last: int = 4, avgpool: bool = False, holdout: float = 0.2, seed: int = 0, primary: bool = True,
-                 log: Optional[logging.Logger] = None):
+                 log: Optional[logging.Logger] = None, normaliser=None):
         lrs = tuple(float(v) for v in lrs)
         if not 1 <= num_classes <= MAX_CLASSES:
             raise ValueError(f"LinearProbe: num_classes must be in 1..{MAX_CLASSES} (got {num_classes})")
@@ -110,6 +110,7 @@ class LinearProbe:
         self.W = self.b = None
         self.head = 0
         self.selection_loss = self.train_loss = None
+        self.normaliser = normaliser                     # gipvit.stainnorm.SlideNormaliser over ``runner``, or None
 
     def features(self, data: torch.Tensor) -> torch.Tensor:
         """f32 [n, F] probe features of one chunk of tiles, on the device."""
@@ -119,7 +120,7 @@ class LinearProbe:
         return self.runner.probe_features(data, self.n_last, self.avgpool)
 
     def _collect(self, loader):
-        return collect_features(loader, self.C, self.features, "LinearProbe")
+        return collect_features(loader, self.C, self.features, "LinearProbe", normaliser=self.normaliser)
 
     def fit(self, bank_loader) -> int:
         """Train every head on the bank (minus the held-out slides when there is more than one head) and choose the head to

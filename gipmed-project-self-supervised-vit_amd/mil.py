@@ -87,7 +87,7 @@ class MilProbe:
 
     def __init__(self, runner, num_classes: int = 2, hidden: int = 128, lr: float = 5e-4, weight_decay: float = 1e-4, epochs: int = 50,
                  batch: int = 8, n_last: int = 1, seed: int = 0, primary: bool = True, log: Optional[logging.Logger] = None,
-                 features: Optional[int] = None):
+                 features: Optional[int] = None, normaliser=None):
         if not 1 <= num_classes <= MAX_CLASSES:
             raise ValueError(f"MilProbe: num_classes must be in 1..{MAX_CLASSES} (got {num_classes})")
         if hidden % 16 or not 16 <= hidden <= MAX_HIDDEN:
@@ -111,6 +111,7 @@ class MilProbe:
         self.n_last, self.seed, self.primary, self.log = n_last, seed, primary, log or _logger
         self.params = None
         self.train_loss = None
+        self.normaliser = normaliser                     # gipvit.stainnorm.SlideNormaliser over ``runner``, or None
 
     def features(self, data: torch.Tensor) -> torch.Tensor:
         """f32 [n, F] probe features of one chunk of tiles, on the device."""
@@ -121,7 +122,7 @@ class MilProbe:
 
     def _collect(self, loader):
         """-> (features f32 [N, F] device, bag_ptr int32 [n + 1], slide labels int64 [n], slides left out)."""
-        feats, labels, slides, skipped = collect_features(loader, self.C, self.features, "MilProbe")
+        feats, labels, slides, skipped = collect_features(loader, self.C, self.features, "MilProbe", normaliser=self.normaliser)
         ptr = bag_table(slides)
         return feats, ptr, labels[ptr[:-1]], skipped
 

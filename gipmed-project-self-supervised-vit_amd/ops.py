@@ -79,12 +79,15 @@ def _erase_table(erase, n_tiles: int, windows):
 
 
 def patchify(tiles_u8: torch.Tensor, windows: Sequence[Sequence[int]], crop: int, mean, std,
-             out: Optional[torch.Tensor] = None, fill: Optional[torch.Tensor] = None, mix: Optional[torch.Tensor] = None, erase=None) -> torch.Tensor:
+             out: Optional[torch.Tensor] = None, fill: Optional[torch.Tensor] = None, mix: Optional[torch.Tensor] = None, erase=None,
+             stain: Optional[torch.Tensor] = None) -> torch.Tensor:
     """tiles_u8 [n_tiles, H, W, 3] u8 NHWC; windows [(y0, x0)] of side ``crop``.
     Returns bf16 patches [(len(windows) * n_tiles) * (crop/16)^2, 768], images crop-major.
     ``mix``: a device mix table (gipvit.mixup) -- the batch is mixed in the same pass (gv_patchify_mix), one window only.
     ``erase``: (device erase table, seed) of a gipvit.erasing.ErasePlan -- random erasing in the same pass, after ``fill`` and
-    ``mix`` (gv_patchify_erase), one window only."""
+    ``mix`` (gv_patchify_erase), one window only.
+    ``stain``: n_tiles packed gv_stain_params records on the device (gipvit.stainnorm) -- each tile's bytes go through its record
+    inside the same pass (gv_patchify_stain), ``fill`` after it; not with ``mix`` / ``erase`` (training tables)."""
     _chk(tiles_u8, torch.uint8, "tiles")
     assert tiles_u8.dim() == 4 and tiles_u8.shape[-1] == 3 and tiles_u8.is_contiguous()
     n_tiles, H, W, _ = tiles_u8.shape
@@ -102,6 +105,11 @@ def patchify(tiles_u8: torch.Tensor, windows: Sequence[Sequence[int]], crop: int
     if fill is not None:        # f32 [n_tiles, 8] device: normalised fill boxes (Cutout after Normalize, MeanPixelRegularization)
         assert fill.is_cuda and fill.dtype == f32 and fill.shape == (n_tiles, 8) and fill.is_contiguous()
         a.fill = fill.data_ptr()
+    if stain is not None:
+        if mix is not None or erase is not None:
+            raise ValueError("stain: inference-time normalisation does not combine with the training tables mix / erase")
+        L.call("gv_patchify_stain" + _sfx(out), L.gv_patchify_stain_args(a, _stain_table(stain, n_tiles, tiles_u8.device)), _stream())
+        return out
     if erase is not None:
         L.call("gv_patchify_erase" + _sfx(out), L.gv_patchify_erase_args(a, None if mix is None else _mix_table(mix, n_tiles, windows),
                                                                          *_erase_table(erase, n_tiles, windows)), _stream())
@@ -206,6 +214,87 @@ def crop_augment_stain(tiles_u8: torch.Tensor, boxes: torch.Tensor, params: torc
     a = L.gv_crop_augment_args(tiles_u8.data_ptr(), out.data_ptr(), boxes.data_ptr(), params.data_ptr(), stats.data_ptr(), n, tiles_u8.shape[0],
                                tiles_u8.shape[1], tiles_u8.shape[2], out_size)
     L.call("gv_crop_augment_stain", L.gv_crop_augment_stain_args(a, stains.data_ptr()), _stream())
+    return out
+
+
+def _stain_table(stain: torch.Tensor, n: int, device) -> int:
+    """Pointer of a device table of ``n`` packed gv_stain_params records (uint8)."""
+    if not (isinstance(stain, torch.Tensor) and stain.is_cuda and stain.device == device and stain.dtype == torch.uint8 and stain.is_contiguous()
+            and stain.numel() == n * _STAIN_PARAMS_BYTES):
+        raise ValueError(f"stain: expected a contiguous uint8 device tensor of {n} gv_stain_params records ({n * _STAIN_PARAMS_BYTES} bytes)")
+    return stain.data_ptr()
+
+
+def _stain_tiles(tiles_u8: torch.Tensor):
+    """(n, h, w, bytes between tiles) of u8 NHWC tiles whose images are dense (a slice along the first dimension is fine)."""
+    _chk(tiles_u8, torch.uint8, "tiles")
+    if tiles_u8.dim() != 4 or tiles_u8.shape[-1] != 3 or tiles_u8.shape[0] < 1:
+        raise ValueError(f"tiles: expected uint8 [n, h, w, 3], got {tuple(tiles_u8.shape)}")
+    n, h, w, _ = tiles_u8.shape
+    if tuple(tiles_u8.stride()[1:]) != (3 * w, 3, 1) or (n > 1 and tiles_u8.stride(0) < 3 * h * w):
+        raise ValueError(f"tiles: every image must be dense NHWC (strides {tiles_u8.stride()})")
+    return n, h, w, (tiles_u8.stride(0) if n > 1 else 3 * h * w)
+
+
+def _stain_groups(n_pixels: int) -> int:
+    """Workgroups (= partials) of the three estimation passes: clamp(ceil(n h w / 256), 1, 512), a function of the shape only."""
+    return max(1, min(512, -(-int(n_pixels) // 256)))
+
+
+def stain_stats(tiles_u8: torch.Tensor, v_max: int):
+    """Pass 1 of the Macenko estimate (gv_stain_stats) over tissue pixels (every byte <= ``v_max``) -> (n int64 [1], sums f64 [9] =
+    sum od_r, od_g, od_b, then sum od_i od_j for rr, rg, rb, gg, gb, bb), device tensors."""
+    n, h, w, stride = _stain_tiles(tiles_u8)
+    ws = torch.empty(_stain_groups(n * h * w) * 10, dtype=torch.int64, device=tiles_u8.device)
+    out = torch.empty(10, dtype=torch.int64, device=tiles_u8.device)
+    L.call("gv_stain_stats", L.gv_stain_stats_args(tiles_u8.data_ptr(), stride, n, h, w, int(v_max), ws.data_ptr(), out.data_ptr()), _stream())
+    return out[:1], out[1:].view(torch.float64)
+
+
+def stain_angle_hist(tiles_u8: torch.Tensor, V, v_max: int, bins: int = 4096) -> torch.Tensor:
+    """Pass 2 (gv_stain_angle_hist): histogram of atan2(od . V[:, 1], od . V[:, 0]) over tissue pixels, ``bins`` bins over
+    [-pi, pi) -> int64 [bins] on the device.  ``V``: host [3, 2] floats."""
+    n, h, w, stride = _stain_tiles(tiles_u8)
+    bins = int(bins)
+    a = L.gv_stain_angle_hist_args()
+    a.tiles, a.img_stride, a.n, a.h, a.w, a.v_max, a.n_bins = tiles_u8.data_ptr(), stride, n, h, w, int(v_max), bins
+    for i in range(3):
+        for k in range(2):
+            a.V[i * 2 + k] = float(V[i][k])
+    ws = torch.empty(_stain_groups(n * h * w) * max(bins, 1), dtype=torch.int32, device=tiles_u8.device)
+    out = torch.empty(max(bins, 1), dtype=torch.int64, device=tiles_u8.device)
+    a.workspace, a.out = ws.data_ptr(), out.data_ptr()
+    L.call("gv_stain_angle_hist", a, _stream())
+    return out
+
+
+def stain_conc_hist(tiles_u8: torch.Tensor, pinv, cmax, bins: int = 4096) -> torch.Tensor:
+    """Pass 3 (gv_stain_conc_hist): per stain k the histogram of c_k = pinv[k] . od over ALL pixels, ``bins`` bins over
+    [0, cmax[k]) -> int64 [2, bins + 1] on the device, the last column the count of c_k < 0.  ``pinv``: host [2, 3]."""
+    n, h, w, stride = _stain_tiles(tiles_u8)
+    bins = int(bins)
+    a = L.gv_stain_conc_hist_args()
+    a.tiles, a.img_stride, a.n, a.h, a.w, a.n_bins = tiles_u8.data_ptr(), stride, n, h, w, bins
+    for k in range(2):
+        a.cmax[k] = float(cmax[k])
+        for j in range(3):
+            a.pinv[k * 3 + j] = float(pinv[k][j])
+    ws = torch.empty(_stain_groups(n * h * w) * 2 * (max(bins, 1) + 1), dtype=torch.int32, device=tiles_u8.device)
+    out = torch.empty(2, max(bins, 1) + 1, dtype=torch.int64, device=tiles_u8.device)
+    a.workspace, a.out = ws.data_ptr(), out.data_ptr()
+    L.call("gv_stain_conc_hist", a, _stream())
+    return out
+
+
+def stain_apply(tiles_u8: torch.Tensor, stains: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """u8 tiles -> u8 tiles through one gv_stain_params record per tile (gv_stain_apply): ``stains`` holds n packed records
+    (uint8, device); a tile whose record has on = 0 is copied."""
+    n, h, w, stride = _stain_tiles(tiles_u8)
+    if out is None:
+        out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=tiles_u8.device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, 3) or not out.is_contiguous() or out.device != tiles_u8.device:
+        raise ValueError(f"out: expected a contiguous uint8 [{n}, {h}, {w}, 3] on {tiles_u8.device}")
+    L.call("gv_stain_apply", L.gv_stain_apply_args(tiles_u8.data_ptr(), out.data_ptr(), _stain_table(stains, n, tiles_u8.device), stride, n, h, w), _stream())
     return out
 
 

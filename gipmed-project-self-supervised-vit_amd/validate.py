@@ -51,10 +51,13 @@ def _auc(y: np.ndarray, score: np.ndarray) -> float:
 
 def validate(runner, loader, *, extract_features: bool = False, extract_attention: bool = False, smoothing: float = 0.1, log_interval: int = 50,
              out_dir: str = "./TCGA_500", log_suffix: str = "", primary: bool = True, reference_layout: bool = False,
-             log: Optional[logging.Logger] = None) -> "OrderedDict[str, float]":
+             log: Optional[logging.Logger] = None, normaliser=None) -> "OrderedDict[str, float]":
     """runner: ``engine.FeatureExtractor`` (``run(tiles) -> (features, logits)``); loader: ``data.InferTiles`` /
     ``data.SyntheticSlides``.  Returns OrderedDict(loss, top1, top5, auc_per_patch, auc_per_slide) -- the first three
-    are the reference's ``metrics`` (train.py:1340), the AUCs what it sends to W&B (train.py:1342-1343)."""
+    are the reference's ``metrics`` (train.py:1340), the AUCs what it sends to W&B (train.py:1342-1343).
+    ``normaliser``: a gipvit.stainnorm.SlideNormaliser over ``runner`` (``--stain-normalize``): every chunk is announced to it
+    before the runner sees it -- a slide begins behind the previous ``Is Last Batch`` -- and with ``extract_features`` the slide's
+    estimate is written to ``<out_dir>/<slide>_stain.pt`` (HE, maxC, n_tissue, on, reason) next to the features."""
     log = log or _logger
     dev = runner.dev
     C = runner.C
@@ -74,11 +77,16 @@ def validate(runner, loader, *, extract_features: bool = False, extract_attentio
         loader.reset_counter()                                              # train.py:932
     if extract_features and primary:
         os.makedirs(out_dir, exist_ok=True)
+    first_of_slide = True
     for batch_idx, mb in enumerate(loader):
         data = mb["Data"]
         if data.dim() == 5:
             data = data.squeeze(0)                                          # batch_size=1 loader, train.py:1211
         data = data.to(dev, non_blocking=True)
+        if normaliser is not None:
+            name = mb.get("Slide Filename", "") if first_of_slide else ""
+            normaliser.begin(data, first_of_slide, name=str(name[0] if isinstance(name, (list, tuple)) else name))
+            first_of_slide = bool(mb["Is Last Batch"])
         n = data.shape[0]
         label = int(mb["Label"].reshape(-1)[0])
         if extract_attention:
@@ -115,6 +123,8 @@ def validate(runner, loader, *, extract_features: bool = False, extract_attentio
                         torch.save(f, path)
                     if extract_attention:
                         torch.save(torch.cat(cur_attn), os.path.join(out_dir, f"{name}_attention.pt"))
+                    if normaliser is not None:
+                        torch.save(normaliser.state(), os.path.join(out_dir, f"{name}_stain.pt"))
                 cur_feat, cur_attn = [], []
             else:
                 so, st = np.concatenate(cur_out), np.concatenate(cur_tgt)
@@ -126,6 +136,8 @@ def validate(runner, loader, *, extract_features: bool = False, extract_attentio
             log.info("Test{}: [{:>4d}]  Time: {:.3f}  Loss: {:>7.4f} ({:>6.4f})  Acc@1: {:>7.4f} ({:>7.4f})  Acc@5: {:>7.4f} ({:>7.4f})".format(
                 log_suffix, batch_idx, batch_time, float(loss_buf), loss_sum / max(n_seen, 1), a1, top1_sum / max(n_seen, 1), a5,
                 top5_sum / max(n_seen, 1)))
+    if normaliser is not None:
+        normaliser.end()
     metrics = OrderedDict()
     if extract_features:
         metrics["slides"] = float(slide_num)

@@ -232,6 +232,89 @@ typedef struct {
 } gv_crop_augment_stain_args;
 int gv_crop_augment_stain(const gv_crop_augment_stain_args* a, void* stream);
 
+/* ---- Macenko stain normalisation at inference (Macenko et al., ISBI 2009; absent from the reference).  Per slide, from a
+ * sample of its tiles (u8 NHWC, already cut to the window the encoder sees), the slide's own haematoxylin / eosin vectors
+ * HE [3][2] and their 99th-percentile concentrations maxC [2] are estimated and the slide is mapped onto a fixed target
+ * (HE_t, maxC_t).  Optical density is this library's, od_c = -ln((v_c + 1) / 256), NOT the -ln(v / 240) of the usual scripts:
+ * a slide whose estimate equals the target maps onto itself.  The map is linear in od,
+ *     od' = od . A,   A = (HE_t diag(maxC_t / maxC) pinv(HE))^T   (fp64, rounded to f32; b = 0, on = 1)
+ * i.e. one gv_stain_params record per slide, evaluated exactly as the crop pass evaluates a jitter record.  The estimate
+ * (gipvit.stainnorm restates it in fp64 numpy) takes three passes over the sample with small host steps between them:
+ *   tissue mask   pixel p is tissue iff all three bytes are <= v_max, v_max = floor(256 exp(-beta)) - 1 (beta = 0.15: 219);
+ *                 an integer test, no floating-point comparison on the device
+ *   pass 1        gv_stain_stats over tissue pixels: the count n, sum od (3) and sum od_i od_j (6, upper triangle), fp64.
+ *                 Host: covariance (S2 - n mu mu^T) / (n - 1), eigh, the two leading eigenvectors V [3][2] (largest first,
+ *                 each flipped so that its component sum is >= 0)
+ *   pass 2        gv_stain_angle_hist over tissue pixels: t = od . V, phi = atan2(t1, t0), bin floor((phi + pi) NB / 2 pi)
+ *                 clamped to [0, NB).  Host: phi_lo / phi_hi = the alpha-th / (100 - alpha)-th percentile of the histogram,
+ *                 v = V (cos phi, sin phi); the vector with the larger first component is H, the other E
+ *   pass 3        gv_stain_conc_hist over ALL pixels: c = pinv(HE) od, one histogram per stain over [0, cmax_k),
+ *                 cmax_k = ln 256 * sum_j max(pinv_kj, 0) (an upper bound: od >= 0; a value past it lands in the last
+ *                 bin); c_k < 0 goes to an underflow count that still counts for the rank.  Host: maxC_k = the 99th percentile
+ * A percentile read from a histogram has the resolution of one bin width.  All three passes compute in fp64 from a per-block
+ * table of the 256 od values and share one launch shape: G = clamp(ceil(n h w / 256), 1, 512) workgroups -- a function of the
+ * shape only, never of the device -- write per-workgroup partials into `workspace`, a second launch sums them in a fixed
+ * order.  No floating-point atomic anywhere (histogram bins are integer adds in LDS): results are bitwise the same run to run
+ * and box to box.  workspace bytes:  gv_stain_stats G * 80;  gv_stain_angle_hist G * NB * 4;  gv_stain_conc_hist
+ * G * 2 * (NB + 1) * 4.  Refused before any launch: a null pointer (GV_E_NULL), tiles-independent pointers not 8-byte aligned
+ * (GV_E_ALIGN), NB outside 256 .. 4096, v_max outside 0 .. 255, n h w >= 2^32 or img_stride < h w 3 (GV_E_SHAPE).         */
+typedef struct {
+    const uint8_t* tiles;        /* [n, h, w, 3] u8 (NHWC), img_stride bytes between tiles                      */
+    int64_t img_stride;
+    int32_t n, h, w;
+    int32_t v_max;               /* tissue: every byte <= v_max                                                 */
+    void* workspace;             /* 8-byte aligned, see above                                                   */
+    void* out;                   /* 8-byte aligned: uint64 n, then f64 {s_r, s_g, s_b, s_rr, s_rg, s_rb, s_gg, s_gb, s_bb} */
+} gv_stain_stats_args;
+int gv_stain_stats(const gv_stain_stats_args* a, void* stream);
+typedef struct {
+    const uint8_t* tiles;
+    int64_t img_stride;
+    int32_t n, h, w;
+    int32_t v_max;
+    int32_t n_bins;              /* NB                                                                          */
+    double V[6];                 /* row-major [3][2]                                                            */
+    void* workspace;
+    int64_t* out;                /* [NB] counts, 8-byte aligned                                                 */
+} gv_stain_angle_hist_args;
+int gv_stain_angle_hist(const gv_stain_angle_hist_args* a, void* stream);
+typedef struct {
+    const uint8_t* tiles;
+    int64_t img_stride;
+    int32_t n, h, w;
+    int32_t n_bins;              /* NB                                                                          */
+    double pinv[6];              /* row-major [2][3]: pinv(HE)                                                  */
+    double cmax[2];              /* > 0                                                                         */
+    void* workspace;
+    int64_t* out;                /* [2][NB + 1]: stain k's bins, then its underflow count; 8-byte aligned       */
+} gv_stain_conc_hist_args;
+int gv_stain_conc_hist(const gv_stain_conc_hist_args* a, void* stream);
+
+/* ---- gv_stain_apply: u8 tiles -> u8 tiles through one gv_stain_params record per tile (what a pathologist looks at for QA).
+ * Every pixel goes through the crop pass's own function (csrc/stain_px.h); a tile whose record has on = 0 is copied bit for
+ * bit.  out is contiguous [n, h, w, 3] and must not overlap tiles' other tiles (in place, out == tiles with the same stride,
+ * is fine: a pixel depends on itself only).  n <= 65535.                                                                    */
+typedef struct {
+    const uint8_t* tiles;        /* [n, h, w, 3] u8 (NHWC), img_stride bytes between tiles                      */
+    uint8_t* out;                /* [n, h, w, 3] u8, contiguous                                                 */
+    const gv_stain_params* stain; /* device [n], 4-byte aligned                                                 */
+    int64_t img_stride;
+    int32_t n, h, w;
+} gv_stain_apply_args;
+int gv_stain_apply(const gv_stain_apply_args* a, void* stream);
+
+/* ---- gv_patchify_stain: gv_patchify with the stain map inside the same pass (no extra pass over the pixels).  The bytes of
+ * tile t go through record stain[t] first (the same function as gv_stain_apply), then through the n(tile, y, x, c) of the plain
+ * kernel computed from the stained BYTE, `fill` applied after the stain as it is applied after Normalize: the rows are
+ * bit-identical to gv_patchify over gv_stain_apply's output.  A workgroup none of whose tiles has on != 0 builds no table and
+ * evaluates no exponential.  No mix / erase combination (those are training tables), no NCHW form.  Checks as gv_patchify,
+ * plus: a null table GV_E_NULL, a table that is not 4-byte aligned GV_E_ALIGN.                                              */
+typedef struct {
+    gv_patchify_args p;
+    const gv_stain_params* stain; /* device [p.n_tiles], 4-byte aligned                                         */
+} gv_patchify_stain_args;
+int gv_patchify_stain(const gv_patchify_stain_args* a, void* stream);
+
 /* ---- tile augmentation on the device (replaces the CPU / PIL recipes of transformations.py:131-197 on tiles that are
  * already in HBM).  One parameter record per tile, drawn on the host; operations in reference order:
  *   colour ops in `order` (0 brightness, 1 contrast, 2 saturation, 3 hue: torchvision ColorJitter on PIL images, PIL's
@@ -842,6 +925,7 @@ int gv_patchify_nchw_f32(const gv_patchify_nchw_args* a, void* stream);    /* ex
 int gv_patchify_mix_f32(const gv_patchify_mix_args* a, void* stream);
 int gv_patchify_nchw_mix_f32(const gv_patchify_nchw_mix_args* a, void* stream);
 int gv_patchify_erase_f32(const gv_patchify_erase_args* a, void* stream);
+int gv_patchify_stain_f32(const gv_patchify_stain_args* a, void* stream);
 int gv_patchify_nchw_erase_f32(const gv_patchify_nchw_erase_args* a, void* stream);
 int gv_tokens_bwd_f32(const gv_tokens_bwd_args* a, void* stream);
 int gv_token_mean_bwd_f32(const gv_token_mean_bwd_args* a, void* stream);      /* gb f32 */

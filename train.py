@@ -92,6 +92,13 @@ def build_parser():
                    "in optical-density space on every crop, in the same pass (gv_crop_augment_stain): per stain (haematoxylin, eosin, residual) "
                    "alpha ~ U(1 - SIGMA, 1 + SIGMA), beta ~ U(-SIGMA, SIGMA); 0 = off, Tellez et al. use 0.05 (light) and 0.2 (strong)")
     g.add_argument("--stain-prob", type=float, default=1.0, metavar="P", help="--stain-jitter: probability that a crop is jittered, 0 < P <= 1")
+    g.add_argument("--stain-normalize", type=str, default="none", metavar="{none,macenko}", help="stain normalisation of every INFERENCE pass of the run "
+                   "(validation, --extract_features, the k-NN / linear / MIL monitors' bank and query passes): per slide, Macenko's H&E vectors and "
+                   "99th-percentile concentrations are estimated on the device from the slide's first chunk and the slide is mapped onto Macenko's "
+                   "reference inside the patchify pass (gv_patchify_stain).  Training batches are never normalised")
+    g.add_argument("--stain-norm-tiles", type=int, default=0, metavar="K", help="--stain-normalize: estimate from the first K tiles of a slide's first chunk (0 = the whole chunk)")
+    g.add_argument("--stain-norm-beta", type=float, default=0.15, help="--stain-normalize: od threshold of the tissue mask, in (0, ln 256)")
+    g.add_argument("--stain-norm-alpha", type=float, default=1.0, help="--stain-normalize: the angle percentiles are alpha and 100 - alpha, alpha in (0, 50)")
     g.add_argument("--global-crops-scale", type=float, nargs=2, default=(0.4, 1.0))
     g.add_argument("--local-crops-scale", type=float, nargs=2, default=(0.05, 0.4))
     g.add_argument("--momentum-teacher", type=float, default=0.996)
@@ -431,6 +438,18 @@ ATTN_STREAM_MAX_TOKENS = 1040   # gv_attention_fwd_stream: forward only
 ATTN_F32_MAX_TOKENS = 260       # the fp32 operand mode's attention
 
 
+def check_stain_normalize(args):
+    """--stain-normalize and its options, refused before any GPU work (main calls this ahead of the device check)."""
+    if args.stain_normalize not in ("none", "macenko"):
+        raise SystemExit(f"--stain-normalize {args.stain_normalize}: 'none' or 'macenko' (Vahadane is not built)")
+    if not (math.isfinite(args.stain_norm_beta) and 0 < args.stain_norm_beta < math.log(256.0)):
+        raise SystemExit(f"--stain-norm-beta {args.stain_norm_beta}: the od threshold of the tissue mask must be in (0, ln 256)")
+    if not (math.isfinite(args.stain_norm_alpha) and 0 < args.stain_norm_alpha < 50):
+        raise SystemExit(f"--stain-norm-alpha {args.stain_norm_alpha}: the angle percentile must be in (0, 50)")
+    if args.stain_norm_tiles < 0:
+        raise SystemExit(f"--stain-norm-tiles {args.stain_norm_tiles}: K >= 0 (0 = the whole first chunk of a slide)")
+
+
 def check_token_limits(args):
     """Image sizes against the attention kernels' sequence limits, before any device work: a run that TRAINS needs every crop within
     288 tokens (256 px at patch 16); --extract_features on the supervised route is forward-only and goes up to 512 px
@@ -584,7 +603,11 @@ def main(argv=None, transform=None):
     args, args_text = parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     check_token_limits(args)
+    check_stain_normalize(args)
     hook_format = hook_batch_format(args, transform, argv) if transform is not None else None
+    if args.stain_normalize != "none" and hook_format == "f32_nchw":
+        raise SystemExit("--stain-normalize: the transform hook returns float32 [3, H, W] images (already normalised); the stain estimate "
+                         "and the map work on uint8 tiles -- return uint8 [H, W, 3] tiles from the hook or drop the flag")
     if not torch.cuda.is_available() or not str(args.device).startswith("cuda"):
         raise SystemExit("train.py: an MI355X is required (device=%s, cuda available=%s); the HIP hot path has no CPU fallback"
                          % (args.device, torch.cuda.is_available()))
@@ -772,21 +795,35 @@ def main(argv=None, transform=None):
     knn_names, probe_names, mil_names = [], [], []
     if want_knn or want_probe or want_mil:        # the teacher backbone at its own image size; larger tiles contribute their centred window (gipvit/knn.py)
         knn_runner = FeatureExtractor(arch, img, eval_B, 0, mean, std, dev, weights=Weights(eng.arena, "backbone.", teacher=True, fp32=args.precision == "fp32"))
+    # --stain-normalize: one SlideNormaliser per forward-only runner (nothing is built without the flag); the training engines never normalise
+    stain_norm = {}
+    if args.stain_normalize == "macenko":
+        from gipvit.stainnorm import MacenkoEstimator, SlideNormaliser
+        estimator = MacenkoEstimator(dev, beta=args.stain_norm_beta, alpha=args.stain_norm_alpha, max_tiles=args.stain_norm_tiles)
+        for key, r in (("val", runner), ("ema", runner_ema), ("mon", knn_runner if (want_knn or want_probe or want_mil) else None)):
+            if r is not None:
+                stain_norm[key] = SlideNormaliser(r, estimator, primary=primary)
+        if primary:
+            _logger.info("stain normalisation: macenko (beta %.3g alpha %.3g, %s of a slide's first chunk) on every inference pass%s; "
+                         "training batches are not normalised", args.stain_norm_beta, args.stain_norm_alpha,
+                         f"the first {args.stain_norm_tiles} tiles" if args.stain_norm_tiles else "every tile",
+                         "" if stain_norm else " (this run has none)")
+    mon_norm = {"normaliser": stain_norm["mon"]} if "mon" in stain_norm else {}      # the keyword exists with the flag only
     if want_knn:
         from gipvit.knn import KnnMonitor
-        monitor = KnnMonitor(knn_runner, k=args.knn_k, temp=args.knn_temp, num_classes=args.num_classes or 2, primary=primary)
+        monitor = KnnMonitor(knn_runner, k=args.knn_k, temp=args.knn_temp, num_classes=args.num_classes or 2, primary=primary, **mon_norm)
         knn_names = ["knn_top1"] + (["knn_auc_per_patch", "knn_auc_per_slide"] if monitor.C > 1 else [])
     if want_probe:      # heads on the same runner's last-layer CLS tokens (gipvit/linprobe.py)
         from gipvit.linprobe import LinearProbe
         probe = LinearProbe(knn_runner, num_classes=args.num_classes or 2, lrs=args.linprobe_lrs, weight_decay=args.linprobe_wd,
                             epochs=args.linprobe_epochs, batch=args.linprobe_batch, n_last=args.linprobe_layers, avgpool=args.linprobe_avgpool,
-                            holdout=args.linprobe_holdout, seed=args.seed, primary=primary)
+                            holdout=args.linprobe_holdout, seed=args.seed, primary=primary, **mon_norm)
         probe_names = ["linear_top1", "linear_loss"] + (["linear_auc_per_patch", "linear_auc_per_slide"] if probe.C > 1 else [])
 
     if want_mil:        # slide-level ABMIL on the same runner's CLS tokens, one bag per slide (gipvit/mil.py)
         from gipvit.mil import MilProbe
         mil = MilProbe(knn_runner, num_classes=args.num_classes or 2, hidden=args.mil_hidden, lr=args.mil_lr, weight_decay=args.mil_wd,
-                       epochs=args.mil_epochs, batch=args.mil_batch, n_last=args.mil_layers, seed=args.seed, primary=primary)
+                       epochs=args.mil_epochs, batch=args.mil_batch, n_last=args.mil_layers, seed=args.seed, primary=primary, **mon_norm)
         mil_names = ["mil_top1", "mil_loss"] + (["mil_auc_per_slide"] if mil.C > 1 else [])
     any_monitor = monitor is not None or probe is not None or mil is not None
 
@@ -956,10 +993,11 @@ def main(argv=None, transform=None):
         if runner is not None:
             eval_metrics = validate(runner, inf_loader, extract_features=bool(args.extract_features),
                                     extract_attention=bool(args.extract_attention), smoothing=args.smoothing,
-                                    log_interval=args.log_interval, out_dir=args.features_dir, primary=primary)
+                                    log_interval=args.log_interval, out_dir=args.features_dir, primary=primary,
+                                    **({"normaliser": stain_norm["val"]} if "val" in stain_norm else {}))
             if runner_ema is not None and not args.extract_features:       # train.py:943-955: the EMA model's metrics win
                 eval_metrics = validate(runner_ema, inf_loader, smoothing=args.smoothing, log_interval=args.log_interval, primary=primary,
-                                        log_suffix=" (EMA)")
+                                        log_suffix=" (EMA)", **({"normaliser": stain_norm["ema"]} if "ema" in stain_norm else {}))
         if monitor is not None:
             if (epoch + 1) % args.knn_rate == 0:                # the teacher moved: the bank is rebuilt at every evaluation
                 monitor.build_bank(knn_bank_loader)
