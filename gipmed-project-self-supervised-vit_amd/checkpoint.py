@@ -60,8 +60,18 @@ class CheckpointSaver:
 
 # --------------------------------------------------------------------------- #
 # the host-side draw streams of a run (dropout step seeds, crop boxes, view augmentation, mixup, erasing, iBOT masks,
-# stochastic depth): every rank has its own, seeded from (seed, rank), and a checkpoint holds every rank's position
+# stochastic depth): every rank has its own, seeded from (seed, rank) by the table below -- stream -> (rank multiplier, offset), for the
+# samplers and a re-seeding resume alike ("drop_path": the DropPathSampler's) --, and a checkpoint holds every rank's position
 # --------------------------------------------------------------------------- #
+HOST_STREAMS = {"crops": (1, 0), "drop": (7919, 11), "views": (53, 5), "stain": (313, 41), "mix": (101, 23), "erase": (211, 37),
+                "ibot": (101, 3), "drop_path": (17, 0)}
+
+
+def stream_seed(name: str, seed: int, rank: int) -> int:
+    mul, off = HOST_STREAMS[name]
+    return seed + mul * rank + off
+
+
 def _stream_states(streams) -> dict:
     import json
     return {k: json.dumps(g.bit_generator.state) for k, g in streams.items() if g is not None}

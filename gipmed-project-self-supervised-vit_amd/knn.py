@@ -95,9 +95,36 @@ def collect_features(loader, C: int, features, who: str, normaliser=None):
     return torch.cat(feats), np.concatenate(labels), np.concatenate(slides), skipped
 
 
-class KnnMonitor:
+class FeatureMonitor:
+    """What the k-NN monitor, the linear probe (gipvit/linprobe.py) and the MIL probe (gipvit/mil.py) share; ``fit(bank)`` then ``evaluate(queries)``."""
+    prefix, metrics, auc_metrics = "", (), ()   # metric names = prefix + each of: always reported / with more than one class only
+    lower_is_better, avgpool = (), False        # those of ``metrics`` where the lower value is the better one; probe_features' pooled vector
+
+    def __init__(self, runner, num_classes: int, primary: bool, log: Optional[logging.Logger], normaliser):
+        if not 1 <= num_classes <= 32:
+            raise ValueError(f"{type(self).__name__}: num_classes must be in 1..32 (got {num_classes})")
+        self.runner, self.C, self.primary, self.log, self.normaliser = runner, num_classes, primary, log or _logger, normaliser
+
+    def metric_names(self):
+        return [self.prefix + m for m in self.metrics + (self.auc_metrics if self.C > 1 else ())]
+
+    def _chunk(self, data: torch.Tensor) -> torch.Tensor:      # one chunk of tiles as the runner takes it
+        if data.dim() == 5:
+            data = data.squeeze(0)
+        return centred_window(data.to(self.runner.dev, non_blocking=True), self.runner.img)
+
+    def features(self, data: torch.Tensor) -> torch.Tensor:
+        """f32 [n, F] probe features of one chunk of tiles, on the device."""
+        return self.runner.probe_features(self._chunk(data), self.n_last, self.avgpool)
+
+    def _collect(self, loader):
+        return collect_features(loader, self.C, self.features, type(self).__name__, normaliser=self.normaliser)
+
+
+class KnnMonitor(FeatureMonitor):
     """``runner``: an ``engine.FeatureExtractor`` (``run(tiles) -> (features f32 [n, D], logits)``).  ``build_bank(loader)`` then
     ``evaluate(loader)``; loaders are ``data.InferTiles`` / ``data.SyntheticSlides``."""
+    prefix, metrics, auc_metrics = "knn_", ("top1",), ("auc_per_patch", "auc_per_slide")
 
     def __init__(self, runner, k: int = 20, temp: float = 0.07, num_classes: int = 2, primary: bool = True, log: Optional[logging.Logger] = None,
                  normaliser=None):
@@ -105,28 +132,17 @@ class KnnMonitor:
             raise ValueError(f"KnnMonitor: k must be in 1..64 (got {k})")
         if not temp > 0:
             raise ValueError(f"KnnMonitor: temp must be > 0 (got {temp})")
-        if not 1 <= num_classes <= 32:
-            raise ValueError(f"KnnMonitor: num_classes must be in 1..32 (got {num_classes})")
-        self.runner, self.k, self.temp, self.C, self.primary, self.log = runner, k, temp, num_classes, primary, log or _logger
+        super().__init__(runner, num_classes, primary, log, normaliser)
+        self.k, self.temp = k, temp
         self.bank = self.bank_labels = None
-        self.normaliser = normaliser                     # gipvit.stainnorm.SlideNormaliser over ``runner``, or None
-
-    def _window(self, data: torch.Tensor) -> torch.Tensor:
-        return centred_window(data, self.runner.img)
 
     def features(self, data: torch.Tensor) -> torch.Tensor:
         """L2-normalised f32 [n, D] CLS features of one chunk of tiles, on the device."""
-        if data.dim() == 5:
-            data = data.squeeze(0)
-        data = self._window(data.to(self.runner.dev, non_blocking=True))
-        feats, _ = self.runner.run(data)
+        feats, _ = self.runner.run(self._chunk(data))
         n, D = feats.shape
         out = torch.empty_like(feats)
         ops.l2norm_fwd(feats, out, torch.empty(n, dtype=f32, device=feats.device), n, D)
         return out
-
-    def _collect(self, loader):
-        return collect_features(loader, self.C, self.features, "KnnMonitor", normaliser=self.normaliser)
 
     def build_bank(self, loader) -> int:
         feats, labels, slides, skipped = self._collect(loader)
@@ -136,6 +152,8 @@ class KnnMonitor:
             self.log.info("k-NN monitor: bank of %d tiles from %d slides (%d slides left out: label outside [0, %d))",
                           feats.shape[0], len(np.unique(slides)), skipped, self.C)
         return feats.shape[0]
+
+    fit = build_bank                # the teacher moved: the bank is rebuilt at every evaluation
 
     def evaluate(self, loader) -> "OrderedDict[str, float]":
         if self.bank is None:

@@ -20,11 +20,10 @@ import numpy as np
 import torch
 
 from . import ops
-from .knn import centred_window, collect_features, tile_slide_metrics
+from .knn import FeatureMonitor, tile_slide_metrics
 
-_logger = logging.getLogger("train")
 f32 = torch.float32
-MAX_HEAD_COLUMNS, MAX_FEATURES, MAX_BATCH, MAX_CLASSES = 64, 4096, 4096, 32      # gv_linprobe_train's limits (include/gipvit.h)
+MAX_HEAD_COLUMNS, MAX_FEATURES, MAX_BATCH = 64, 4096, 4096      # gv_linprobe_train's limits (include/gipvit.h)
 MOMENTUM, INIT_STD = 0.9, 0.01
 
 
@@ -79,16 +78,16 @@ def probe_metrics(prob: np.ndarray, labels: np.ndarray, slide_ids, loss: float) 
     return out
 
 
-class LinearProbe:
+class LinearProbe(FeatureMonitor):
     """``runner``: an ``engine.FeatureExtractor`` of a CLS-token model.  ``fit(bank_loader)`` then ``evaluate(query_loader)``;
     loaders are ``data.InferTiles`` / ``data.SyntheticSlides``.  ``state_dict(head)`` hands a head out as nn.Linear's."""
+    prefix, metrics, auc_metrics, lower_is_better = "linear_", ("top1", "loss"), ("auc_per_patch", "auc_per_slide"), ("loss",)
 
     def __init__(self, runner, num_classes: int = 2, lrs: Sequence[float] = (0.001,), weight_decay: float = 0.0, epochs: int = 100,
                  batch: int = 1024, n_last: int = 4, avgpool: bool = False, holdout: float = 0.2, seed: int = 0, primary: bool = True,
                  log: Optional[logging.Logger] = None, normaliser=None):
         lrs = tuple(float(v) for v in lrs)
-        if not 1 <= num_classes <= MAX_CLASSES:
-            raise ValueError(f"LinearProbe: num_classes must be in 1..{MAX_CLASSES} (got {num_classes})")
+        super().__init__(runner, num_classes, primary, log, normaliser)
         if not lrs or not all(math.isfinite(v) and v > 0 for v in lrs):
             raise ValueError(f"LinearProbe: lrs must be a non-empty list of positive finite rates (got {lrs})")
         if len(lrs) * num_classes > MAX_HEAD_COLUMNS:
@@ -104,23 +103,12 @@ class LinearProbe:
         if self.F > MAX_FEATURES:
             raise ValueError(f"LinearProbe: {self.F} features per tile ({n_last} layers{' + the pooled vector' if avgpool else ''} of width "
                              f"{runner.D}) is past the kernel's {MAX_FEATURES}")
-        self.runner, self.C, self.lrs, self.wd, self.epochs, self.batch = runner, num_classes, lrs, float(weight_decay), epochs, batch
-        self.n_last, self.avgpool, self.holdout, self.seed, self.primary, self.log = n_last, bool(avgpool), holdout, seed, primary, log or _logger
+        self.lrs, self.wd, self.epochs, self.batch = lrs, float(weight_decay), epochs, batch
+        self.n_last, self.avgpool, self.holdout, self.seed = n_last, bool(avgpool), holdout, seed
         self.H = len(lrs)
         self.W = self.b = None
         self.head = 0
         self.selection_loss = self.train_loss = None
-        self.normaliser = normaliser                     # gipvit.stainnorm.SlideNormaliser over ``runner``, or None
-
-    def features(self, data: torch.Tensor) -> torch.Tensor:
-        """f32 [n, F] probe features of one chunk of tiles, on the device."""
-        if data.dim() == 5:
-            data = data.squeeze(0)
-        data = centred_window(data.to(self.runner.dev, non_blocking=True), self.runner.img)
-        return self.runner.probe_features(data, self.n_last, self.avgpool)
-
-    def _collect(self, loader):
-        return collect_features(loader, self.C, self.features, "LinearProbe", normaliser=self.normaliser)
 
     def fit(self, bank_loader) -> int:
         """Train every head on the bank (minus the held-out slides when there is more than one head) and choose the head to

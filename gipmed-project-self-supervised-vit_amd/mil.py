@@ -18,13 +18,12 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .knn import centred_window, collect_features
+from .knn import FeatureMonitor
 from .linprobe import epoch_permutations, lr_scale_at
 from .validate import _auc
 
-_logger = logging.getLogger("train")
 f32 = torch.float32
-MAX_FEATURES, MAX_HIDDEN, MAX_CLASSES, MAX_BATCH, MAX_BAG = 4096, 256, 32, 64, 4096      # gv_mil_train's limits (include/gipvit.h)
+MAX_FEATURES, MAX_HIDDEN, MAX_BATCH, MAX_BAG = 4096, 256, 64, 4096      # gv_mil_train's limits (include/gipvit.h)
 BETA1, BETA2, EPS = 0.9, 0.999, 1e-8
 
 
@@ -80,16 +79,16 @@ def mil_metrics(prob: np.ndarray, labels: np.ndarray, loss: float) -> "OrderedDi
     return out
 
 
-class MilProbe:
+class MilProbe(FeatureMonitor):
     """``runner``: an ``engine.FeatureExtractor`` of a CLS-token model.  ``fit(bank_loader)`` then ``evaluate(query_loader)``;
     loaders are ``data.InferTiles`` / ``data.SyntheticSlides``.  ``train(feats, bag_ptr, labels)`` is the device run on its own:
     features read back from <slide>_features.pt files train without an encoder (``runner`` may then be None with ``features=F``)."""
+    prefix, metrics, auc_metrics, lower_is_better = "mil_", ("top1", "loss"), ("auc_per_slide",), ("loss",)
 
     def __init__(self, runner, num_classes: int = 2, hidden: int = 128, lr: float = 5e-4, weight_decay: float = 1e-4, epochs: int = 50,
                  batch: int = 8, n_last: int = 1, seed: int = 0, primary: bool = True, log: Optional[logging.Logger] = None,
                  features: Optional[int] = None, normaliser=None):
-        if not 1 <= num_classes <= MAX_CLASSES:
-            raise ValueError(f"MilProbe: num_classes must be in 1..{MAX_CLASSES} (got {num_classes})")
+        super().__init__(runner, num_classes, primary, log, normaliser)
         if hidden % 16 or not 16 <= hidden <= MAX_HIDDEN:
             raise ValueError(f"MilProbe: hidden must be a multiple of 16 in 16..{MAX_HIDDEN} (got {hidden})")
         if not (math.isfinite(lr) and lr > 0) or not weight_decay >= 0:
@@ -107,22 +106,14 @@ class MilProbe:
             self.F = int(features)
         if self.F % 4 or not 4 <= self.F <= MAX_FEATURES:
             raise ValueError(f"MilProbe: {self.F} features per tile; the kernels take a multiple of 4 in 4..{MAX_FEATURES}")
-        self.runner, self.C, self.L, self.lr, self.wd, self.epochs, self.batch = runner, num_classes, hidden, float(lr), float(weight_decay), epochs, batch
-        self.n_last, self.seed, self.primary, self.log = n_last, seed, primary, log or _logger
+        self.L, self.lr, self.wd, self.epochs, self.batch = hidden, float(lr), float(weight_decay), epochs, batch
+        self.n_last, self.seed = n_last, seed
         self.params = None
         self.train_loss = None
-        self.normaliser = normaliser                     # gipvit.stainnorm.SlideNormaliser over ``runner``, or None
-
-    def features(self, data: torch.Tensor) -> torch.Tensor:
-        """f32 [n, F] probe features of one chunk of tiles, on the device."""
-        if data.dim() == 5:
-            data = data.squeeze(0)
-        data = centred_window(data.to(self.runner.dev, non_blocking=True), self.runner.img)
-        return self.runner.probe_features(data, self.n_last, False)
 
     def _collect(self, loader):
         """-> (features f32 [N, F] device, bag_ptr int32 [n + 1], slide labels int64 [n], slides left out)."""
-        feats, labels, slides, skipped = collect_features(loader, self.C, self.features, "MilProbe", normaliser=self.normaliser)
+        feats, labels, slides, skipped = super()._collect(loader)
         ptr = bag_table(slides)
         return feats, ptr, labels[ptr[:-1]], skipped
 

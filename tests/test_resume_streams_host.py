@@ -1,10 +1,9 @@
 """CPU: the host-side draw streams of a data-parallel run across a resume (checkpoint.pack_host_rng / restore_host_rng), and
 the refusals of dist.reduction_plan / dist.comm_setup.
 
-Every rank seeds its own streams (the driver's seeds: seed + rank for the crop boxes, + 101 rank + 3 for the iBOT masks,
-+ 7919 rank + 11 for the dropout step seeds, + 17 rank for stochastic depth).  A checkpoint is written by rank 0 alone, so
-before ``host_rng_ranks`` existed it held rank 0's positions only and a resumed world > 1 run restored them on EVERY rank:
-from then on all ranks drew the same boxes, masks and seeds."""
+Every rank seeds its own streams (the driver's seeds: checkpoint.HOST_STREAMS through checkpoint.stream_seed).  A checkpoint
+is written by rank 0 alone, so before ``host_rng_ranks`` existed it held rank 0's positions only and a resumed world > 1 run
+restored them on EVERY rank: from then on all ranks drew the same boxes, masks and seeds."""
 import json
 import os
 import sys
@@ -18,14 +17,15 @@ SEED = 42
 
 
 class Rank:
-    """One rank's host draw streams, built and seeded as train.py builds them."""
+    """One rank's host draw streams, built as train.py builds them and seeded from the same table."""
 
     def __init__(self, rank):
+        from gipvit.checkpoint import stream_seed
         from gipvit.droppath import DropPathSampler
         from gipvit.masking import MaskSampler
         from gipvit.multicrop import MultiCropSampler
         self.rank = rank
-        self.seeds = {"drop": SEED + 7919 * rank + 11, "crops": SEED + rank, "ibot": SEED + 101 * rank + 3, "drop_path": SEED + 17 * rank}
+        self.seeds = {k: stream_seed(k, SEED, rank) for k in ("drop", "crops", "ibot", "drop_path")}
         self.crops = MultiCropSampler(2, 256, 2, 3, seed=self.seeds["crops"])
         self.masks = MaskSampler(14, 4, (0.1, 0.5), 0.5, seed=self.seeds["ibot"])
         self.drop = np.random.default_rng(self.seeds["drop"])
@@ -213,28 +213,65 @@ def test_pack_gathers_over_gloo_with_two_processes():
         assert [x.tolist() for x in r.draw()] == res[rank][2]
 
 
+def _pack_sites(src):
+    """-> (line numbers of the pack_host_rng calls reachable from ``main``, those of them under a gate, the functions entered).  The
+    walk starts at ``main`` and follows its calls into the module's own functions, carrying the gate of the call site along.  A gate
+    is an ``if`` (either branch) whose test names ``saver`` / ``primary``, bare or as an attribute (``run.saver``, ``ctx.primary``),
+    and everything in a block behind such an ``if`` that can leave the block (return / break / continue / raise)."""
+    import ast
+    funcs = {n.name: n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef)}
+    gated, calls, entered = set(), [], {"main"}
+    is_gate = lambda test: any((isinstance(n, ast.Name) and n.id in ("saver", "primary")) or (isinstance(n, ast.Attribute) and n.attr in ("saver", "primary"))
+                               for n in ast.walk(test))
+    leaves = lambda st: any(isinstance(n, (ast.Return, ast.Break, ast.Continue, ast.Raise)) for n in ast.walk(st))
+
+    def walk(node, g):
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Name):
+            if node.func.id == "pack_host_rng":
+                calls.append(node.lineno)
+                if g:
+                    gated.add(node.lineno)
+            elif node.func.id in funcs and node.func.id not in entered:
+                entered.add(node.func.id)
+                walk(funcs[node.func.id], g)
+        for field, value in ast.iter_fields(node):
+            if isinstance(value, list) and value and isinstance(value[0], ast.stmt):
+                gg = g or (isinstance(node, ast.If) and is_gate(node.test))
+                for st in value:
+                    walk(st, gg)
+                    gg = gg or (isinstance(st, ast.If) and is_gate(st.test) and leaves(st))
+            else:
+                for ch in (value if isinstance(value, list) else [value]):
+                    if isinstance(ch, ast.AST):
+                        walk(ch, g or (isinstance(node, ast.If) and field != "test" and is_gate(node.test)))
+    walk(funcs["main"], False)
+    return calls, gated, entered
+
+
 def test_driver_packs_on_every_rank_and_writes_on_the_primary():
     """train.py: pack_host_rng (a collective at world > 1) is called outside every ``saver is not None`` / ``primary`` gate, at both
-    save points, and the old rank-0-only restore is gone."""
-    import ast
+    save points, and the old rank-0-only restore is gone.  The save points sit in the stages ``main`` calls; the walk follows it there."""
     src = open(os.path.join(ROOT, "train.py")).read()
-    tree = ast.parse(src)
-    main = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "main")
-    gated, calls = set(), []
-
-    def walk(node, under_gate):
-        for ch in ast.iter_child_nodes(node):
-            g = under_gate
-            if isinstance(node, ast.If) and ch in node.body and any(isinstance(n, ast.Name) and n.id in ("saver", "primary") for n in ast.walk(node.test)):
-                g = True
-            if isinstance(ch, ast.Call) and isinstance(ch.func, ast.Name) and ch.func.id == "pack_host_rng":
-                calls.append(ch.lineno)
-                if g:
-                    gated.add(ch.lineno)
-            walk(ch, g)
-    walk(main, False)
+    calls, gated, entered = _pack_sites(src)
     assert len(calls) == 2 and not gated, (calls, gated)
+    assert {"train_epoch", "end_of_epoch"} <= entered
     assert "restore_host_rng(ck," in src and 'ck["host_rng"]' not in src and 'ck.get("drop_path_rng")' not in src
+    # the walk sees every form of the gate: attribute tests, a gated call site of the stage, an early return ahead of the call
+    stage = "def main():\n    stage(run)\n\n\ndef stage(run):\n"
+    for body in ("    if run.saver is not None:\n        x = pack_host_rng(s, d, g)\n", "    if ctx.primary:\n        x = pack_host_rng(s, d, g)\n",
+                 "    if saver is None:\n        pass\n    else:\n        x = pack_host_rng(s, d, g)\n",
+                 "    if not run.primary:\n        return\n    x = pack_host_rng(s, d, g)\n",
+                 "    for i in r:\n        if not ctx.primary:\n            continue\n        x = pack_host_rng(s, d, g)\n"):
+        assert _pack_sites(stage + body)[:2] == ([6 + body.count("\n") - 1], {6 + body.count("\n") - 1}), body
+    assert _pack_sites("def main():\n    if primary:\n        stage(run)\n\n\ndef stage(run):\n    x = pack_host_rng(s, d, g)\n")[:2] == ([7], {7})
+    assert _pack_sites(stage + "    if args.recovery_interval:\n        x = pack_host_rng(s, d, g)\n    if not run.primary:\n        return\n")[:2] == ([7], set())
+    # and on the driver itself: either save point moved under either gate is found
+    lines = src.splitlines()
+    for at in calls:
+        pad = lines[at - 1][:len(lines[at - 1]) - len(lines[at - 1].lstrip())]
+        for gate in ("if run.saver is not None:", "if run.primary:"):
+            moved = "\n".join(lines[:at - 1] + [pad + gate, "    " + lines[at - 1]] + lines[at:])
+            assert _pack_sites(moved)[:2] == ([c + (c >= at) for c in calls], {at + 1}), (at, gate)
 
 
 def test_reduction_plan_refuses_a_layout_that_is_not_in_backward_order():

@@ -265,10 +265,11 @@ def _streams(sp, crops):
 
 
 def test_stain_stream_rides_in_the_checkpoint(tmp_path):
-    from gipvit.checkpoint import load_checkpoint_file, pack_host_rng, restore_host_rng
+    from gipvit.checkpoint import load_checkpoint_file, pack_host_rng, restore_host_rng, stream_seed
     from gipvit.multicrop import MultiCropSampler
     from gipvit.stain import StainJitterSampler
-    mk = lambda seed=42 + 41: (StainJitterSampler(2, 2, 3, 0.2, prob=0.7, seed=seed), MultiCropSampler(2, 256, 2, 3, seed=42))
+    mk = lambda seed=stream_seed("stain", 42, 0): (StainJitterSampler(2, 2, 3, 0.2, prob=0.7, seed=seed),
+                                                   MultiCropSampler(2, 256, 2, 3, seed=stream_seed("crops", 42, 0)))
     sp, crops = mk()
     for _ in range(3):
         sp.sample_host(); crops.sample()
@@ -296,15 +297,15 @@ def test_stain_stream_rides_in_the_checkpoint(tmp_path):
 
 
 def test_stain_stream_is_reseeded_per_rank_when_the_world_changes():
-    from gipvit.checkpoint import pack_host_rng, restore_host_rng
+    from gipvit.checkpoint import pack_host_rng, restore_host_rng, stream_seed
     from gipvit.multicrop import MultiCropSampler
     from gipvit.stain import StainJitterSampler
-    sp, crops = StainJitterSampler(2, 2, 3, 0.2, seed=42 + 41), MultiCropSampler(2, 256, 2, 3, seed=42)
+    sp, crops = StainJitterSampler(2, 2, 3, 0.2, seed=stream_seed("stain", 42, 0)), MultiCropSampler(2, 256, 2, 3, seed=stream_seed("crops", 42, 0))
     ex = pack_host_rng(_streams(sp, crops), None, lambda o: [o])          # saved by one rank, resumed by two
     got = []
     for rank in (0, 1):
         s, c = StainJitterSampler(2, 2, 3, 0.2, seed=0), MultiCropSampler(2, 256, 2, 3, seed=0)
-        seeds = {"crops": 42 + rank, "stain": 42 + 313 * rank + 41}
+        seeds = {k: stream_seed(k, 42, rank) for k in ("crops", "stain")}
         assert restore_host_rng(ex, _streams(s, c), None, rank, 2, 4, seeds=seeds) == "reseeded"
         want = np.random.default_rng([4, seeds["stain"]]).bit_generator.state
         assert s.rng.bit_generator.state == want

@@ -43,13 +43,16 @@ import os
 import sys
 import time
 from collections import OrderedDict
+from types import SimpleNamespace
 
+import numpy as np
 import torch
 import yaml
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+from gipvit.checkpoint import HOST_STREAMS, CheckpointSaver, load_checkpoint_file, pack_host_rng, restore_host_rng, stream_seed  # noqa: E402
 from gipvit.cli_spec import REFERENCE_FLAGS  # noqa: E402
 
 _logger = logging.getLogger("train")
@@ -182,6 +185,7 @@ def parse_args(argv=None):
 
 SUPPORTED_OPTS = ("sgd", "adam", "adamw", "lamb")  # modes of gv_adamw_ema (sgd = momentum + nesterov, timm's default for 'sgd') + gv_lamb
 SUPPORTED_SCHEDS = ("cosine", "step")               # gipvit/sched.py
+LOWER_IS_BETTER = ("loss", "linear_loss", "mil_loss")     # train.py:866: the --eval-metric values where the lower checkpoint is the better one
 
 
 def dino_loss_options(args) -> dict:
@@ -529,7 +533,7 @@ def build_mix_sampler(args, img_size: int, rank: int = 0):
     from gipvit.mixup import MixSampler
     return MixSampler(mixup_alpha=args.mixup, cutmix_alpha=args.cutmix, cutmix_minmax=args.cutmix_minmax, prob=args.mixup_prob,
                       switch_prob=args.mixup_switch_prob, mode=args.mixup_mode, batch=args.batch_size, img_size=img_size,
-                      seed=args.seed + 101 * rank + 23)
+                      seed=stream_seed("mix", args.seed, rank))
 
 
 def build_erase_sampler(args, img_size: int, rank: int = 0):
@@ -538,7 +542,7 @@ def build_erase_sampler(args, img_size: int, rank: int = 0):
         return None
     from gipvit.erasing import EraseSampler
     return EraseSampler(prob=args.reprob, mode=args.remode, count=args.recount, batch=args.batch_size, img_size=img_size,
-                        seed=args.seed + 211 * rank + 37)
+                        seed=stream_seed("erase", args.seed, rank))
 
 
 def amp_is_f16(args) -> bool:
@@ -595,6 +599,351 @@ def hook_batch_format(args, transform, argv=None) -> str:
     return fmt
 
 
+def select_slides(args, slides, primary=True):
+    """-> (training slides, evaluation slides, whether validate() has a fold to run on)."""
+    from gipvit import data as D
+    want_eval = not args.no_validate and (not args.dino or args.extract_features)
+    train_slides = D.select_fold(slides, args.test_fold, True)
+    if args.supervised or (monitor_metric_names(args) and not args.extract_features) or (want_eval and args.test_fold not in (-1, "-1")):
+        eval_slides = D.select_fold(slides, args.test_fold, False)       # raises when evaluation was asked for and no slide is in the fold
+    else:
+        eval_slides = []        # the reference's "no validation" setting (train.py:367, datasets.py:284-287): every fold but 'test' / 'val' trains
+        if want_eval and primary:
+            _logger.info("--test_fold -1: no validation fold; validate() is skipped (reference train.py:367)")
+        want_eval = False
+    if args.supervised:     # train.py:715-717: --supervised re-splits the TEST-fold set 80 / 20 into train / eval
+        perm = np.random.default_rng(args.seed).permutation(len(eval_slides))
+        k = max(1, int(len(eval_slides) * 0.8))
+        train_slides, eval_slides = [eval_slides[i] for i in perm[:k]], [eval_slides[i] for i in perm[k:]] or eval_slides
+    return train_slides, eval_slides, want_eval
+
+
+def build_loaders(args, run, transform, hook_format):
+    """-> SimpleNamespace(source, augmenter: a named recipe's; inf: validate()'s loader; bank / query: the monitors', training / evaluation fold) or Nones."""
+    from gipvit import data as D, transformations as T
+    B, tile, rank = run.B, run.tile, run.rank
+    synthetic = args.dataset in ("", "synthetic")
+    transform = T.define_transformations(transform if transform is not None else args.transform_type if not synthetic else "none", True, tile, args.c_param, "Ron")
+    augmenter = None
+    if getattr(transform, "device_recipe", None):      # the named recipes run on the DEVICE once the tiles are in HBM (gv_augment); the readers deliver raw tiles
+        from gipvit.augment import TileAugmenter
+        augmenter = TileAugmenter(transform.device_recipe, tile, transform.color_param, run.mean, run.std, seed=args.seed + 31 * rank, device=run.dev)
+        transform = None
+    if hook_format == "f32_nchw" and run.primary:
+        _logger.info("transform hook returns float32 [3, H, W]: batches are float32 NCHW, patchified without the fused normalise")
+    inf = bank = query = None
+    bank_tiles, monitors_on = args.knn_bank_tiles or args.num_tiles, bool(monitor_metric_names(args)) and not args.extract_features
+    if synthetic:
+        source = D.SyntheticTiles(B, tile, args.batches_per_epoch, args.num_classes or 2, seed=args.seed + rank)
+        if not args.no_validate and (not args.dino or args.extract_features):
+            inf = D.SyntheticSlides(args.synthetic_slides, min(args.num_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 99)
+        if monitors_on:      # (--extract_features runs alone)
+            bank = D.SyntheticSlides(args.synthetic_slides, min(bank_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 77)
+            query = D.SyntheticSlides(args.synthetic_slides, min(args.num_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 99)
+    elif args.dataset.startswith("tiles:") or args.data_dir:
+        root = args.dataset[6:] if args.dataset.startswith("tiles:") else args.data_dir
+        train_slides, eval_slides, want_eval = select_slides(args, D.scan_slides(root, args.target), run.primary)
+        infer = lambda n, seed, slides: D.InferTiles(root, tile, args.tiles_per_iter, n, seed=seed, dataset_name=args.dataset, workers=args.workers, slides=slides)
+        source = D.TileFolder(root, B, transform, rank, run.world, args.seed, tile, n_tiles=args.n_patches_train, workers=args.workers, slides=train_slides)
+        if want_eval:
+            inf = infer(args.num_tiles, args.seed, eval_slides)
+        if monitors_on:      # (--extract_features runs alone)
+            bank, query = infer(bank_tiles, args.seed + 1, train_slides), infer(args.num_tiles, args.seed, eval_slides)
+    else:
+        raise SystemExit(f"--dataset {args.dataset}: whole-slide datasets need openslide and are outside this build "
+                         "(SURVEY section 2 #15); use 'synthetic' or 'tiles:<dir>' with pre-extracted tile_<i>.data files")
+    return SimpleNamespace(source=source, augmenter=augmenter, inf=inf, bank=bank, query=query)
+
+
+def build_engine(args, run, img_from_input_size):
+    """-> (engine with its initial, --initial-checkpoint or --resume state, image size, classes (0: --dino), --model-ema's decay or None, the --resume
+    checkpoint or None, the epoch to start at)."""
+    from gipvit import models as M
+    from gipvit.engine import DinoEngine, SupervisedEngine
+    arch, B, tile = run.arch, run.B, run.tile
+    common = dict(arch=arch, batch=B, lr=run.lr, weight_decay=args.weight_decay, betas=run.betas, eps=run.eps, clip_grad=args.clip_grad or 0.0,
+                  mean=run.mean, std=run.std, device=run.dev, reducer=run.reducer, precision=args.precision, clip_mode=args.clip_mode)
+    ema_decay = args.model_ema_decay if args.model_ema else None                 # train.py:615-622
+    if args.dino:
+        if args.model_ema and run.primary:
+            _logger.warning("--model-ema with --dino: the DINO teacher IS the EMA model (momentum schedule --momentum-teacher); flag has no further effect")
+        img, nc = args.global_crop_size, 0
+        eng = DinoEngine(img_size=img, out_dim=args.out_dim, tile=tile, n_local=args.local_crops_number, gsize=args.global_crop_size, lsize=args.local_crop_size,
+                         momentum_teacher=args.momentum_teacher, teacher_temp=args.teacher_temp, **common, **dino_loss_options(args), **ibot_options(args))
+        bb = (M.load_encoder_checkpoint(args.initial_checkpoint, arch, img, mask_token=args.ibot_weight > 0) if args.initial_checkpoint
+              else M.init_vit_state(arch, img, 0, seed=args.seed))
+        eng.load_state(bb, M.init_dino_head_state(eng.D, args.out_dim, seed=args.seed + 1))
+    else:
+        img, nc = args.img_size or img_from_input_size or tile, args.num_classes or 2   # the reference patches timm's default cfg to 256 (train_instruct.txt:9-13)
+        eng = SupervisedEngine(img_size=img, num_classes=nc, smoothing=args.smoothing, opt=run.opt, momentum=args.momentum, train_backbone=not args.no_grad,
+                               model_ema_decay=ema_decay, loss=loss_kind(args), bce_target_thresh=args.bce_target_thresh if loss_kind(args) == "bce" else None,
+                               layer_decay=args.layer_decay, global_pool=args.gp, **common)
+        st = (M.load_encoder_checkpoint(args.initial_checkpoint, arch, img, nc, eng.pool) if args.initial_checkpoint
+              else M.init_vit_state(arch, img, nc, seed=args.seed, global_pool=eng.pool))
+        eng.load_state(st)
+    if not args.resume:
+        return eng, img, nc, ema_decay, None, args.start_epoch or 0
+    ck = load_checkpoint_file(args.resume)        # weights, teacher / EMA copy, optimizer moments and loss scaler into the engine
+    strip = lambda d: {k[7:] if k.startswith("module.") else k: v for k, v in d.items()}
+    sd = strip(ck["state_dict"])
+    sub = lambda d, pre: {k[len(pre):]: v for k, v in d.items() if k.startswith(pre)}
+    if args.dino:
+        eng.load_state(sub(sd, "backbone."), sub(sd, "head."))
+        if "state_dict_ema" in ck:        # the teacher + centre: without them the run would restart the EMA from the student
+            te = strip(ck["state_dict_ema"])
+            eng.load_teacher_state(sub(te, "backbone."), sub(te, "head."), ck.get("dino_center"))
+            if args.ibot_weight > 0 and ck.get("ibot_center") is not None:
+                eng.patch_center.copy_(ck["ibot_center"].to(run.dev, torch.float32).view(-1))
+        elif run.primary:
+            _logger.warning("--resume: %s holds no teacher ('state_dict_ema'); the teacher restarts as a copy of the student", args.resume)
+    else:
+        eng.load_state(sd, strip(ck["state_dict_ema"]) if (ema_decay is not None and "state_dict_ema" in ck) else None)
+    if "optimizer" in ck and not args.no_resume_opt:
+        eng.arena.m.copy_(ck["optimizer"]["exp_avg"]); eng.arena.v.copy_(ck["optimizer"]["exp_avg_sq"]); eng.t = int(ck["optimizer"]["step"])
+    if eng.scaler is not None and isinstance(ck.get("amp_scaler"), dict):      # timm resume_checkpoint(..., loss_scaler=...); a GradScaler state
+        # written by torch itself has no count of applied steps: the optimizer's step count stands in
+        eng.scaler.load_state_dict(dict({"applied_steps": eng.t}, **ck["amp_scaler"]))
+    return eng, img, nc, ema_decay, ck, args.start_epoch if args.start_epoch is not None else ck.get("epoch", -1) + 1
+
+
+def build_evaluation(args, args_text, run):
+    """What ends an epoch -> (runners over the engine's LIVE weights: SimpleNamespace(val, ema, mon: the monitors', norm: {name: its SlideNormaliser} or {}),
+    the monitors, the resolved --eval-metric, the primary's saver and output dir (train.py:854-879))."""
+    from gipvit.engine import FeatureExtractor, Weights
+    arch, tile, mean, std, dev, eng, img, nc = run.arch, run.tile, run.mean, run.std, run.dev, run.eng, run.img, run.nc
+    eval_B = min(256, max(run.B, 32))
+    teacher = lambda: Weights(eng.arena, "backbone.", teacher=True, fp32=args.precision == "fp32")
+    r = SimpleNamespace(val=None, ema=None, mon=None, norm={})
+    if run.data.inf is not None:
+        if args.dino:       # features come from the teacher backbone (the model DINO users evaluate)
+            r.val = FeatureExtractor(arch, tile, eval_B, 0, mean, std, dev, weights=teacher())
+            if tile != img:
+                raise SystemExit(f"--extract_features with --dino: tile size {tile} must equal the teacher's image size {img}")
+        else:
+            r.val = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.W, global_pool=eng.pool)
+            if run.ema_decay is not None:
+                r.ema = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.Wema, global_pool=eng.pool)
+    if run.data.bank is not None:   # the teacher backbone at its own image size; larger tiles contribute their centred window (gipvit/knn.py)
+        r.mon = FeatureExtractor(arch, img, eval_B, 0, mean, std, dev, weights=teacher())
+    if args.stain_normalize == "macenko":
+        from gipvit.stainnorm import MacenkoEstimator, SlideNormaliser
+        estimator = MacenkoEstimator(dev, beta=args.stain_norm_beta, alpha=args.stain_norm_alpha, max_tiles=args.stain_norm_tiles)
+        r.norm = {key: SlideNormaliser(getattr(r, key), estimator, primary=run.primary) for key in ("val", "ema", "mon") if getattr(r, key) is not None}
+        if run.primary:
+            _logger.info("stain normalisation: macenko (beta %.3g alpha %.3g, %s of a slide's first chunk) on every inference pass%s; "
+                         "training batches are not normalised", args.stain_norm_beta, args.stain_norm_alpha,
+                         f"the first {args.stain_norm_tiles} tiles" if args.stain_norm_tiles else "every tile", "" if r.norm else " (this run has none)")
+    monitors = build_monitors(args, r.mon, run.primary, r.norm.get("mon"))
+    eval_metric = resolve_eval_metric(args.eval_metric, *(any(m.prefix == p for m in monitors) for p in ("knn_", "linear_", "mil_")))   # 'top1' -> knn_top1
+    saver = output_dir = None
+    if run.primary:
+        exp = args.experiment or "-".join([time.strftime("%Y%m%d-%H%M%S"), args.model.replace("/", "_"), str(img)])
+        output_dir = os.path.join(args.output or "./output/train", exp, args.subexperiment or "")
+        decreasing = eval_metric in LOWER_IS_BETTER or not (monitors or (run.data.inf is not None and not args.dino))       # train.py:866
+        saver = CheckpointSaver(output_dir, args.model, vars(args), decreasing=decreasing, max_history=args.checkpoint_hist)
+        with open(os.path.join(output_dir, "args.yaml"), "w") as f:
+            f.write(args_text)
+    return r, monitors, eval_metric, saver, output_dir
+
+
+def build_monitors(args, runner, primary=True, normaliser=None):
+    """The run's monitors on ``runner``, in the fixed order k-NN, linear probe, MIL probe.  ``normaliser``: the keyword exists with --stain-normalize only."""
+    if runner is None:
+        return []
+    from gipvit.knn import KnnMonitor as Knn            # (imported late: they load the library)
+    from gipvit.linprobe import LinearProbe as Linear
+    from gipvit.mil import MilProbe as Mil
+    kw = dict(num_classes=args.num_classes or 2, primary=primary, **({"normaliser": normaliser} if normaliser is not None else {}))
+    monitors = []
+    if args.knn_monitor:
+        monitors.append(Knn(runner, k=args.knn_k, temp=args.knn_temp, **kw))
+    if args.linear_probe:       # heads on the same runner's last-layer CLS tokens (gipvit/linprobe.py)
+        monitors.append(Linear(runner, lrs=args.linprobe_lrs, weight_decay=args.linprobe_wd, epochs=args.linprobe_epochs, batch=args.linprobe_batch,
+                               n_last=args.linprobe_layers, avgpool=args.linprobe_avgpool, holdout=args.linprobe_holdout, seed=args.seed, **kw))
+    if args.mil_probe:          # slide-level ABMIL on the same runner's CLS tokens, one bag per slide (gipvit/mil.py)
+        monitors.append(Mil(runner, hidden=args.mil_hidden, lr=args.mil_lr, weight_decay=args.mil_wd, epochs=args.mil_epochs, batch=args.mil_batch,
+                            n_last=args.mil_layers, seed=args.seed, **kw))
+    assert [n for m in monitors for n in m.metric_names()] == monitor_metric_names(args)        # the flag-level statements the refusals and the saver use
+    assert [m.prefix + x for m in monitors for x in m.lower_is_better] == [n for n in monitor_metric_names(args) if n in LOWER_IS_BETTER]
+    return monitors
+
+
+def monitor_due(args, prefix: str, epoch: int) -> bool:
+    """The monitor with this metric prefix runs after ``epoch``: k-NN every --knn-rate epochs; a probe after the last and, at a rate >= 1, every rate epochs."""
+    if prefix == "knn_":
+        return (epoch + 1) % args.knn_rate == 0
+    rate = args.linprobe_rate if prefix == "linear_" else args.mil_rate
+    return epoch == args.epochs - 1 or (rate >= 1 and (epoch + 1) % rate == 0)
+
+
+def build_samplers(args, rank, primary, dev, img, depth, drop_rows):
+    """The run's host draw streams, seeded per rank from checkpoint.HOST_STREAMS -> SimpleNamespace(samplers or None, streams: {name: Generator}, seeds)."""
+    B, seed = args.batch_size, (lambda name: stream_seed(name, args.seed, rank))
+    s = SimpleNamespace(crops=None, ibot=None, views=None, stain=None, drop_path=None, drop=None)
+    if args.dino and args.random_crops:       # DINO recipe: random-resized crops + flips, cut on the device
+        from gipvit.multicrop import MultiCropSampler
+        s.crops = MultiCropSampler(B, args.tile_size, 2, args.local_crops_number, tuple(args.global_crops_scale), tuple(args.local_crops_scale), seed=seed("crops"))
+    # mixup / cutmix (train.py:752-771, 1037-1040): the draws are the host's, the mixed batch is made inside the patchify pass
+    s.mix = None if args.dino else build_mix_sampler(args, img, rank)
+    if s.mix is not None and primary:
+        _logger.info("mixup / cutmix on the device: mixup %.3g cutmix %.3g minmax %s prob %.3g switch %.3g mode %s, loss %s", args.mixup, args.cutmix,
+                     args.cutmix_minmax, args.mixup_prob, args.mixup_switch_prob, args.mixup_mode, loss_kind(args))
+    # random erasing (--reprob / --remode / --recount): boxes drawn on the host, erased inside the same patchify pass, after the mixing
+    s.erase = None if args.dino else build_erase_sampler(args, img, rank)
+    if s.erase is not None and primary:
+        _logger.info("random erasing on the device: reprob %.3g remode %s recount %d (training steps only, after mixup / cutmix)", args.reprob, args.remode, args.recount)
+    if args.dino and args.ibot_weight > 0:      # iBOT: which patches of which global crop the student does not see, drawn per rank
+        from gipvit.masking import MaskSampler
+        s.ibot = MaskSampler(args.global_crop_size // 16, 2 * B, tuple(args.ibot_mask_ratio), args.ibot_mask_prob, seed=seed("ibot"))
+    if args.view_augment:
+        from gipvit.multicrop import ViewAugmentSampler
+        s.views = ViewAugmentSampler(B, 2, args.local_crops_number, jitter_p=args.color_jitter_p, gray_p=args.gray_p, blur_p=tuple(args.blur_p),
+                                     solar_p=(0.0, args.solarize_p, 0.0), seed=seed("views"))
+    if args.stain_jitter > 0:       # H&E stain jitter: folded per-crop records drawn per rank, applied in the view-augmentation pass
+        from gipvit.stain import StainJitterSampler
+        s.stain = StainJitterSampler(B, 2, args.local_crops_number, args.stain_jitter, prob=args.stain_prob, seed=seed("stain"))
+        if primary:
+            _logger.info("H&E stain jitter on the device: sigma %.3g prob %.3g (every crop, ahead of the view augmentation)", args.stain_jitter, args.stain_prob)
+    if args.drop_path:      # train.py:287-288: stochastic depth on the training passes (DINO: the student's, every crop of every tile its own sample)
+        from gipvit.droppath import DropPathSampler
+        s.drop_path = DropPathSampler(depth, drop_rows, args.drop_path, seed("drop_path"), dev)
+    if args.drop:           # train.py:283-284: nn.Dropout at the four sites of the encoder, a fresh 32-bit seed per step (counter-based masks)
+        s.drop = np.random.default_rng(seed("drop"))
+    s.streams = {"drop": s.drop, **{k: getattr(getattr(s, k), "rng", None) for k in ("crops", "views", "stain", "mix", "erase", "ibot")}}
+    s.seeds = {k: seed(k) for k in HOST_STREAMS}
+    return s
+
+
+def extra_state(args, eng, ema_decay, rng_state):
+    """A checkpoint's entries beside weights and optimizer; ``rng_state``: pack_host_rng's, gathered by ALL ranks at the save point."""
+    ex = dict(rng_state)
+    if args.dino:       # teacher (the EMA model) + centre: a DINO run cannot be resumed (or evaluated) without them
+        ex.update(state_dict_ema=eng.arena.state_dict(eng.arena.t), dino_center=eng.center.detach().cpu())
+        if eng.ibot_weight > 0:
+            ex["ibot_center"] = eng.patch_center.detach().cpu()
+    elif ema_decay is not None:
+        ex["state_dict_ema"] = eng.state_dict(ema=True)     # timm CheckpointSaver key (SURVEY section 5)
+    if eng.scaler is not None:
+        ex["amp_scaler"] = eng.scaler.state_dict()          # timm CheckpointSaver(amp_scaler=loss_scaler) key, train.py:585-602
+    return ex
+
+
+def train_epoch(args, run, epoch):
+    """The step loop (train.py:988-1143) -> the epoch's train metrics; leaves the last step's rate in ``run.cur_lr``."""
+    from gipvit import sched as S
+    eng, smp, dev, B, world = run.eng, run.smp, run.dev, run.B, run.world
+    batch_time, data_time, losses, probs, targets = Meter(), Meter(), Meter(), [], []
+    end, last_idx, total_updates = time.time(), run.updates_per_epoch - 1, args.epochs * run.updates_per_epoch
+    if args.dino:
+        eng.train_last_layer = epoch >= args.freeze_last_layer
+    if smp.mix is not None and args.mixup_off_epoch and epoch >= args.mixup_off_epoch:
+        smp.mix.enabled = False                # train.py:1005-1009: no mixing from this epoch on; the loss stays the soft-target one
+    for batch_idx, mb in (enumerate(run.loader) if not args.extract_features else ()):      # train.py:906
+        data, target, fill = mb["Data"], mb["Target"], None
+        if run.data.augmenter is not None:      # the draws came with the batch (pinned staging); the pixel work is one launch here
+            data, fill = run.data.augmenter.run(data, mb["AugParams"]), mb["Fill"]
+        data_time.update(time.time() - end)
+        run.cur_lr = cur_lr = run.schedule.at(epoch, batch_idx)
+        if smp.drop_path is not None:
+            eng.set_drop_path(smp.drop_path.sample())
+        if smp.drop is not None:
+            eng.set_dropout(args.drop, int(smp.drop.integers(0, 1 << 32)))
+        if args.dino:
+            it = epoch * run.updates_per_epoch + batch_idx
+            sch = dict(lr=cur_lr, wd=S.cosine_between(args.weight_decay, args.weight_decay_end, it, total_updates),
+                       momentum_teacher=S.cosine_between(args.momentum_teacher, 1.0, it, total_updates),
+                       teacher_temp=teacher_temp_at(args, epoch))
+            loss_t = eng.step(data, boxes=smp.crops.sample(dev) if smp.crops is not None else None, fill=fill if smp.crops is None else None,
+                              views=smp.views.sample(dev) if smp.views is not None else None,
+                              **({"masks": smp.ibot.sample(dev)} if smp.ibot is not None else {}),
+                              **({"stains": smp.stain.sample(dev)} if smp.stain is not None else {}), **sch)
+        else:
+            ekw = {"erase": smp.erase.sample(dev)} if smp.erase is not None else {}
+            loss_t = eng.step(data, target, lr=cur_lr, fill=fill, mix=smp.mix.sample(dev) if smp.mix is not None else None, **ekw)
+            probs.append(eng.prob[:, 1].clone() if eng.C > 1 else eng.prob[:, 0].clone()); targets.append(target.view(-1).clone())
+        torch.cuda.synchronize()                  # train.py:1083
+        batch_time.update(time.time() - end)
+        if batch_idx == last_idx or batch_idx % args.log_interval == 0:
+            lv = float(loss_t)
+            if world > 1:
+                t = torch.tensor([lv], device=dev)
+                torch.distributed.all_reduce(t)   # utils.reduce_tensor, train.py:1091-1093
+                lv = float(t) / world
+            losses.update(lv, B)
+            if run.primary:
+                _logger.info("Train: {} [{:>4d}/{} ({:>3.0f}%)]  Loss: {:#.4g} ({:#.3g})  Time: {:.3f}s, {:>7.2f}/s  ({:.3f}s, {:>7.2f}/s)  "
+                             "LR: {:.3e}  Data: {:.3f} ({:.3f})".format(
+                                 epoch, batch_idx, run.updates_per_epoch, 100.0 * batch_idx / max(last_idx, 1), losses.val, losses.avg,
+                                 batch_time.val, B * world / batch_time.val, batch_time.avg, B * world / batch_time.avg, run.logged_lr(cur_lr),
+                                 data_time.val, data_time.avg)
+                             + ("  KoLeo: {:#.4g}".format(float(eng.koleo)) if args.dino and args.koleo_weight > 0 else "")
+                             + ("  iBOT: {:#.4g}".format(float(eng.ibot)) if args.dino and args.ibot_weight > 0 else ""))
+            if args.recovery_interval and (batch_idx + 1) % args.recovery_interval == 0:
+                rng_state = pack_host_rng(smp.streams, smp.drop_path, run.gather)       # a collective: every rank, only the write is the primary's
+                if run.saver is not None:
+                    run.saver.save_recovery(epoch, batch_idx, eng.arena.state_dict(), extra=extra_state(args, eng, run.ema_decay, rng_state))
+        end = time.time()
+    train_metrics = OrderedDict(loss=losses.avg)
+    if probs:
+        try:
+            from sklearn.metrics import roc_auc_score
+            train_metrics["auc"] = float(roc_auc_score(torch.cat(targets).cpu().numpy(), torch.cat(probs).float().cpu().numpy()))
+        except Exception:                       # single-class epoch etc. (the reference would raise, train.py:1054)
+            train_metrics["auc"] = float("nan")
+    return train_metrics
+
+
+def end_of_epoch(args, run, epoch, train_metrics):
+    """Slide-level validation (train.py:932-955), the monitors that are due, summary.csv, checkpoint on --eval-metric (958-973)."""
+    from gipvit.validate import validate
+    eng, runners, primary = run.eng, run.runners, run.primary
+    norm = lambda key: {"normaliser": runners.norm[key]} if key in runners.norm else {}
+    eval_metrics = OrderedDict()
+    if runners.val is not None:
+        eval_metrics = validate(runners.val, run.data.inf, extract_features=bool(args.extract_features), extract_attention=bool(args.extract_attention),
+                                smoothing=args.smoothing, log_interval=args.log_interval, out_dir=args.features_dir, primary=primary, **norm("val"))
+        if runners.ema is not None and not args.extract_features:       # train.py:943-955: the EMA model's metrics win
+            eval_metrics = validate(runners.ema, run.data.inf, smoothing=args.smoothing, log_interval=args.log_interval, primary=primary,
+                                    log_suffix=" (EMA)", **norm("ema"))
+    for m in run.monitors:
+        if monitor_due(args, m.prefix, epoch):      # the teacher moved: a fresh bank / fresh heads / a fresh model on it as it stands
+            m.fit(run.data.bank)
+            eval_metrics.update(m.evaluate(run.data.query))
+    if args.extract_features:
+        if primary:
+            _logger.info(f"*** features of {int(eval_metrics.get('slides', 0))} slides written to {args.features_dir}")
+        return
+    rng_state = pack_host_rng(run.smp.streams, run.smp.drop_path, run.gather)       # every rank: the checkpoint holds each rank's streams
+    if not primary:
+        return
+    # the monitors' columns stay in one order, empty for a monitor that did not run this epoch
+    monitor_names = [n for m in run.monitors for n in m.metric_names()]
+    row = summary_row(epoch, train_metrics, eval_metrics, monitor_names, run.logged_lr(run.cur_lr))
+    fn = os.path.join(run.output_dir, "summary.csv")
+    new = not os.path.exists(fn)
+    with open(fn, "a") as f:
+        w = csv.DictWriter(f, fieldnames=row.keys())
+        if new:
+            w.writeheader()
+        w.writerow(row)
+    if run.wandb is not None:
+        run.wandb.log({k: v for k, v in row.items() if v != ""})
+    optim, eval_metric = {"exp_avg": eng.arena.m, "exp_avg_sq": eng.arena.v, "step": eng.t}, run.eval_metric
+    if eval_metric in eval_metrics:
+        save_metric, name = eval_metrics[eval_metric], "eval " + eval_metric          # train.py:970-973
+    elif eval_metric in monitor_names or (not eval_metrics and run.monitors):
+        save_metric, name = None, "eval " + eval_metric                               # not evaluated this epoch (--knn-rate / --linprobe-rate / --mil-rate)
+    elif eval_metrics:
+        who = ("validate() reports" if not run.monitors else "the k-NN monitor reports" if [m.prefix for m in run.monitors] == ["knn_"]
+               else "the monitors of this run report")
+        raise SystemExit(f"--eval-metric {eval_metric}: {who} {list(eval_metrics)}")
+    else:
+        save_metric, name = train_metrics["loss"], "train loss"
+    best, best_ep = run.saver.save_checkpoint(epoch, eng.arena.state_dict(), optim, metric=save_metric, extra=extra_state(args, eng, run.ema_decay, rng_state))
+    _logger.info(f"*** epoch {epoch}: " + "  ".join(f"{k} {v:.4f}" for k, v in list(train_metrics.items()) + [("eval_" + k, v) for k, v in eval_metrics.items()])
+                 + (f"  (best {name} {best:.4f} @ {best_ep})" if best is not None else f"  (no {name} yet)"))
+
+
 def main(argv=None, transform=None):
     """``transform``: a custom augmentation hook in place of ``--transform_type`` (the reference's "any callable is the
     transform", transformations.py:199-200), applied by the tile reader threads.  It maps a uint8 [H, W, 3] tile to a uint8
@@ -620,426 +969,69 @@ def main(argv=None, transform=None):
         os.environ["GIPVIT_ACT_FORMAT"] = "f16"
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    reducer = None
+    reducer, gather = None, (lambda obj: [obj])            # gather: pack_host_rng's collective, [rank 0's obj, rank 1's, ...]
     if world > 1:
         import torch.distributed as dist
         from gipvit.dist import RcclReducer, comm_setup
         comm = comm_setup(world)                               # CUs left to RCCL's channels; the library sizes its launches for the rest
         dist.init_process_group("nccl", device_id=dev)         # RCCL
         reducer = RcclReducer()
+
+        def gather(obj):
+            out = [None] * world
+            dist.all_gather_object(out, obj)
+            return out
         if primary:
             _logger.info("data parallel over %d ranks (RCCL): launches sized for %d CUs (GIPVIT_COMM_CUS=%d)", world, comm["cu_budget"], comm["comm_cus"])
     torch.manual_seed(args.seed + rank)                        # utils.random_seed(seed, rank), train.py:467
-
     ignored = [e["flags"][-1] for e in REFERENCE_FLAGS if not e["used"] and e["flags"][-1].startswith("-")
                and getattr(args, flag_dest(e), None) not in (e.get("default"), None, False)]
     if ignored and primary:
         _logger.warning("flags accepted for CLI compatibility but outside this build's hot path: %s", " ".join(ignored))
-    run = None
+    wandb_run = None
     if args.log_wandb and primary:                             # train.py:447-450 (optional here; credentials from the environment only)
         try:
             import wandb
-            run = wandb.init(project=args.experiment or "gipvit", group=args.group or None, config=vars(args))
+            wandb_run = wandb.init(project=args.experiment or "gipvit", group=args.group or None, config=vars(args))
         except Exception as ex:                                # not installed / offline
             _logger.warning("--log-wandb: wandb unavailable (%s); metrics go to the log and summary.csv only", ex)
 
     from gipvit import models as M, sched as S, data as D, transformations as T
-    from gipvit.engine import ARCHS, DinoEngine, SupervisedEngine, FeatureExtractor, Weights
-    from gipvit.checkpoint import CheckpointSaver, load_checkpoint_file, pack_host_rng, restore_host_rng
-    from gipvit.validate import validate
-    arch = M.resolve_arch(args.model)
-    B = args.batch_size
-    mean = tuple(args.mean) if args.mean else T.MEAN["Ron"]
-    std = tuple(args.std) if args.std else T.STD["Ron"]
-    tile = args.tile_size
+    from gipvit.engine import ARCHS
     opt = args.opt.lower()
-    lr = S.scaled_lr(args.lr, args.lr_base, B, world, args.lr_base_size, args.lr_base_scale, opt)
+    run = SimpleNamespace(rank=rank, world=world, primary=primary, dev=dev, reducer=reducer, gather=gather, wandb=wandb_run, arch=M.resolve_arch(args.model),
+                          B=args.batch_size, tile=args.tile_size, mean=tuple(args.mean) if args.mean else T.MEAN["Ron"],
+                          std=tuple(args.std) if args.std else T.STD["Ron"], opt=opt, betas=tuple(args.opt_betas) if args.opt_betas else (0.9, 0.999),
+                          lr=S.scaled_lr(args.lr, args.lr_base, args.batch_size, world, args.lr_base_size, args.lr_base_scale, opt),
+                          eps=args.opt_eps if args.opt_eps is not None else (1e-6 if opt == "lamb" else 1e-8))     # timm defaults: Lamb 1e-6, Adam(W) 1e-8
     if primary:
-        _logger.info(f"Learning rate ({lr}) calculated from base learning rate ({args.lr_base}) and global batch size ({B * world})")
-    betas = tuple(args.opt_betas) if args.opt_betas else (0.9, 0.999)
-    eps = args.opt_eps if args.opt_eps is not None else (1e-6 if opt == "lamb" else 1e-8)       # timm defaults: Lamb 1e-6, Adam(W) 1e-8
-
-    # ---- data (batch dict contract of the reference: 'Data', 'Target'; inference: Infer_Dataset's dict)
-    synthetic = args.dataset in ("", "synthetic")
-    transform = T.define_transformations(transform if transform is not None else args.transform_type if not synthetic else "none", True, tile,
-                                         args.c_param, "Ron")
-    # the named recipes run on the DEVICE once the tiles are in HBM (gv_augment); the reader threads then deliver raw tiles
-    augmenter = None
-    if getattr(transform, "device_recipe", None):
-        from gipvit.augment import TileAugmenter
-        augmenter = TileAugmenter(transform.device_recipe, tile, transform.color_param, mean, std, seed=args.seed + 31 * rank, device=dev)
-        transform = None
-    if hook_format == "f32_nchw" and primary:
-        _logger.info("transform hook returns float32 [3, H, W]: batches are float32 NCHW, patchified without the fused normalise")
-    inf_loader = None
-    # --knn-monitor: the bank comes from the training fold, the queries from the evaluation fold; --extract_features runs alone
-    want_knn = bool(args.knn_monitor) and not args.extract_features
-    want_probe = bool(args.linear_probe) and not args.extract_features     # the same bank and query loaders, shared when both are on
-    want_mil = bool(args.mil_probe) and not args.extract_features
-    knn_bank_loader = knn_query_loader = None
-    bank_tiles = args.knn_bank_tiles or args.num_tiles
-    if synthetic:
-        source = D.SyntheticTiles(B, tile, args.batches_per_epoch, args.num_classes or 2, seed=args.seed + rank)
-        if not args.no_validate and (not args.dino or args.extract_features):
-            inf_loader = D.SyntheticSlides(args.synthetic_slides, min(args.num_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 99)
-        if want_knn or want_probe or want_mil:
-            knn_bank_loader = D.SyntheticSlides(args.synthetic_slides, min(bank_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 77)
-            knn_query_loader = D.SyntheticSlides(args.synthetic_slides, min(args.num_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 99)
-    elif args.dataset.startswith("tiles:") or args.data_dir:
-        root = args.dataset[6:] if args.dataset.startswith("tiles:") else args.data_dir
-        slides = D.scan_slides(root, args.target)
-        # the evaluation selection is needed only where an inference loader (or --supervised's re-split) will use it; --test_fold -1
-        # is the reference's documented "no validation" setting (train.py:367, datasets.py:284-287 give folds = []): such a run
-        # trains on every fold but 'test' / 'val' and skips validate() instead of failing on the empty selection
-        want_eval = not args.no_validate and (not args.dino or args.extract_features)
-        no_val_fold = args.test_fold in (-1, "-1")
-        train_slides = D.select_fold(slides, args.test_fold, True)
-        if args.supervised or want_knn or want_probe or want_mil or (want_eval and not no_val_fold):
-            eval_slides = D.select_fold(slides, args.test_fold, False)       # raises when evaluation was asked for and no slide is in the fold
-        else:
-            eval_slides = []
-            if want_eval and primary:
-                _logger.info("--test_fold -1: no validation fold; validate() is skipped (reference train.py:367)")
-            want_eval = False
-        if args.supervised:
-            # train.py:715-717: --supervised re-splits the TEST-fold set 80 / 20 into train / eval
-            import numpy as np
-            perm = np.random.default_rng(args.seed).permutation(len(eval_slides))
-            k = max(1, int(len(eval_slides) * 0.8))
-            train_slides, eval_slides = [eval_slides[i] for i in perm[:k]], [eval_slides[i] for i in perm[k:]] or eval_slides
-        source = D.TileFolder(root, B, transform, rank, world, args.seed, tile, n_tiles=args.n_patches_train, workers=args.workers,
-                              slides=train_slides)
-        if want_eval:
-            inf_loader = D.InferTiles(root, tile, args.tiles_per_iter, args.num_tiles, seed=args.seed, dataset_name=args.dataset,
-                                      workers=args.workers, slides=eval_slides)
-        if want_knn or want_probe or want_mil:
-            knn_bank_loader = D.InferTiles(root, tile, args.tiles_per_iter, bank_tiles, seed=args.seed + 1, dataset_name=args.dataset,
-                                           workers=args.workers, slides=train_slides)
-            knn_query_loader = D.InferTiles(root, tile, args.tiles_per_iter, args.num_tiles, seed=args.seed, dataset_name=args.dataset,
-                                            workers=args.workers, slides=eval_slides)
-    else:
-        raise SystemExit(f"--dataset {args.dataset}: whole-slide datasets need openslide and are outside this build "
-                         "(SURVEY section 2 #15); use 'synthetic' or 'tiles:<dir>' with pre-extracted tile_<i>.data files")
-    updates_per_epoch = len(source)
-
-    # ---- model + engine
-    ema_decay = args.model_ema_decay if args.model_ema else None                 # train.py:615-622
-    if args.dino:
-        if args.model_ema and primary:
-            _logger.warning("--model-ema with --dino: the DINO teacher IS the EMA model (momentum schedule --momentum-teacher); flag has no further effect")
-        img = args.global_crop_size
-        eng = DinoEngine(arch=arch, img_size=img, out_dim=args.out_dim, batch=B, tile=tile, n_local=args.local_crops_number,
-                         gsize=args.global_crop_size, lsize=args.local_crop_size, lr=lr, weight_decay=args.weight_decay, betas=betas, eps=eps,
-                         momentum_teacher=args.momentum_teacher, teacher_temp=args.teacher_temp, clip_grad=args.clip_grad or 0.0,
-                         mean=mean, std=std, device=dev, reducer=reducer, precision=args.precision, clip_mode=args.clip_mode,
-                         **dino_loss_options(args), **ibot_options(args))
-        bb = (M.load_encoder_checkpoint(args.initial_checkpoint, arch, img, mask_token=args.ibot_weight > 0) if args.initial_checkpoint
-              else M.init_vit_state(arch, img, 0, seed=args.seed))
-        eng.load_state(bb, M.init_dino_head_state(eng.D, args.out_dim, seed=args.seed + 1))
-        nc = 0
-    else:
-        img = args.img_size or img_from_input_size or tile   # the reference patches timm's default cfg to 256 (train_instruct.txt:9-13)
-        nc = args.num_classes or 2
-        eng = SupervisedEngine(arch=arch, img_size=img, num_classes=nc, batch=B, lr=lr, weight_decay=args.weight_decay, betas=betas, eps=eps,
-                               smoothing=args.smoothing, clip_grad=args.clip_grad or 0.0, mean=mean, std=std, device=dev, reducer=reducer,
-                               opt=opt, momentum=args.momentum,
-                               train_backbone=not args.no_grad, model_ema_decay=ema_decay, precision=args.precision, clip_mode=args.clip_mode,
-                               loss=loss_kind(args), bce_target_thresh=args.bce_target_thresh if loss_kind(args) == "bce" else None,
-                               layer_decay=args.layer_decay, global_pool=args.gp)
-        st = (M.load_encoder_checkpoint(args.initial_checkpoint, arch, img, nc, eng.pool) if args.initial_checkpoint
-              else M.init_vit_state(arch, img, nc, seed=args.seed, global_pool=eng.pool))
-        eng.load_state(st)
-    start_epoch = args.start_epoch or 0
-    if args.resume:
-        ck = load_checkpoint_file(args.resume)
-        strip = lambda d: {k[7:] if k.startswith("module.") else k: v for k, v in d.items()}
-        sd = strip(ck["state_dict"])
-        sub = lambda d, pre: {k[len(pre):]: v for k, v in d.items() if k.startswith(pre)}
-        if args.dino:
-            eng.load_state(sub(sd, "backbone."), sub(sd, "head."))
-            if "state_dict_ema" in ck:        # the teacher + centre: without them the run would restart the EMA from the student
-                te = strip(ck["state_dict_ema"])
-                eng.load_teacher_state(sub(te, "backbone."), sub(te, "head."), ck.get("dino_center"))
-                if args.ibot_weight > 0 and ck.get("ibot_center") is not None:
-                    eng.patch_center.copy_(ck["ibot_center"].to(dev, torch.float32).view(-1))
-            elif primary:
-                _logger.warning("--resume: %s holds no teacher ('state_dict_ema'); the teacher restarts as a copy of the student", args.resume)
-        else:
-            eng.load_state(sd, strip(ck["state_dict_ema"]) if (ema_decay is not None and "state_dict_ema" in ck) else None)
-        if "optimizer" in ck and not args.no_resume_opt:
-            eng.arena.m.copy_(ck["optimizer"]["exp_avg"]); eng.arena.v.copy_(ck["optimizer"]["exp_avg_sq"]); eng.t = int(ck["optimizer"]["step"])
-        if eng.scaler is not None and isinstance(ck.get("amp_scaler"), dict):      # timm resume_checkpoint(..., loss_scaler=...)
-            # (a GradScaler state written by torch itself has no count of applied steps: the optimizer's step count stands in)
-            eng.scaler.load_state_dict(dict({"applied_steps": eng.t}, **ck["amp_scaler"]))
-        start_epoch = args.start_epoch if args.start_epoch is not None else ck.get("epoch", -1) + 1
-    if hasattr(source, "epoch"):
-        source.epoch = start_epoch                 # the synthetic source seeds every epoch: a resumed run sees epoch k's tiles
+        _logger.info(f"Learning rate ({run.lr}) calculated from base learning rate ({args.lr_base}) and global batch size ({run.B * world})")
+    run.data = build_loaders(args, run, transform, hook_format)
+    run.eng, run.img, run.nc, run.ema_decay, ck, start_epoch = build_engine(args, run, img_from_input_size)
+    if hasattr(run.data.source, "epoch"):
+        run.data.source.epoch = start_epoch        # the synthetic source seeds every epoch: a resumed run sees epoch k's tiles
     if primary:
-        n_params = sum(int(torch.tensor(s).prod()) for s in eng.arena.specs.values())
-        _logger.info(f"Model {args.model} ({arch}) created, param count:{n_params}" + ("" if args.dino else f", global pool: {eng.pool}"))
-
-    # ---- forward-only runners for validation / feature extraction: they evaluate the engine's LIVE weights
-    eval_B = min(256, max(B, 32))
-    runner = runner_ema = None
-    if inf_loader is not None:
-        if args.dino:       # features come from the teacher backbone (the model DINO users evaluate)
-            runner = FeatureExtractor(arch, tile, eval_B, 0, mean, std, dev, weights=Weights(eng.arena, "backbone.", teacher=True, fp32=args.precision == "fp32"))
-            if tile != img:
-                raise SystemExit(f"--extract_features with --dino: tile size {tile} must equal the teacher's image size {img}")
-        else:
-            runner = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.W, global_pool=eng.pool)
-            if ema_decay is not None:
-                runner_ema = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.Wema, global_pool=eng.pool)
-
-    monitor = probe = mil = None
-    knn_names, probe_names, mil_names = [], [], []
-    if want_knn or want_probe or want_mil:        # the teacher backbone at its own image size; larger tiles contribute their centred window (gipvit/knn.py)
-        knn_runner = FeatureExtractor(arch, img, eval_B, 0, mean, std, dev, weights=Weights(eng.arena, "backbone.", teacher=True, fp32=args.precision == "fp32"))
-    # --stain-normalize: one SlideNormaliser per forward-only runner (nothing is built without the flag); the training engines never normalise
-    stain_norm = {}
-    if args.stain_normalize == "macenko":
-        from gipvit.stainnorm import MacenkoEstimator, SlideNormaliser
-        estimator = MacenkoEstimator(dev, beta=args.stain_norm_beta, alpha=args.stain_norm_alpha, max_tiles=args.stain_norm_tiles)
-        for key, r in (("val", runner), ("ema", runner_ema), ("mon", knn_runner if (want_knn or want_probe or want_mil) else None)):
-            if r is not None:
-                stain_norm[key] = SlideNormaliser(r, estimator, primary=primary)
-        if primary:
-            _logger.info("stain normalisation: macenko (beta %.3g alpha %.3g, %s of a slide's first chunk) on every inference pass%s; "
-                         "training batches are not normalised", args.stain_norm_beta, args.stain_norm_alpha,
-                         f"the first {args.stain_norm_tiles} tiles" if args.stain_norm_tiles else "every tile",
-                         "" if stain_norm else " (this run has none)")
-    mon_norm = {"normaliser": stain_norm["mon"]} if "mon" in stain_norm else {}      # the keyword exists with the flag only
-    if want_knn:
-        from gipvit.knn import KnnMonitor
-        monitor = KnnMonitor(knn_runner, k=args.knn_k, temp=args.knn_temp, num_classes=args.num_classes or 2, primary=primary, **mon_norm)
-        knn_names = ["knn_top1"] + (["knn_auc_per_patch", "knn_auc_per_slide"] if monitor.C > 1 else [])
-    if want_probe:      # heads on the same runner's last-layer CLS tokens (gipvit/linprobe.py)
-        from gipvit.linprobe import LinearProbe
-        probe = LinearProbe(knn_runner, num_classes=args.num_classes or 2, lrs=args.linprobe_lrs, weight_decay=args.linprobe_wd,
-                            epochs=args.linprobe_epochs, batch=args.linprobe_batch, n_last=args.linprobe_layers, avgpool=args.linprobe_avgpool,
-                            holdout=args.linprobe_holdout, seed=args.seed, primary=primary, **mon_norm)
-        probe_names = ["linear_top1", "linear_loss"] + (["linear_auc_per_patch", "linear_auc_per_slide"] if probe.C > 1 else [])
-
-    if want_mil:        # slide-level ABMIL on the same runner's CLS tokens, one bag per slide (gipvit/mil.py)
-        from gipvit.mil import MilProbe
-        mil = MilProbe(knn_runner, num_classes=args.num_classes or 2, hidden=args.mil_hidden, lr=args.mil_lr, weight_decay=args.mil_wd,
-                       epochs=args.mil_epochs, batch=args.mil_batch, n_last=args.mil_layers, seed=args.seed, primary=primary, **mon_norm)
-        mil_names = ["mil_top1", "mil_loss"] + (["mil_auc_per_slide"] if mil.C > 1 else [])
-    any_monitor = monitor is not None or probe is not None or mil is not None
-
-    # ---- output dir, args.yaml, saver (train.py:854-879)
-    eval_metric = resolve_eval_metric(args.eval_metric, monitor is not None, probe is not None, mil is not None)      # train.py:849; 'top1' -> knn_top1
-    decreasing = eval_metric in ("loss", "linear_loss", "mil_loss")         # train.py:866
-    saver = output_dir = None
-    if primary:
-        exp = args.experiment or "-".join([time.strftime("%Y%m%d-%H%M%S"), args.model.replace("/", "_"), str(img)])
-        output_dir = os.path.join(args.output or "./output/train", exp, args.subexperiment or "")
-        os.makedirs(output_dir, exist_ok=True)
-        saver = CheckpointSaver(output_dir, args.model, vars(args), decreasing=decreasing if any_monitor else (decreasing or inf_loader is None or args.dino),
-                                max_history=args.checkpoint_hist)
-        with open(os.path.join(output_dir, "args.yaml"), "w") as f:
-            f.write(args_text)
-    schedule = S.LrSchedule(lr, args.sched, args.epochs, args.warmup_epochs, args.warmup_lr, args.min_lr, updates_per_epoch,
-                            args.decay_epochs, args.decay_rate, on_updates=args.sched_on_updates or args.dino)
-    total_updates = args.epochs * updates_per_epoch
-    sampler = None
-    if args.dino and args.random_crops:       # DINO recipe: random-resized crops + flips, cut on the device
-        from gipvit.multicrop import MultiCropSampler
-        sampler = MultiCropSampler(B, tile, 2, args.local_crops_number, tuple(args.global_crops_scale), tuple(args.local_crops_scale),
-                                   seed=args.seed + rank)
-    # mixup / cutmix (train.py:752-771, 1037-1040): the draws are the host's, the mixed batch is made inside the patchify pass
-    mix_sampler = None if args.dino else build_mix_sampler(args, img, rank)
-    if mix_sampler is not None and primary:
-        _logger.info("mixup / cutmix on the device: mixup %.3g cutmix %.3g minmax %s prob %.3g switch %.3g mode %s, loss %s", args.mixup, args.cutmix,
-                     args.cutmix_minmax, args.mixup_prob, args.mixup_switch_prob, args.mixup_mode, loss_kind(args))
-    # random erasing (--reprob / --remode / --recount): boxes drawn on the host, erased inside the same patchify pass, after the mixing
-    erase_sampler = None if args.dino else build_erase_sampler(args, img, rank)
-    if erase_sampler is not None and primary:
-        _logger.info("random erasing on the device: reprob %.3g remode %s recount %d (training steps only, after mixup / cutmix)",
-                     args.reprob, args.remode, args.recount)
-    mask_sampler = None
-    if args.dino and args.ibot_weight > 0:      # iBOT: which patches of which global crop the student does not see, drawn per rank
-        from gipvit.masking import MaskSampler
-        mask_sampler = MaskSampler(args.global_crop_size // 16, 2 * B, tuple(args.ibot_mask_ratio), args.ibot_mask_prob, seed=args.seed + 101 * rank + 3)
-    view_sampler = None
-    if args.view_augment:
-        from gipvit.multicrop import ViewAugmentSampler
-        view_sampler = ViewAugmentSampler(B, 2, args.local_crops_number, jitter_p=args.color_jitter_p, gray_p=args.gray_p, blur_p=tuple(args.blur_p),
-                                          solar_p=(0.0, args.solarize_p, 0.0), seed=args.seed + 53 * rank + 5)
-    stain_sampler = None
-    if args.stain_jitter > 0:       # H&E stain jitter: folded per-crop records drawn per rank, applied in the view-augmentation pass
-        from gipvit.stain import StainJitterSampler
-        stain_sampler = StainJitterSampler(B, 2, args.local_crops_number, args.stain_jitter, prob=args.stain_prob, seed=args.seed + 313 * rank + 41)
-        if primary:
-            _logger.info("H&E stain jitter on the device: sigma %.3g prob %.3g (every crop, ahead of the view augmentation)", args.stain_jitter, args.stain_prob)
-
-    def host_streams():
-        return {"drop": drop_rng, "crops": getattr(sampler, "rng", None), "views": getattr(view_sampler, "rng", None), "stain": getattr(stain_sampler, "rng", None),
-                "mix": getattr(mix_sampler, "rng", None), "erase": getattr(erase_sampler, "rng", None), "ibot": getattr(mask_sampler, "rng", None)}
-
-    def gather_ranks(obj):
-        if world == 1:
-            return [obj]
-        out = [None] * world
-        torch.distributed.all_gather_object(out, obj)
-        return out
-
-    def extra_state(rng_state):
-        """``rng_state``: pack_host_rng's entries -- every rank's host-side draw streams (--drop step seeds, random-resized-crop
-        boxes, view augmentation, stain jitter, mixup, erasing, iBOT masks, --drop-path), gathered by ALL ranks at the save point."""
-        ex = dict(rng_state)
-        if args.dino:       # teacher (the EMA model) + centre: a DINO run cannot be resumed (or evaluated) without them
-            ex["state_dict_ema"] = eng.arena.state_dict(eng.arena.t)
-            ex["dino_center"] = eng.center.detach().cpu()
-            if eng.ibot_weight > 0:
-                ex["ibot_center"] = eng.patch_center.detach().cpu()
-        elif ema_decay is not None:
-            ex["state_dict_ema"] = eng.state_dict(ema=True)     # timm CheckpointSaver key (SURVEY section 5)
-        if eng.scaler is not None:
-            ex["amp_scaler"] = eng.scaler.state_dict()          # timm CheckpointSaver(amp_scaler=loss_scaler) key, train.py:585-602
-        return ex
-
+        n_params = sum(int(torch.tensor(s).prod()) for s in run.eng.arena.specs.values())
+        _logger.info(f"Model {args.model} ({run.arch}) created, param count:{n_params}" + ("" if args.dino else f", global pool: {run.eng.pool}"))
+    run.runners, run.monitors, run.eval_metric, run.saver, run.output_dir = build_evaluation(args, args_text, run)
+    run.updates_per_epoch = len(run.data.source)
+    run.schedule = S.LrSchedule(run.lr, args.sched, args.epochs, args.warmup_epochs, args.warmup_lr, args.min_lr, run.updates_per_epoch, args.decay_epochs,
+                                args.decay_rate, on_updates=args.sched_on_updates or args.dino)
     # the step's critical path runs on a high-priority stream; the engine's side stream (teacher forward,
     # weight-gradient GEMMs) fills the CU slots it leaves (DESIGN.md section 3a)
     torch.cuda.synchronize()
     torch.cuda.set_stream(torch.cuda.Stream(dev, priority=-1))
     # tiles reach HBM one batch ahead of the step: pinned staging + a copy stream (replaces pin_memory workers, train.py:732)
-    loader = D.DevicePrefetcher(source, dev, (B, tile, tile, 3), augmenter)
-    # --drop-path (train.py:287-288): stochastic depth on the training passes (DINO: the student's; every crop of every tile is
-    # its own sample); validation runs on its own forward-only group and never sees it
-    drop_sampler = None
-    if args.drop_path:
-        from gipvit.droppath import DropPathSampler
-        drop_sampler = DropPathSampler(ARCHS[arch]["depth"], (eng.V * B) if args.dino else B, args.drop_path, args.seed + 17 * rank, dev)
-    # --drop (train.py:283-284): nn.Dropout at the four sites of the encoder, a fresh 32-bit seed per step (counter-based masks)
-    drop_rng = None
-    if args.drop:
-        import numpy as np
-        drop_rng = np.random.default_rng(args.seed + 7919 * rank + 11)
+    run.loader = D.DevicePrefetcher(run.data.source, dev, (run.B, run.tile, run.tile, 3), run.data.augmenter)
+    run.smp = smp = build_samplers(args, rank, primary, dev, run.img, ARCHS[run.arch]["depth"], (run.eng.V * run.B) if args.dino else run.B)
     if args.resume:     # continue every rank's draw streams where the saved run left them (or, across a change of world size, restart them apart)
-        restore_host_rng(ck, host_streams(), drop_sampler, rank, world, start_epoch, warn=_logger.warning,
-                         seeds={"drop": args.seed + 7919 * rank + 11, "crops": args.seed + rank, "views": args.seed + 53 * rank + 5,
-                                "stain": args.seed + 313 * rank + 41, "mix": args.seed + 101 * rank + 23, "erase": args.seed + 211 * rank + 37, "ibot": args.seed + 101 * rank + 3,
-                                "drop_path": args.seed + 17 * rank})
-    cur_lr = lr
-    # the reference logs the MEAN rate over the optimizer's parameter groups (train.py:1088-1089, 959-965): with --layer-decay
-    # that is cur_lr x the mean group scale, without it cur_lr itself
-    logged_lr = eng.mean_lr if hasattr(eng, "mean_lr") else (lambda v: v)
-    # ---- epoch loop (train.py:905-977) / step loop (988-1143)
-    for epoch in range(start_epoch, args.epochs):
-        batch_time, data_time, losses = Meter(), Meter(), Meter()
-        probs, targets = [], []
-        end = time.time()
-        last_idx = updates_per_epoch - 1
-        if args.dino:
-            eng.train_last_layer = epoch >= args.freeze_last_layer
-        if mix_sampler is not None and args.mixup_off_epoch and epoch >= args.mixup_off_epoch:
-            mix_sampler.enabled = False                # train.py:1005-1009: no mixing from this epoch on; the loss stays the soft-target one
-        for batch_idx, mb in (enumerate(loader) if not args.extract_features else ()):      # train.py:906
-            data, target = mb["Data"], mb["Target"]
-            fill = None
-            if augmenter is not None:      # the draws came with the batch (pinned staging); the pixel work is one launch here
-                data, fill = augmenter.run(data, mb["AugParams"]), mb["Fill"]
-            data_time.update(time.time() - end)
-            cur_lr = schedule.at(epoch, batch_idx)
-            if drop_sampler is not None:
-                eng.set_drop_path(drop_sampler.sample())
-            if drop_rng is not None:
-                eng.set_dropout(args.drop, int(drop_rng.integers(0, 1 << 32)))
-            if args.dino:
-                it = epoch * updates_per_epoch + batch_idx
-                sch = dict(lr=cur_lr, wd=S.cosine_between(args.weight_decay, args.weight_decay_end, it, total_updates),
-                           momentum_teacher=S.cosine_between(args.momentum_teacher, 1.0, it, total_updates),
-                           teacher_temp=teacher_temp_at(args, epoch))
-                loss_t = eng.step(data, boxes=sampler.sample(dev) if sampler is not None else None, fill=fill if sampler is None else None,
-                                  views=view_sampler.sample(dev) if view_sampler is not None else None,
-                                  **({"masks": mask_sampler.sample(dev)} if mask_sampler is not None else {}),
-                                  **({"stains": stain_sampler.sample(dev)} if stain_sampler is not None else {}), **sch)
-            else:
-                ekw = {"erase": erase_sampler.sample(dev)} if erase_sampler is not None else {}
-                loss_t = eng.step(data, target, lr=cur_lr, fill=fill, mix=mix_sampler.sample(dev) if mix_sampler is not None else None, **ekw)
-                probs.append(eng.prob[:, 1].clone() if eng.C > 1 else eng.prob[:, 0].clone()); targets.append(target.view(-1).clone())
-            torch.cuda.synchronize()                  # train.py:1083
-            batch_time.update(time.time() - end)
-            if batch_idx == last_idx or batch_idx % args.log_interval == 0:
-                lv = float(loss_t)
-                if world > 1:
-                    t = torch.tensor([lv], device=dev)
-                    torch.distributed.all_reduce(t)   # utils.reduce_tensor, train.py:1091-1093
-                    lv = float(t) / world
-                losses.update(lv, B)
-                if primary:
-                    _logger.info("Train: {} [{:>4d}/{} ({:>3.0f}%)]  Loss: {:#.4g} ({:#.3g})  Time: {:.3f}s, {:>7.2f}/s  ({:.3f}s, {:>7.2f}/s)  "
-                                 "LR: {:.3e}  Data: {:.3f} ({:.3f})".format(
-                                     epoch, batch_idx, updates_per_epoch, 100.0 * batch_idx / max(last_idx, 1), losses.val, losses.avg,
-                                     batch_time.val, B * world / batch_time.val, batch_time.avg, B * world / batch_time.avg, logged_lr(cur_lr),
-                                     data_time.val, data_time.avg)
-                                 + ("  KoLeo: {:#.4g}".format(float(eng.koleo)) if args.dino and args.koleo_weight > 0 else "")
-                                 + ("  iBOT: {:#.4g}".format(float(eng.ibot)) if args.dino and args.ibot_weight > 0 else ""))
-                if args.recovery_interval and (batch_idx + 1) % args.recovery_interval == 0:
-                    rng_state = pack_host_rng(host_streams(), drop_sampler, gather_ranks)       # a collective: every rank, only the write is the primary's
-                    if saver is not None:
-                        saver.save_recovery(epoch, batch_idx, eng.arena.state_dict(), extra=extra_state(rng_state))
-            end = time.time()
-        # ---- end of epoch: train metrics, slide-level validation (train.py:932-955), summary.csv, checkpoint (958-973)
-        train_metrics = OrderedDict(loss=losses.avg)
-        if probs:
-            try:
-                from sklearn.metrics import roc_auc_score
-                train_metrics["auc"] = float(roc_auc_score(torch.cat(targets).cpu().numpy(), torch.cat(probs).float().cpu().numpy()))
-            except Exception:                       # single-class epoch etc. (the reference would raise, train.py:1054)
-                train_metrics["auc"] = float("nan")
-        eval_metrics = OrderedDict()
-        if runner is not None:
-            eval_metrics = validate(runner, inf_loader, extract_features=bool(args.extract_features),
-                                    extract_attention=bool(args.extract_attention), smoothing=args.smoothing,
-                                    log_interval=args.log_interval, out_dir=args.features_dir, primary=primary,
-                                    **({"normaliser": stain_norm["val"]} if "val" in stain_norm else {}))
-            if runner_ema is not None and not args.extract_features:       # train.py:943-955: the EMA model's metrics win
-                eval_metrics = validate(runner_ema, inf_loader, smoothing=args.smoothing, log_interval=args.log_interval, primary=primary,
-                                        log_suffix=" (EMA)", **({"normaliser": stain_norm["ema"]} if "ema" in stain_norm else {}))
-        if monitor is not None:
-            if (epoch + 1) % args.knn_rate == 0:                # the teacher moved: the bank is rebuilt at every evaluation
-                monitor.build_bank(knn_bank_loader)
-                eval_metrics.update(monitor.evaluate(knn_query_loader))
-        if probe is not None:
-            if epoch == args.epochs - 1 or (args.linprobe_rate >= 1 and (epoch + 1) % args.linprobe_rate == 0):
-                probe.fit(knn_bank_loader)                      # fresh heads on the teacher as it stands
-                eval_metrics.update(probe.evaluate(knn_query_loader))
-        if mil is not None:
-            if epoch == args.epochs - 1 or (args.mil_rate >= 1 and (epoch + 1) % args.mil_rate == 0):
-                mil.fit(knn_bank_loader)                        # a fresh model on the teacher as it stands
-                eval_metrics.update(mil.evaluate(knn_query_loader))
+        restore_host_rng(ck, smp.streams, smp.drop_path, rank, world, start_epoch, warn=_logger.warning, seeds=smp.seeds)
+    # the reference logs the MEAN rate over the parameter groups (train.py:1088-1089, 959-965): with --layer-decay cur_lr x the mean scale
+    run.cur_lr, run.logged_lr = run.lr, run.eng.mean_lr if hasattr(run.eng, "mean_lr") else (lambda v: v)
+    for epoch in range(start_epoch, args.epochs):      # train.py:905-977
+        end_of_epoch(args, run, epoch, train_epoch(args, run, epoch))
         if args.extract_features:
-            if primary:
-                _logger.info(f"*** features of {int(eval_metrics.get('slides', 0))} slides written to {args.features_dir}")
             break
-        rng_state = pack_host_rng(host_streams(), drop_sampler, gather_ranks)       # every rank: the checkpoint holds each rank's streams
-        if primary:
-            # the monitors' columns stay in one order, empty for a monitor that did not run this epoch
-            row = summary_row(epoch, train_metrics, eval_metrics, knn_names + probe_names + mil_names, logged_lr(cur_lr))
-            fn = os.path.join(output_dir, "summary.csv")
-            new = not os.path.exists(fn)
-            with open(fn, "a") as f:
-                w = csv.DictWriter(f, fieldnames=row.keys())
-                if new:
-                    w.writeheader()
-                w.writerow(row)
-            if run is not None:
-                run.log({k: v for k, v in row.items() if v != ""})
-            optim = {"exp_avg": eng.arena.m, "exp_avg_sq": eng.arena.v, "step": eng.t}
-            if eval_metric in eval_metrics:
-                save_metric, name = eval_metrics[eval_metric], "eval " + eval_metric          # train.py:970-973
-            elif eval_metric in knn_names + probe_names + mil_names or (not eval_metrics and any_monitor):
-                save_metric, name = None, "eval " + eval_metric                               # not evaluated this epoch (--knn-rate / --linprobe-rate / --mil-rate)
-            elif eval_metrics:
-                who = "the monitors of this run report" if (probe is not None or mil is not None) else "the k-NN monitor reports" if monitor is not None else "validate() reports"
-                raise SystemExit(f"--eval-metric {eval_metric}: {who} {list(eval_metrics)}")
-            else:
-                save_metric, name = train_metrics["loss"], "train loss"
-            best, best_ep = saver.save_checkpoint(epoch, eng.arena.state_dict(), optim, metric=save_metric, extra=extra_state(rng_state))
-            _logger.info(f"*** epoch {epoch}: " + "  ".join(f"{k} {v:.4f}" for k, v in list(train_metrics.items()) + [("eval_" + k, v) for k, v in eval_metrics.items()])
-                         + (f"  (best {name} {best:.4f} @ {best_ep})" if best is not None else f"  (no {name} yet)"))
     if world > 1:
         torch.distributed.destroy_process_group()
     return 0
