@@ -509,34 +509,17 @@ class VitRunner:
                 capture: Optional[Capture] = None, mix: Optional[torch.Tensor] = None, erase=None, masks=None, patch=None, stain=None):
         """windows: one list of (y0, x0) crop origins per segment; tiles_u8: one NHWC u8 tensor for all
         segments, or one per segment (pre-cut crops: each with the single window (0, 0)).  A float32 NCHW source (already
-        normalised, engine.input_form) goes through gv_patchify_nchw instead, without mean / std.  ``fill``: per-tile normalised
-        fill boxes of the augmentation (gipvit.augment: Cutout after Normalize, MeanPixelRegularization), f32 [n_tiles, 8].
+        normalised, engine.input_form) goes through gv_patchify_nchw instead, without mean / std.
+        ``fill`` / ``mix`` / ``erase`` / ``masks`` / ``stain``: optional inputs of the first stage (``_embed``).
         ``on_side``: the call is queued on the side stream (the teacher beside the student): its split-K products take that
         stream's scratch.  ``capture``: extra outputs of a forward-only pass (``Capture``); None issues exactly the default launches.
-        ``mix``: a device mix table (gipvit.mixup.MixPlan.table) -- the single-segment, single-window batch is mixed inside the
-        patchify pass (gv_patchify_mix / gv_patchify_nchw_mix); None issues exactly the default launches.
-        ``erase``: (device erase table, seed) of a gipvit.erasing.ErasePlan -- random erasing in that same pass, after ``fill`` and
-        ``mix`` (gv_patchify_erase / gv_patchify_nchw_erase); None issues exactly the default launches.
-        ``masks``: a gipvit.masking.MaskPlan over the images of the FIRST segment (iBOT: the student's global crops) -- the marked
-        patch embeddings are replaced by ``mask_token`` (+ pos) behind the patch-embedding product (gv_mask_tokens_fwd).
         ``patch``: (MaskPlan, PatchRows) -- the final norm also runs on the plan's rows of the first segment, into
         ``PatchRows.hb.feats`` (gv_rows_gather + gv_layernorm_fwd); the group must have ``all_tokens`` set.  Either None, or a
-        plan without a marked patch, issues exactly the default launches.
-        ``stain``: one packed gv_stain_params record per tile on the device (gipvit.stainnorm: stain normalisation at inference) --
-        the uint8 tiles of a forward-only single-segment group go through it inside the patchify pass (gv_patchify_stain); None
-        issues exactly the default launches."""
+        plan without a marked patch, issues exactly the default launches."""
         D, T, H = self.D, G.T, self.H
-        if stain is not None and (G.save or len(G.segs) != 1 or mix is not None or erase is not None):
-            raise ValueError("stain: inference only -- a forward-only single-segment group without mix / erase tables (training is never normalised)")
-        skw = {} if stain is None else {"stain": stain}        # the keyword exists for a pass with a record only
         if (masks is not None or patch is not None) and not G.all_tokens:
             raise ValueError("masks / patch: the group must run its last block on every token (VitGroup.all_tokens)")
         cap = capture
-        if mix is not None and (len(G.segs) != 1 or len(windows[0]) != 1):
-            raise ValueError("mix: the supervised step's one window of one segment only")
-        if erase is not None and (len(G.segs) != 1 or len(windows[0]) != 1):
-            raise ValueError("erase: the supervised step's one window of one segment only")
-        ekw = {} if erase is None else {"erase": erase}        # the keyword exists for a step with a plan only
         if cap is not None:
             assert not G.save and len(G.segs) == 1, "capture: forward-only single-crop groups"
         tok0 = self.depth - len(cap.tokens) if cap is not None else self.depth        # first block whose normed tokens are captured
@@ -545,41 +528,13 @@ class VitRunner:
         streams = any(sg.N > L.GV_ATTN_MAX_N for sg in G.segs)       # the fused varlen call holds whole sequences in LDS
         if cap is not None and cap.attn is not None:
             self.require_attention_maps(G)
-
-        def capture_tokens(i, xc):
-            ops.layernorm_fwd(xc, W.f("norm.weight"), W.f("norm.bias"), T, D, y=cap.tokens[i - tok0], mean=cap.stats[0], rstd=cap.stats[1])
         E = L
-        pos_full = W.f("pos_embed").view(-1, D)
-        x0 = G.xbuf(0)
-        for k, (sg, wins) in enumerate(zip(G.segs, windows)):
-            src = tiles_u8[k] if isinstance(tiles_u8, (list, tuple)) else tiles_u8
-            if src.dtype == f32:
-                if fill is not None:
-                    raise ValueError("fill= works on uint8 tiles: not with float32 NCHW input")
-                if stain is not None:
-                    raise ValueError("stain= works on uint8 tiles: float32 NCHW input is already normalised, its bytes are gone")
-                ops.patchify_nchw(src, wins, sg.crop, out=sg.patches, mix=mix, **ekw)
-            else:
-                ops.patchify(src, wins, sg.crop, mean, std, out=sg.patches, fill=fill, mix=mix, **ekw, **skw)
-            if sg.pos is None:
-                pos = pos_full
-            else:   # interpolate_pos_encoding: row 0 = cls pos, rows 1.. = M @ pos[1:]
-                pos = sg.pos
-                Ps = pos_full.shape[0] - 1
-                ops.small_matmul(self.one, pos_full, pos, 1, D, 1, sam=0, sak=0, sbk=0, sbn=1)
-                ops.small_matmul(sg.interp, pos_full[1:], pos[1:], sg.P, D, Ps, sam=Ps, sak=1, sbk=D, sbn=1)
-            xs = sg.rows(x0)
-            ops.cls_rows(xs, W.f("cls_token").view(-1), pos, sg.n_img, sg.N, D)
-            ops.linear(sg.patches, W.w("patch_embed.proj.weight").view(D, 768), xs, sg.n_img * sg.P, D, 768,
-                       epilogue=E.EPI_BIAS | E.EPI_POS, bias=W.f("patch_embed.proj.bias"), pos=pos, P=sg.P)
-            if masks is not None and k == 0 and masks.M > 0:
-                masks_fit(masks, sg)
-                ops.mask_tokens_fwd(xs, W.f("mask_token").view(-1), pos, masks.rows, masks.M, sg.N, D)
+        self._embed(W, G, tiles_u8, windows, mean, std, fill, mix, erase, masks, stain)
         # --drop: counter-based masks at the four nn.Dropout sites (gv_dropout / gv_dropout_add); the residual adds then run unfused
         dp = G.dropout
         dseed = (lambda layer, site: ops.dropout_site_seed(dp[1], layer, site)) if dp else None
         if dp:
-            ops.dropout(x0, dseed(0, 0), dp[0], n=T * D)                                  # pos_drop
+            ops.dropout(G.xbuf(0), dseed(0, 0), dp[0], n=T * D)                           # pos_drop
         # D = 384 (ViT-S): proj / fc2 run as full-row products with the residual add AND the LayerNorm that reads the new
         # row next fused into the epilogue (gv_linear_ln_fwd) -- only block 0's norm1 is a stand-alone pass
         fused = self.fused and dp is None
@@ -646,22 +601,73 @@ class VitRunner:
                 if dp:
                     ops.dropout(G.h[s], dseed(i, 2), dp[0], n=T * 4 * D)
                 residual(i, 3, G.h[s], "mlp.fc2", 4 * D, xb, xc, rs_m, ln_next)
-            if i >= tok0:
-                capture_tokens(i, xc)
-        xl = G.xbuf(2 * self.depth)
-        for sg in G.segs:
-            r0 = row_off + sg.img0
-            if G.pool == "avg":     # mean of the patch tokens -> fc_norm (timm global_pool='avg': the final norm is Identity)
-                pooled = G.pooled[sg.img0:sg.img0 + sg.n_img]
-                ops.token_mean_fwd(sg.rows(xl), pooled, sg.n_img, sg.N, D)
-                ops.layernorm_fwd(pooled, W.f("fc_norm.weight"), W.f("fc_norm.bias"), sg.n_img, D,
-                                  y=feats[r0:r0 + sg.n_img], mean=sg.fstats[0], rstd=sg.fstats[1])
-            elif cls_tail:         # the last block left its output for the CLS rows only, contiguous
-                ops.layernorm_fwd(G.c_xc[sg.img0:sg.img0 + sg.n_img], W.f("norm.weight"), W.f("norm.bias"), sg.n_img, D,
-                                  y=feats[r0:r0 + sg.n_img], mean=sg.fstats[0], rstd=sg.fstats[1])
+            if i >= tok0:     # capture: the final norm over every token of this block's output
+                ops.layernorm_fwd(xc, W.f("norm.weight"), W.f("norm.bias"), T, D, y=cap.tokens[i - tok0], mean=cap.stats[0], rstd=cap.stats[1])
+        self._final_norm(W, G, feats, row_off, cls_tail, patch)
+
+    def _embed(self, W: Weights, G: VitGroup, tiles_u8, windows, mean, std, fill, mix, erase, masks, stain):
+        """The first stage of ``forward``, per segment: patchify, the segment's pos embedding, CLS rows, the patch-embedding product
+        and iBOT's mask tokens -> the segment's rows of ``G.xbuf(0)``.  Its optional inputs, and what it refuses of them before anything is launched:
+        ``fill``: per-tile normalised fill boxes of the augmentation (gipvit.augment: Cutout after Normalize,
+        MeanPixelRegularization), f32 [n_tiles, 8].
+        ``mix``: a device mix table (gipvit.mixup.MixPlan.table) -- the single-segment, single-window batch is mixed inside the
+        patchify pass (gv_patchify_mix / gv_patchify_nchw_mix); None issues exactly the default launches.
+        ``erase``: (device erase table, seed) of a gipvit.erasing.ErasePlan -- random erasing in that same pass, after ``fill`` and
+        ``mix`` (gv_patchify_erase / gv_patchify_nchw_erase); None issues exactly the default launches.
+        ``masks``: a gipvit.masking.MaskPlan over the images of the FIRST segment (iBOT: the student's global crops) -- the marked
+        patch embeddings are replaced by ``mask_token`` (+ pos) behind the patch-embedding product (gv_mask_tokens_fwd).
+        ``stain``: one packed gv_stain_params record per tile on the device (gipvit.stainnorm: stain normalisation at inference) --
+        the uint8 tiles of a forward-only single-segment group go through it inside the patchify pass (gv_patchify_stain); None
+        issues exactly the default launches."""
+        D, E = self.D, L
+        if stain is not None and (G.save or len(G.segs) != 1 or mix is not None or erase is not None):
+            raise ValueError("stain: inference only -- a forward-only single-segment group without mix / erase tables (training is never normalised)")
+        for name, table in (("mix", mix), ("erase", erase)):
+            if table is not None and (len(G.segs) != 1 or len(windows[0]) != 1):
+                raise ValueError(f"{name}: the supervised step's one window of one segment only")
+        # (these two keywords exist for a step with a plan / a pass with a record only: without one the patchify call is the one it always was)
+        okw = {k: v for k, v in (("erase", erase), ("stain", stain)) if v is not None}
+        pos_full = W.f("pos_embed").view(-1, D)
+        x0 = G.xbuf(0)
+        for k, (sg, wins) in enumerate(zip(G.segs, windows)):
+            src = tiles_u8[k] if isinstance(tiles_u8, (list, tuple)) else tiles_u8
+            if src.dtype == f32:
+                if fill is not None:
+                    raise ValueError("fill= works on uint8 tiles: not with float32 NCHW input")
+                if stain is not None:
+                    raise ValueError("stain= works on uint8 tiles: float32 NCHW input is already normalised, its bytes are gone")
+                ops.patchify_nchw(src, wins, sg.crop, out=sg.patches, mix=mix, **okw)
             else:
-                ops.layernorm_fwd(sg.rows(xl), W.f("norm.weight"), W.f("norm.bias"), sg.n_img, D, x_stride=sg.N * D,
-                                  y=feats[r0:r0 + sg.n_img], mean=sg.fstats[0], rstd=sg.fstats[1])
+                ops.patchify(src, wins, sg.crop, mean, std, out=sg.patches, fill=fill, mix=mix, **okw)
+            if sg.pos is None:
+                pos = pos_full
+            else:   # interpolate_pos_encoding: row 0 = cls pos, rows 1.. = M @ pos[1:]
+                pos = sg.pos
+                Ps = pos_full.shape[0] - 1
+                ops.small_matmul(self.one, pos_full, pos, 1, D, 1, sam=0, sak=0, sbk=0, sbn=1)
+                ops.small_matmul(sg.interp, pos_full[1:], pos[1:], sg.P, D, Ps, sam=Ps, sak=1, sbk=D, sbn=1)
+            xs = sg.rows(x0)
+            ops.cls_rows(xs, W.f("cls_token").view(-1), pos, sg.n_img, sg.N, D)
+            ops.linear(sg.patches, W.w("patch_embed.proj.weight").view(D, 768), xs, sg.n_img * sg.P, D, 768,
+                       epilogue=E.EPI_BIAS | E.EPI_POS, bias=W.f("patch_embed.proj.bias"), pos=pos, P=sg.P)
+            if masks is not None and k == 0 and masks.M > 0:
+                masks_fit(masks, sg)
+                ops.mask_tokens_fwd(xs, W.f("mask_token").view(-1), pos, masks.rows, masks.M, sg.N, D)
+
+    def _final_norm(self, W: Weights, G: VitGroup, feats, row_off: int, cls_tail: bool, patch):
+        """The last stage of ``forward``: the pooled / CLS-only / strided-CLS final norm of every segment into ``feats``, and iBOT's
+        marked rows (``patch``) through the same norm into their own head buffers."""
+        D, xl = self.D, G.xbuf(2 * self.depth)
+        for sg in G.segs:
+            im, r0 = slice(sg.img0, sg.img0 + sg.n_img), row_off + sg.img0
+            out = dict(y=feats[r0:r0 + sg.n_img], mean=sg.fstats[0], rstd=sg.fstats[1])
+            if G.pool == "avg":     # mean of the patch tokens -> fc_norm (timm global_pool='avg': the final norm is Identity)
+                ops.token_mean_fwd(sg.rows(xl), G.pooled[im], sg.n_img, sg.N, D)
+                ops.layernorm_fwd(G.pooled[im], W.f("fc_norm.weight"), W.f("fc_norm.bias"), sg.n_img, D, **out)
+            elif cls_tail:         # the last block left its output for the CLS rows only, contiguous
+                ops.layernorm_fwd(G.c_xc[im], W.f("norm.weight"), W.f("norm.bias"), sg.n_img, D, **out)
+            else:
+                ops.layernorm_fwd(sg.rows(xl), W.f("norm.weight"), W.f("norm.bias"), sg.n_img, D, x_stride=sg.N * D, **out)
         if patch is not None and patch[0].M > 0:
             # iBOT: the final norm on the marked rows of the first segment, compact and in table order, for the head's second pass
             plan, pr = patch
@@ -756,48 +762,15 @@ class VitRunner:
         if not G.prepared:
             self.prepare_backward(G)
         G.prepared = False
-        xl = G.x[2 * self.depth]
         # stochastic depth: the bf16 gradient handed to a branch carries that branch's row factor (rs[i, 0] attention, rs[i, 1] MLP)
         rs = G.rs
         ring = self.partials_ring
-        for sg in G.segs:
-            # (the final norm touches the CLS rows only, one per image: the per-image factors are its row factors)
-            im = slice(sg.img0, sg.img0 + sg.n_img)
-            if G.pool == "avg":
-                # fc_norm backward over the pooled rows -> dpool, spread over the patch rows of the residual gradient and of the
-                # last block's MLP-half dY (the CLS rows: zeros).  The last mlp.fc2.bias gradient is the column sum of that dY's
-                # f32 source over every token row, sum_img gb_scale[img] * dpool[img]: the third sum of this launch
-                gs = None if rs is None else G.drop_img[self.depth - 1, 1, im]
-                ops.layernorm_bwd(dfeat[im], G.pooled[im], sg.fstats[0], sg.fstats[1], W.f("fc_norm.weight"), G.dpool[im], None, ring[0],
-                                  sg.n_img, D, g_init=True, gb_scale=gs)
-                ops.ln_finalize(ring[0], L.LN_PARTIAL_BLOCKS, D, W.g("fc_norm.weight"), W.g("fc_norm.bias"),
-                                None if dp else W.g(f"blocks.{self.depth - 1}.mlp.fc2.bias"))
-                ops.token_mean_bwd(G.dpool[im], sg.rows(G.g), sg.rows(gb_first), sg.n_img, sg.N, D, gb_scale=gs)
-                continue
-            if cls_tail:
-                ops.layernorm_bwd(dfeat[im], G.c_xc[im], sg.fstats[0], sg.fstats[1], W.f("norm.weight"), G.c_g[im], G.c_gb[im], ring[0],
-                                  sg.n_img, D, g_init=True, gb_scale=None if rs is None else G.drop_img[self.depth - 1, 1, im])
-            else:
-                ops.layernorm_bwd(dfeat[im], sg.rows(xl), sg.fstats[0], sg.fstats[1], W.f("norm.weight"), sg.rows(G.g),
-                                  sg.rows(gb_first), ring[0], sg.n_img, D, x_stride=sg.N * D, g_stride=sg.N * D, gb_stride=sg.N * D, g_init=True,
-                                  gb_scale=None if rs is None else G.drop_img[self.depth - 1, 1, im])
-            ops.ln_finalize(ring[0], L.LN_PARTIAL_BLOCKS, D, W.g("norm.weight"), W.g("norm.bias"),
-                            None if dp else W.g(f"blocks.{self.depth - 1}.mlp.fc2.bias"))
-        if patch is not None:
-            # the marked rows (unique, never a CLS row): the norm's backward on the compact copy, its three column sums next to the
-            # CLS rows' share, then a plain store into the rows prepare_backward left at zero
-            assert not cls_tail and G.pool != "avg" and dp is None
-            plan, pr = patch
-            sg, M = G.segs[0], plan.M
-            ops.layernorm_bwd(pr.hb.dfeats, pr.x, pr.mean, pr.rstd, W.f("norm.weight"), pr.g, pr.gb, ring[0], M, D, g_init=True,
-                              gb_scale=None if rs is None else pr.scale)
-            ops.ln_finalize(ring[0], L.LN_PARTIAL_BLOCKS, D, W.g("norm.weight"), W.g("norm.bias"), W.g(f"blocks.{self.depth - 1}.mlp.fc2.bias"))
-            ops.rows_scatter(pr.g, sg.rows(G.g), plan.rows, M, D, sg.T, gb_src=pr.gb, gb=sg.rows(gb_first))
+        self._final_norm_bwd(W, G, dfeat, gb_first, cls_tail, patch)
         # The weight-gradient GEMMs are off the critical path (nothing in backward consumes dW):
         # they run on a side stream beside the dX chain, so their tiles fill the tail of every
         # main-stream kernel (a 345 x 3-tile GEMM occupies 2.02 rounds of the 512 workgroup slots).
         # join(ev): main waits for a side event before it overwrites a buffer a dW product still reads (gb / dh / dqkv).
-        sx = SideStream(self.side if xl.is_cuda else None, self._events)
+        sx = SideStream(self.side if G.g.is_cuda else None, self._events)
         join = sx.join
 
         # LayerNorm backward leaves per-block column sums in a partials buffer; folding them into the gamma / beta /
@@ -901,7 +874,48 @@ class VitRunner:
         join(last_fin)          # ... and the last finalize
         if dp:
             ops.dropout(G.g, dseed(0, 0), dp[0], n=T * D)                                 # pos_drop's mask on the token gradient
-        # token assembly + patch embedding, per segment
+        self._embed_bwd(W, G, patch)
+
+    def _final_norm_bwd(self, W: Weights, G: VitGroup, dfeat: torch.Tensor, gb_first: torch.Tensor, cls_tail: bool, patch):
+        """The first stage of ``backward``: the final norm's backward of every segment (``_final_norm``'s three forms) and of iBOT's
+        marked rows, into the residual gradient ``G.g`` and ``gb_first``, the last block's MLP-half dY."""
+        D, dp, rs, ring, xl = self.D, G.dropout, G.rs, self.partials_ring, G.x[2 * self.depth]
+        fc2_bias = W.g(f"blocks.{self.depth - 1}.mlp.fc2.bias")      # its gradient is the third column sum of these launches (not under --drop)
+        for sg in G.segs:
+            # (the final norm touches the CLS rows only, one per image: the per-image factors are its row factors)
+            im = slice(sg.img0, sg.img0 + sg.n_img)
+            gs = None if rs is None else G.drop_img[self.depth - 1, 1, im]
+            if G.pool == "avg":
+                # fc_norm backward over the pooled rows -> dpool, spread over the patch rows of the residual gradient and of the
+                # last block's MLP-half dY (the CLS rows: zeros).  The last mlp.fc2.bias gradient is the column sum of that dY's
+                # f32 source over every token row, sum_img gb_scale[img] * dpool[img]: the third sum of this launch
+                ops.layernorm_bwd(dfeat[im], G.pooled[im], sg.fstats[0], sg.fstats[1], W.f("fc_norm.weight"), G.dpool[im], None, ring[0],
+                                  sg.n_img, D, g_init=True, gb_scale=gs)
+                ops.ln_finalize(ring[0], L.LN_PARTIAL_BLOCKS, D, W.g("fc_norm.weight"), W.g("fc_norm.bias"), None if dp else fc2_bias)
+                ops.token_mean_bwd(G.dpool[im], sg.rows(G.g), sg.rows(gb_first), sg.n_img, sg.N, D, gb_scale=gs)
+                continue
+            if cls_tail:
+                ops.layernorm_bwd(dfeat[im], G.c_xc[im], sg.fstats[0], sg.fstats[1], W.f("norm.weight"), G.c_g[im], G.c_gb[im], ring[0],
+                                  sg.n_img, D, g_init=True, gb_scale=gs)
+            else:
+                ops.layernorm_bwd(dfeat[im], sg.rows(xl), sg.fstats[0], sg.fstats[1], W.f("norm.weight"), sg.rows(G.g),
+                                  sg.rows(gb_first), ring[0], sg.n_img, D, x_stride=sg.N * D, g_stride=sg.N * D, gb_stride=sg.N * D, g_init=True,
+                                  gb_scale=gs)
+            ops.ln_finalize(ring[0], L.LN_PARTIAL_BLOCKS, D, W.g("norm.weight"), W.g("norm.bias"), None if dp else fc2_bias)
+        if patch is not None:
+            # the marked rows (unique, never a CLS row): the norm's backward on the compact copy, its three column sums next to the
+            # CLS rows' share, then a plain store into the rows prepare_backward left at zero
+            assert not cls_tail and G.pool != "avg" and dp is None
+            plan, pr = patch
+            sg, M = G.segs[0], plan.M
+            ops.layernorm_bwd(pr.hb.dfeats, pr.x, pr.mean, pr.rstd, W.f("norm.weight"), pr.g, pr.gb, ring[0], M, D, g_init=True,
+                              gb_scale=None if rs is None else pr.scale)
+            ops.ln_finalize(ring[0], L.LN_PARTIAL_BLOCKS, D, W.g("norm.weight"), W.g("norm.bias"), fc2_bias)
+            ops.rows_scatter(pr.g, sg.rows(G.g), plan.rows, M, D, sg.T, gb_src=pr.gb, gb=sg.rows(gb_first))
+
+    def _embed_bwd(self, W: Weights, G: VitGroup, patch):
+        """The last stage of ``backward``, per segment: token assembly and the patch embedding's gradients (``_embed``'s mirror)."""
+        D, ACC = self.D, L.EPI_ACCUM
         gpos = W.g("pos_embed").view(-1, D)
         for k, sg in enumerate(G.segs):
             ops.tokens_bwd(sg.rows(G.g), sg.gpatch, sg.dpos, None, sg.n_img, sg.N, D, accumulate=False)
@@ -1077,6 +1091,18 @@ def _check_ibot(weight, ratio, prob, gsize: int, drop: float, centering: str) ->
     return float(weight)
 
 
+def accumulate_micro(acc: Dict[torch.Tensor, torch.Tensor], table, j: int, n: int):
+    """Gradient accumulation of a step's outputs: micro-batch ``j`` of ``n`` has just written every tensor of ``table``, rows of
+    (tensor, mean).  Their running sums are kept in ``acc`` (a clone on the first micro-batch), and the last micro-batch leaves in
+    the tensor the mean over the n values (``mean``: the loss terms) or their sum (the centre sums).  n = 1: nothing is touched."""
+    if n == 1:
+        return
+    for t, mean in table:
+        acc[t] = t.clone() if j == 0 else acc[t] + t
+        if j == n - 1:
+            t.copy_(acc[t] / n if mean else acc[t])
+
+
 class TrainEngine:
     """What the two training engines share: the precision / clip-mode arguments and the loss scaler, the gradients handed out,
     and the clip / loss-scale part of the optimizer's arguments."""
@@ -1092,6 +1118,11 @@ class TrainEngine:
         self.scaler = ops.LossScaler(dev) if (L.ACT_FORMAT == "f16" and not fp32) else None
         return fp32, act
 
+    @property
+    def loss_scale(self) -> Optional[torch.Tensor]:
+        """The ``loss_scale`` argument of the loss and optimizer launches: the scaler's device scale, None without loss scaling."""
+        return self.scaler.scale if self.scaler is not None else None
+
     def grads(self) -> Dict[str, torch.Tensor]:
         """Copies of the parameter gradients of the last forward_backward.  Under float16 loss scaling the arena holds S x gradient:
         the copies are divided by the scale in force (call before optimizer_step, whose scaler update may change S)."""
@@ -1103,12 +1134,12 @@ class TrainEngine:
         """The optimizer launches' clip_norm / gnorm_sq / clip_value / loss_scale arguments; queues the gradient's sum of squares
         when they need it (under loss scaling it is also the finite check of GradScaler.step())."""
         by_norm = self.clip > 0 and self.clip_mode == "norm"
-        scaled = self.scaler is not None
-        if by_norm or scaled:
+        need_norm = by_norm or self.scaler is not None
+        if need_norm:
             ops.sumsq(self.arena.g, self.red_ws, self.gnorm_sq)
-        return dict(clip_norm=self.clip if by_norm else 0.0, gnorm_sq=self.gnorm_sq if (by_norm or scaled) else None,
+        return dict(clip_norm=self.clip if by_norm else 0.0, gnorm_sq=self.gnorm_sq if need_norm else None,
                     clip_value=self.clip if (self.clip > 0 and self.clip_mode == "value") else 0.0,
-                    loss_scale=self.scaler.scale if scaled else None)
+                    loss_scale=self.loss_scale)
 
 
 # --------------------------------------------------------------------------- #
@@ -1214,6 +1245,8 @@ class DinoEngine(TrainEngine):
         self.t = 0
         self.reducer = reducer if reducer is not None else NoReducer()
         self._n_micro = 1
+        self._drop = None             # set_dropout: (p, step seed) of the student's --drop
+        self._acc: Dict[torch.Tensor, torch.Tensor] = {}       # running sums of the step's outputs over its micro-batches (accumulate_micro)
         self._plan = None             # gradient all-reduce ranges (dist.reduction_plan), built on first use
         self._events: List[torch.cuda.Event] = []       # the SideStream pool of forward_backward
         # contiguous arena range of every block's weight-decayed matrices (arena order = backward order)
@@ -1306,62 +1339,21 @@ class DinoEngine(TrainEngine):
         ``masks``: this micro-batch's gipvit.masking.MaskPlan over the G * B global crops (crop-major, like the feature rows) --
         given exactly when ``ibot_weight`` > 0."""
         B, G, V = self.B, self.G, self.V
-        self.vit.require_trainable(self.g_stu)
-        if (masks is not None) != (self.ibot_weight > 0):
-            raise ValueError("masks= goes with ibot_weight > 0: " + ("this engine was built without the iBOT term" if masks is not None else
-                                                                       "an engine with the iBOT term needs a MaskPlan for every micro-batch"))
-        # (keywords of the iBOT term exist for a step with a plan only: without one every call below is the one it always was)
-        ikw_t = {} if masks is None else dict(patch=(masks, self.pr_t))
-        ikw_s = {} if masks is None else dict(masks=masks, patch=(masks, self.pr_s))
+        self._check_step(tiles_u8, boxes, fill, views, masks, stains)
         M = 0 if masks is None else masks.M
-        if masks is not None:
-            masks_fit(masks, self.g_stu.segs[0], self.pr_s)
-        input_form(tiles_u8, B, (self.tile, self.tile), (("fill", fill), ("boxes", boxes), ("views", views), ("stains", stains)))
-        a = self.arena
+        patch_t, patch_s = (None, None) if masks is None else ((masks, self.pr_t), (masks, self.pr_s))
         mj, mn = micro
         first, last = mj == 0, mj == mn - 1
-        if mn > 1 and getattr(self, "_drop", None):      # micro-batches of one step must not share their dropout masks
+        if mn > 1 and self._drop:      # micro-batches of one step must not share their dropout masks
             self.g_stu.set_dropout(self._drop[0], ops.dropout_site_seed(self._drop[1], 15, mj))
-        t_src, t_win, s_src, s_win = tiles_u8, [self.gwins], tiles_u8, self.s_wins
-        if boxes is not None and fill is not None:
-            raise ValueError("fill boxes are tile coordinates: they cannot be combined with re-cut random crops (boxes)")
-        if views is not None and boxes is None:
-            raise ValueError("views (per-crop augmentation draws) need boxes: the views are produced by the pass that cuts the crops")
-        if stains is not None and views is None:
-            raise ValueError("stains (per-crop stain jitter draws) need views: the jitter runs inside the view-augmentation pass")
-        if boxes is not None:
-            # random-resized crops (multicrop.MultiCropSampler): cut on the device, then every crop is its own
-            # "tile" with the single window (0, 0); rows stay crop-major like the fixed windows
-            bg, bl = boxes
-            assert bg.shape[0] == self.G * B and (self.V == self.G or bl.shape[0] == (self.V - self.G) * B)
-            if self._gcrops is None:
-                self._gcrops = _empty((self.G * B, self.gsize, self.gsize, 3), torch.uint8, self.dev)
-                self._lcrops = _empty(((self.V - self.G) * B, self.lsize, self.lsize, 3), torch.uint8, self.dev) if self.V > self.G else None
-            if views is not None and self._vstats is None:
-                self._vstats = torch.zeros(max(self.G, self.V - self.G) * B, dtype=torch.int64, device=self.dev)
-            if views is None:
-                ops.crop_resize(tiles_u8, bg, self.gsize, out=self._gcrops)
-            elif stains is None:
-                ops.crop_augment(tiles_u8, bg, views[0], self._vstats, self.gsize, out=self._gcrops)
-            else:
-                ops.crop_augment_stain(tiles_u8, bg, views[0], stains[0], self._vstats, self.gsize, out=self._gcrops)
-            t_src, t_win = self._gcrops, [[(0, 0)]]
-            s_src, s_win = [self._gcrops], [[(0, 0)]]
-            if self.V > self.G:
-                if views is None:
-                    ops.crop_resize(tiles_u8, bl, self.lsize, out=self._lcrops)
-                elif stains is None:
-                    ops.crop_augment(tiles_u8, bl, views[1], self._vstats, self.lsize, out=self._lcrops)
-                else:
-                    ops.crop_augment_stain(tiles_u8, bl, views[1], stains[1], self._vstats, self.lsize, out=self._lcrops)
-                s_src.append(self._lcrops); s_win.append([(0, 0)])
+        t_src, t_win, s_src, s_win = self._cut_crops(tiles_u8, boxes, views, stains)
         sx = SideStream(self.vit.side if tiles_u8.is_cuda else None, self._events)
 
         def fills():
             # fills nothing in the forward depends on (the gradient arena, the backward's zero-initialised scratch): on the side
             # stream, beside the forward pass (without one, the backward zeroes its scratch when it starts)
             if first:
-                a.g.zero_()
+                self.arena.g.zero_()
             if sx.side is not None:
                 self.vit.prepare_backward(self.g_stu)
 
@@ -1370,13 +1362,13 @@ class DinoEngine(TrainEngine):
         t_side = sx.side is not None and self.sw.teacher_side
 
         def teacher():
-            self.vit.forward(self.tW, self.g_teach, t_src, t_win, self.mean, self.std, self.hb_t.feats, fill=fill, on_side=t_side, **ikw_t)
+            self.vit.forward(self.tW, self.g_teach, t_src, t_win, self.mean, self.std, self.hb_t.feats, fill=fill, on_side=t_side, patch=patch_t)
             self.head.forward(self.tH, self.wn_t, self.hb_t, on_side=t_side)
             if M > 0:
                 self.head.forward(self.tH, self.wn_t, self.pr_t.hb, on_side=t_side, rows=M)
         ev_zero = sx.run(fills)
         ev_teacher = sx.run(teacher) if t_side else teacher()
-        self.vit.forward(self.sW, self.g_stu, s_src, s_win, self.mean, self.std, self.hb_s.feats, fill=fill, **ikw_s)
+        self.vit.forward(self.sW, self.g_stu, s_src, s_win, self.mean, self.std, self.hb_s.feats, fill=fill, masks=masks, patch=patch_s)
         if self.koleo_weight > 0:
             ops.koleo_fwd(self.hb_s.feats, self.koleo_ws, self.koleo_nn, self.koleo, G, B, self.D)
         self.head.forward(self.sH, self.wn_s, self.hb_s)
@@ -1385,33 +1377,19 @@ class DinoEngine(TrainEngine):
         sx.join(ev_teacher)
         center = self.center if self.centering == "center" else self._sinkhorn()
         ops.dino_loss(self.hb_s.logits, self.hb_t.logits, center, self.hb_s.dlogits, self.loss, self.center_sum,
-                      self.loss_ws, B, V, G, self.K, self.ts, self.tt, hyper=self.hyper,
-                      loss_scale=self.scaler.scale if self.scaler is not None else None)
+                      self.loss_ws, B, V, G, self.K, self.ts, self.tt, hyper=self.hyper, loss_scale=self.loss_scale)
         if masks is not None:
             if M > 0:
                 ops.ibot_loss(self.pr_s.hb.logits, self.pr_t.hb.logits, self.patch_center, masks.weight, self.pr_s.hb.dlogits, self.ibot,
                               self.patch_center_sum, self.ibot_ws, M, self.K, self.ts, self.tt, self.ibot_weight, hyper=self.hyper,
-                              loss_scale=self.scaler.scale if self.scaler is not None else None)
+                              loss_scale=self.loss_scale)
             else:       # no marked patch on this rank: no patch launch, the term is 0 and the rank adds nothing to the centre
                 self.ibot.zero_(); self.patch_center_sum.zero_()
-            if mn > 1:  # the mean over the micro-batches like the loss; sums and count add up like the CLS centre's
-                self._ibot_acc = self.ibot.clone() if first else self._ibot_acc + self.ibot
-                self._pcenter_acc = self.patch_center_sum.clone() if first else self._pcenter_acc + self.patch_center_sum
-                if last:
-                    self.ibot.copy_(self._ibot_acc / mn); self.patch_center_sum.copy_(self._pcenter_acc)
+            # the mean over the micro-batches like the loss; sums and count add up like the CLS centre's
+            accumulate_micro(self._acc, ((self.ibot, True), (self.patch_center_sum, False)), mj, mn)
             if last:
                 self.reducer.reduce_tensor(self.patch_center_sum)
-        if mn > 1:
-            if first:
-                self._loss_acc, self._center_acc = self.loss.clone(), self.center_sum.clone()
-            else:
-                self._loss_acc += self.loss; self._center_acc += self.center_sum
-            if last:
-                self.loss.copy_(self._loss_acc / mn); self.center_sum.copy_(self._center_acc)
-            if self.koleo_weight > 0:       # the mean over the micro-batches, like the loss
-                self._koleo_acc = self.koleo.clone() if first else self._koleo_acc + self.koleo
-                if last:
-                    self.koleo.copy_(self._koleo_acc / mn)
+        accumulate_micro(self._acc, ((self.loss, True), (self.center_sum, False)) + (((self.koleo, True),) if self.koleo_weight > 0 else ()), mj, mn)
         if last:
             self.reducer.reduce_tensor(self.center_sum)
         sx.join(ev_zero)
@@ -1419,27 +1397,68 @@ class DinoEngine(TrainEngine):
         if M > 0:       # the marked rows through the same head: its weight gradients accumulate behind the CLS rows'
             self.head.backward(self.sH, self.wn_s, self.pr_s.hb, self.train_last_layer, sx, rows=M)
         if self.koleo_weight > 0:       # into the global crops' rows of the feature gradient, under the loss scale the DINO term carries
-            ops.koleo_bwd(self.hb_s.dfeats, self.koleo_ws, self.koleo_nn, G, B, self.D, self.koleo_weight,
-                          loss_scale=self.scaler.scale if self.scaler is not None else None)
-        if not last:        # more micro-batches follow: gradients keep accumulating locally
-            self.vit.backward(self.sW, self.g_stu, self.hb_s.dfeats, **({} if masks is None else dict(patch=(masks, self.pr_s))))
-            return
+            ops.koleo_bwd(self.hb_s.dfeats, self.koleo_ws, self.koleo_nn, G, B, self.D, self.koleo_weight, loss_scale=self.loss_scale)
         # The gradient all-reduce goes out as a few contiguous arena ranges, each as soon as it is final (dist.reduction_plan):
         # the head's matrices when the head backward ends, then coalesced block ranges of >= 25 MB from the side stream (the
         # block's weight gradients are produced there), then block 0 + patch embed + the no-decay tail as ONE message when
         # backward ends -- RCCL's stream runs beside the remaining backward (reference: NativeDDP's buckets, train.py:634, 1071)
-        plan = self._reduction_plan()
-        active = self.reducer.world > 1 or getattr(self.reducer, "always", False)
+        if last:        # (before the last micro-batch gradients keep accumulating locally)
+            sx.then(lambda: self._release("head"))     # behind the head's weight gradients, which were queued on the side stream
+        self.vit.backward(self.sW, self.g_stu, self.hb_s.dfeats, on_block_done=self._release if last else None, patch=patch_s)
+        if last:
+            self._release("end")
+            self.reducer.finish()
 
-        def release(trigger):
-            if active:
-                for trg, lo, hi in plan:
-                    if trg == trigger:
-                        self.reducer.reduce_range(a.g, lo, hi)
-        sx.then(lambda: release("head"))     # behind the head's weight gradients, which were queued on the side stream
-        self.vit.backward(self.sW, self.g_stu, self.hb_s.dfeats, on_block_done=release, **({} if masks is None else dict(patch=(masks, self.pr_s))))
-        release("end")
-        self.reducer.finish()
+    def _check_step(self, tiles_u8, boxes, fill, views, masks, stains):
+        """Everything ``forward_backward`` refuses, raised before its first launch."""
+        self.vit.require_trainable(self.g_stu)
+        if (masks is not None) != (self.ibot_weight > 0):
+            raise ValueError("masks= goes with ibot_weight > 0: " + ("this engine was built without the iBOT term" if masks is not None else
+                                                                       "an engine with the iBOT term needs a MaskPlan for every micro-batch"))
+        if masks is not None:
+            masks_fit(masks, self.g_stu.segs[0], self.pr_s)
+        input_form(tiles_u8, self.B, (self.tile, self.tile), (("fill", fill), ("boxes", boxes), ("views", views), ("stains", stains)))
+        if boxes is not None and fill is not None:
+            raise ValueError("fill boxes are tile coordinates: they cannot be combined with re-cut random crops (boxes)")
+        if views is not None and boxes is None:
+            raise ValueError("views (per-crop augmentation draws) need boxes: the views are produced by the pass that cuts the crops")
+        if stains is not None and views is None:
+            raise ValueError("stains (per-crop stain jitter draws) need views: the jitter runs inside the view-augmentation pass")
+        if boxes is not None:
+            bg, bl = boxes
+            assert bg.shape[0] == self.G * self.B and (self.V == self.G or bl.shape[0] == (self.V - self.G) * self.B)
+
+    def _cut_crops(self, tiles_u8, boxes, views, stains):
+        """-> (t_src, t_win, s_src, s_win), the sources and windows of the teacher's and the student's ``VitRunner.forward``: the
+        tiles under the fixed windows, or with ``boxes`` the crops cut here."""
+        if boxes is None:
+            return tiles_u8, [self.gwins], tiles_u8, self.s_wins
+        # random-resized crops (multicrop.MultiCropSampler): cut on the device, then every crop is its own
+        # "tile" with the single window (0, 0); rows stay crop-major like the fixed windows
+        B, n_local = self.B, self.V - self.G
+        if self._gcrops is None:
+            self._gcrops = _empty((self.G * B, self.gsize, self.gsize, 3), torch.uint8, self.dev)
+            self._lcrops = _empty((n_local * B, self.lsize, self.lsize, 3), torch.uint8, self.dev) if n_local else None
+        if views is not None and self._vstats is None:
+            self._vstats = torch.zeros(max(self.G, n_local) * B, dtype=torch.int64, device=self.dev)
+
+        def cut(k, size, out):      # crop group k (0 global, 1 local): plain, with every crop's view chain, or with its stain jitter ahead of that
+            if views is None:
+                ops.crop_resize(tiles_u8, boxes[k], size, out=out)
+            elif stains is None:
+                ops.crop_augment(tiles_u8, boxes[k], views[k], self._vstats, size, out=out)
+            else:
+                ops.crop_augment_stain(tiles_u8, boxes[k], views[k], stains[k], self._vstats, size, out=out)
+            return out
+        crops = [cut(0, self.gsize, self._gcrops)] + ([cut(1, self.lsize, self._lcrops)] if n_local else [])
+        return crops[0], [[(0, 0)]], crops, [[(0, 0)]] * len(crops)
+
+    def _release(self, trigger):
+        """Queue the all-reduce of the plan's ranges that ``trigger`` ("head", a block number, "end") completes."""
+        if self.reducer.world > 1 or getattr(self.reducer, "always", False):
+            for trg, lo, hi in self._reduction_plan():
+                if trg == trigger:
+                    self.reducer.reduce_range(self.arena.g, lo, hi)
 
     def _sinkhorn(self) -> torch.Tensor:
         """Sinkhorn-Knopp centring of this step's teacher logits (include/gipvit.h), 2 n + 1 calls (4 n + 1 kernel launches) on the
@@ -1503,7 +1522,7 @@ class DinoEngine(TrainEngine):
         for j, tb in enumerate(tile_batches):
             if input_form(tb, self.B, (self.tile, self.tile)) == "u8":
                 assert tb.shape == (self.B, self.tile, self.tile, 3)
-            self.forward_backward(tb, micro=(j, n), **({} if masks is None else dict(masks=masks[j])))
+            self.forward_backward(tb, micro=(j, n), masks=None if masks is None else masks[j])
         self._n_micro = n
         try:
             self.optimizer_step()
@@ -1519,8 +1538,7 @@ class DinoEngine(TrainEngine):
         if input_form(tiles_u8, self.B, (self.tile, self.tile), (("fill", fill), ("boxes", boxes), ("views", views), ("stains", stains))) == "u8":
             assert tiles_u8.shape == (self.B, self.tile, self.tile, 3)
         self.set_hyper(**sched)
-        self.forward_backward(tiles_u8, boxes=boxes, fill=fill, views=views, **({} if masks is None else dict(masks=masks)),
-                              **({} if stains is None else dict(stains=stains)))
+        self.forward_backward(tiles_u8, boxes=boxes, fill=fill, views=views, masks=masks, stains=stains)
         self.optimizer_step()
         return self.loss
 
@@ -1663,8 +1681,8 @@ class SupervisedEngine(TrainEngine):
     def _forward(self, tiles_u8, ema, fill, mix, erase):
         B, C, D, W = self.B, self.C, self.D, (self.Wema if ema else self.W)
         input_form(tiles_u8, B, None, (("fill", fill),))
-        ekw = {} if erase is None else {"erase": (erase.table, erase.seed)}
-        self.vit.forward(W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats, fill=fill, mix=None if mix is None else mix.table, **ekw)
+        self.vit.forward(W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats, fill=fill, mix=None if mix is None else mix.table,
+                         erase=None if erase is None else (erase.table, erase.seed))
         ops.small_matmul(self.feats, W.f("head.weight"), self.logits, B, C, D, sam=D, sak=1, sbk=1, sbn=D, bias=W.f("head.bias"))
         return self.logits, self.feats
 
@@ -1679,13 +1697,12 @@ class SupervisedEngine(TrainEngine):
         self.vit.require_trainable(self.grp)
         self.arena.g.zero_()
         self._forward(tiles_u8, False, fill, mix, erase)
-        loss_scale = self.scaler.scale if self.scaler is not None else None
         if self.loss_kind == "lsce":
-            ops.softmax_lsce(self.logits, target.view(-1), self.loss, self.dlogits, self.prob, B, C, self.smoothing, loss_scale=loss_scale)
+            ops.softmax_lsce(self.logits, target.view(-1), self.loss, self.dlogits, self.prob, B, C, self.smoothing, loss_scale=self.loss_scale)
         else:
             ops.softmax_mix_loss(self.logits, target.view(-1), self.loss, self.dlogits, self.prob, B, C, self.smoothing, self.loss_kind,
                                  partner=None if mix is None else mix.partner, lam=None if mix is None else mix.lam,
-                                 threshold=self.bce_target_thresh, loss_scale=loss_scale)
+                                 threshold=self.bce_target_thresh, loss_scale=self.loss_scale)
         # head backward: dW = dlogits^T f, db = colsum(dlogits), df = dlogits W
         ops.small_matmul(self.dlogits, self.feats, W.g("head.weight"), C, D, B, sam=1, sak=C, sbk=D, sbn=1, accumulate=True)
         ops.small_matmul(self.ones, self.dlogits, W.g("head.bias").view(1, C), 1, C, B, sam=0, sak=1, sbk=C, sbn=1, accumulate=True)
@@ -1787,9 +1804,8 @@ class FeatureExtractor:
         self.grp = VitGroup(arch, [(batch, img_size)], img_size, dev, save=False, act=act, pool=self.pool)
         self.feats = _empty((batch, self.D), act, dev)
         self.logits = _empty((batch, num_classes), f32, dev) if num_classes else None
-        self._pad = self._pad_f32 = None
-        self._scratch: Dict[str, torch.Tensor] = {}      # capture buffers of a padded last batch (_out_or_scratch)
-        self._tok_stats = None                             # f32 [2, T]: LayerNorm statistics of captured tokens
+        self._pad: Dict[str, torch.Tensor] = {}          # the zero-padded last batch per input form (_batches)
+        self._scratch: Dict[str, torch.Tensor] = {}      # capture buffers of a padded last batch, token statistics (_scratch_buf)
         self._stain = self._stain_buf = None               # set_stain: B copies of the slide's gv_stain_params record, device
 
     def set_stain(self, record) -> None:
@@ -1823,8 +1839,7 @@ class FeatureExtractor:
             assert tiles_u8.shape == (self.B, self.img, self.img, 3)
         elif self._stain is not None:
             raise ValueError("a stain record is set (set_stain): float32 NCHW input is already normalised and cannot be stain-normalised")
-        skw = {} if self._stain is None else {"stain": self._stain}
-        self.vit.forward(self.W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats, capture=capture, **skw)
+        self.vit.forward(self.W, self.grp, tiles_u8, [[(0, 0)]], self.mean, self.std, self.feats, capture=capture, stain=self._stain)
         if self.C:
             ops.small_matmul(self.feats, self.W.f("head.weight"), self.logits, self.B, self.C, self.D, sam=self.D, sak=1, sbk=1, sbn=self.D,
                              bias=self.W.f("head.bias"))
@@ -1838,16 +1853,11 @@ class FeatureExtractor:
             hi = min(n, lo + self.B)
             part = tiles_u8[lo:hi]
             if hi - lo < self.B:
-                if form == "u8":
-                    if self._pad is None:
-                        self._pad = torch.zeros(self.B, self.img, self.img, 3, dtype=torch.uint8, device=self.dev)
-                    pad = self._pad
-                else:
-                    if self._pad_f32 is None:
-                        self._pad_f32 = torch.zeros(self.B, 3, self.img, self.img, dtype=f32, device=self.dev)
-                    pad = self._pad_f32
-                pad[: hi - lo].copy_(part)
-                part = pad
+                if form not in self._pad:
+                    shape = (self.B, self.img, self.img, 3) if form == "u8" else (self.B, 3, self.img, self.img)
+                    self._pad[form] = torch.zeros(shape, dtype=tiles_u8.dtype, device=self.dev)
+                self._pad[form][: hi - lo].copy_(part)
+                part = self._pad[form]
             yield lo, hi, part
 
     def run(self, tiles_u8: torch.Tensor):
@@ -1863,31 +1873,42 @@ class FeatureExtractor:
         self._check_size(tiles_u8)
         self.vit.require_attention_maps(self.grp)
         attn = torch.empty(tiles_u8.shape[0], self.vit.H, self.grp.segs[0].N, dtype=f32, device=self.dev)
-        feats, logits = self._run(tiles_u8, attn)
-        return feats, logits, attn
+        return (*self._run(tiles_u8, attn), attn)
 
     def _run(self, tiles_u8, attn):
         n = tiles_u8.shape[0]
         feats = torch.empty(n, self.D, dtype=f32, device=self.dev)
         logits = torch.empty(n, self.C, dtype=f32, device=self.dev) if self.C else None
-        for lo, hi, part in self._batches(tiles_u8):
-            cap = None if attn is None else Capture(attn=self._out_or_scratch(attn, lo, hi, "_cls_attn"), attn_rows=1)
-            f, l = self.forward(part, cap)
+        outs = [] if attn is None else [("_cls_attn", attn)]
+        for lo, hi, f, l in self._captured(tiles_u8, outs, lambda bufs: Capture(attn=bufs[0], attn_rows=1) if bufs else None):
             feats[lo:hi].copy_(f[: hi - lo])
             if logits is not None:
                 logits[lo:hi].copy_(l[: hi - lo])
-            if cap is not None and hi - lo < self.B:
-                attn[lo:hi].copy_(cap.attn[: hi - lo])
         return feats, logits
 
-    def _out_or_scratch(self, out: torch.Tensor, lo: int, hi: int, name: str) -> torch.Tensor:
-        """The capture buffer of batch [lo, hi): the output rows themselves when the batch is full, else a B-row scratch (kept)."""
-        if hi - lo == self.B:
-            return out[lo:hi]
+    def _captured(self, tiles_u8, outs, capture):
+        """The batched pass of every entry point over any number of tiles.  Per batch (``_batches``): a capture buffer for each (scratch
+        name, [n, ...] output) of ``outs`` -- the output's rows themselves when the batch is full, else a B-row scratch --, ``forward`` with
+        ``capture(buffers)``, a yield of (lo, hi, features, logits), then the rows of a partial batch copied from the scratch to the outputs."""
+        for lo, hi, part in self._batches(tiles_u8):
+            full = hi - lo == self.B
+            bufs = [out[lo:hi] if full else self._scratch_buf(name, (self.B,) + tuple(out.shape[1:])) for name, out in outs]
+            yield (lo, hi) + self.forward(part, capture(bufs))
+            if not full:
+                for (_, out), b in zip(outs, bufs):
+                    out[lo:hi].copy_(b[: hi - lo])
+
+    def _scratch_buf(self, name: str, shape) -> torch.Tensor:
+        """The f32 scratch ``name`` of ``shape`` (allocated on first use and kept, again when the shape changes)."""
         buf = self._scratch.get(name)
-        if buf is None or buf.shape[1:] != out.shape[1:]:
-            buf = self._scratch[name] = torch.empty((self.B,) + tuple(out.shape[1:]), dtype=out.dtype, device=self.dev)
+        if buf is None or tuple(buf.shape) != tuple(shape):
+            buf = self._scratch[name] = torch.empty(tuple(shape), dtype=f32, device=self.dev)
         return buf
+
+    def _token_capture(self, bufs) -> Capture:
+        """The ``Capture`` of the final norm's tokens into ``bufs`` (f32 [B, N, D] each), with the LayerNorm statistics scratch they share."""
+        T = self.grp.T
+        return Capture(tokens=[b.view(T, self.D) for b in bufs], stats=self._scratch_buf("_tok_stats", (2, T)))
 
     def _check_size(self, tiles_u8: torch.Tensor):
         form = input_form(tiles_u8, None, (self.img, self.img))       # (float32 NCHW of another size: ValueError there)
@@ -1903,11 +1924,8 @@ class FeatureExtractor:
         N, H = self.grp.segs[0].N, self.vit.H
         q = 1 if cls_only else N
         out = torch.empty(tiles_u8.shape[0], H, q, N, dtype=f32, device=self.dev)
-        for lo, hi, part in self._batches(tiles_u8):
-            buf = self._out_or_scratch(out, lo, hi, "_attn_buf")
-            self.forward(part, Capture(attn=buf, attn_rows=q))
-            if hi - lo < self.B:
-                out[lo:hi].copy_(buf[: hi - lo])
+        for _ in self._captured(tiles_u8, [("_attn_buf", out)], lambda bufs: Capture(attn=bufs[0], attn_rows=q)):
+            pass        # (the capture is the output)
         return out
 
     def intermediate_layers(self, tiles_u8: torch.Tensor, n: int = 1) -> List[torch.Tensor]:
@@ -1919,16 +1937,9 @@ class FeatureExtractor:
         self._check_size(tiles_u8)
         if not 1 <= n <= self.vit.depth:
             raise ValueError(f"intermediate_layers: n = {n}, need 1 <= n <= depth = {self.vit.depth}")
-        N, D, T = self.grp.segs[0].N, self.D, self.grp.T
-        outs = [torch.empty(tiles_u8.shape[0], N, D, dtype=f32, device=self.dev) for _ in range(n)]
-        if self._tok_stats is None:
-            self._tok_stats = torch.empty(2, T, dtype=f32, device=self.dev)
-        for lo, hi, part in self._batches(tiles_u8):
-            bufs = [self._out_or_scratch(o, lo, hi, f"_tok_buf{k}") for k, o in enumerate(outs)]
-            self.forward(part, Capture(tokens=[b.view(T, D) for b in bufs], stats=self._tok_stats))
-            if hi - lo < self.B:
-                for o, b in zip(outs, bufs):
-                    o[lo:hi].copy_(b[: hi - lo])
+        outs = [torch.empty(tiles_u8.shape[0], self.grp.segs[0].N, self.D, dtype=f32, device=self.dev) for _ in range(n)]
+        for _ in self._captured(tiles_u8, [(f"_tok_buf{k}", o) for k, o in enumerate(outs)], self._token_capture):
+            pass        # (the capture is the output)
         return outs
 
     def probe_features(self, tiles_u8: torch.Tensor, n_last: int = 4, avgpool: bool = False) -> torch.Tensor:
@@ -1944,20 +1955,9 @@ class FeatureExtractor:
             raise ValueError(f"probe_features: n_last = {n_last}, need 1 <= n_last <= depth = {self.vit.depth}")
         N, D, T, B = self.grp.segs[0].N, self.D, self.grp.T, self.B
         out = torch.empty(tiles_u8.shape[0], (n_last + bool(avgpool)) * D, dtype=f32, device=self.dev)
-        bufs = []
-        for k in range(n_last):
-            buf = self._scratch.get(f"_tok_buf{k}")
-            if buf is None or tuple(buf.shape) != (B, N, D):
-                buf = self._scratch[f"_tok_buf{k}"] = torch.empty(B, N, D, dtype=f32, device=self.dev)
-            bufs.append(buf)
-        if self._tok_stats is None:
-            self._tok_stats = torch.empty(2, T, dtype=f32, device=self.dev)
-        if avgpool:
-            pooled = self._scratch.get("_probe_pool")
-            if pooled is None:
-                pooled = self._scratch["_probe_pool"] = torch.empty(B, D, dtype=f32, device=self.dev)
-        for lo, hi, part in self._batches(tiles_u8):
-            self.forward(part, Capture(tokens=[b.view(T, D) for b in bufs], stats=self._tok_stats))
+        bufs = [self._scratch_buf(f"_tok_buf{k}", (B, N, D)) for k in range(n_last)]       # (every batch through the scratch: no [n, N, D] output)
+        pooled = self._scratch_buf("_probe_pool", (B, D)) if avgpool else None
+        for lo, hi, _, _ in self._captured(tiles_u8, [], lambda _: self._token_capture(bufs)):
             for k, b in enumerate(bufs):
                 out[lo:hi, k * D:(k + 1) * D].copy_(b[: hi - lo, 0, :])          # the CLS rows: a strided copy
             if avgpool:

@@ -221,6 +221,97 @@ def fx():
     return eng
 
 
+def _masks(eng, marked):
+    """A MaskPlan over the engine's G * B global crops: ``marked`` patches in the first image, none elsewhere."""
+    import numpy as np
+    from gipvit.masking import MaskPlan
+    m = np.zeros((eng.G * eng.B, (eng.gsize // 16) ** 2), np.bool_)
+    m[0, 3:3 + marked] = True
+    return MaskPlan(m, "cpu")
+
+
+def dino_s_ibot():
+    eng = _dino("vit_small", ibot_weight=1.0)
+    eng.step(_tiles(1, 256), masks=_masks(eng, 20))
+    return eng
+
+
+def dino_t_ibot_micro():
+    eng = _dino("vit_tiny", ibot_weight=1.0)          # the first micro-batch marks nothing: the M = 0 fills, then the sums
+    eng.set_drop_path(torch.ones(12, 2, eng.V * eng.B))
+    eng.step_micro([_tiles(1, 256)] * 2, masks=[_masks(eng, 0), _masks(eng, 9)])
+    return eng
+
+
+def dino_s_sk_koleo():
+    eng = _dino("vit_small", batch=2, centering="sinkhorn_knopp", koleo_weight=0.1)
+    eng.step_micro([_tiles(2, 256)] * 2)
+    return eng
+
+
+def dino_t_views_stains():
+    from gipvit.engine import DinoEngine
+    from gipvit.multicrop import MultiCropSampler, ViewAugmentSampler
+    from gipvit.stain import StainJitterSampler
+    eng = DinoEngine(arch="vit_tiny", img_size=224, out_dim=256, batch=2, n_local=2, device="cpu")
+    boxes = MultiCropSampler(2, 256, 2, 2, seed=1).sample()
+    views = ViewAugmentSampler(2, 2, 2, seed=2).sample()
+    stains = StainJitterSampler(2, 2, 2, 0.2, seed=3).sample()
+    eng.step(_tiles(2, 256), boxes=boxes)
+    eng.step(_tiles(2, 256), boxes=boxes, views=views)
+    eng.step(_tiles(2, 256), boxes=boxes, views=views, stains=stains)
+    eng.step(_tiles(2, 256), fill=torch.zeros(2, 8))
+    eng.step(torch.zeros(2, 3, 256, 256))
+    return eng
+
+
+def _erase_plan():
+    from gipvit.erasing import ErasePlan
+    rows = ErasePlan.make_rows(2)
+    ErasePlan.add_box(rows, 1, (1, 9, 2, 30), (0.5, 0.5, 0.5))
+    return ErasePlan(rows, seed=77)
+
+
+def sup_t_mix_erase():
+    from gipvit.mixup import MixPlan
+    eng, plan, tgt = _sup(loss="soft_ce"), _erase_plan(), torch.zeros(2, 1, dtype=torch.int64)
+    eng.step(_tiles(2, 64), tgt, fill=torch.zeros(2, 8), erase=plan)
+    eng.step(torch.zeros(2, 3, 64, 64), tgt, mix=MixPlan(MixPlan.make_rows(2)), erase=plan)
+    eng.forward(_tiles(2, 64))
+    return eng
+
+
+def sup_t_avg_drop():
+    eng = _sup(global_pool="avg")
+    eng.set_dropout(0.1, 5)
+    eng.set_drop_path(torch.ones(12, 2, 2))
+    eng.step(_tiles(2, 64), torch.zeros(2, 1, dtype=torch.int64))
+    return eng
+
+
+def fx_stain_512():
+    from gipvit import ops
+    from gipvit.engine import FeatureExtractor
+    eng = FeatureExtractor(arch="vit_tiny", img_size=512, batch=1, device="cpu")       # 1025 tokens: the streaming attention forward
+    eng.set_stain(torch.zeros(ops._STAIN_PARAMS_BYTES, dtype=torch.uint8))
+    eng.run(_tiles(1, 512))
+    eng.set_stain(None)
+    eng.probe_features(_tiles(1, 512), n_last=2, avgpool=True)
+    return eng
+
+
+def fx_padded():
+    """Every batched capture on a padded last batch, float input included."""
+    from gipvit.engine import FeatureExtractor
+    eng = FeatureExtractor(arch="vit_tiny", img_size=64, batch=2, device="cpu")
+    tiles = _tiles(3, 64)
+    eng.last_selfattention(tiles, cls_only=True)
+    eng.probe_features(tiles, n_last=2, avgpool=True)
+    eng.intermediate_layers(tiles, n=3)             # the scratch of probe_features, and one more
+    eng.run(torch.zeros(3, 3, 64, 64))
+    return eng
+
+
 # id -> (EngineSwitches fields that differ from the defaults, run)
 CONFIGS = {
     "dino_s": ({}, lambda: _dino_step("vit_small")),
@@ -236,6 +327,18 @@ CONFIGS = {
     "sup_lamb": ({}, lambda: _sup_step(opt="lamb")),
     "sup_agc_head": ({}, lambda: _sup_step(clip_mode="agc", clip_grad=0.01, train_backbone=False)),
     "fx": ({}, fx),
+    "dino_s_ibot": ({}, dino_s_ibot),
+    "dino_t_ibot_micro": ({}, dino_t_ibot_micro),
+    "dino_s_sk_koleo": ({}, dino_s_sk_koleo),
+    "dino_t_views_stains": ({}, dino_t_views_stains),
+    "sup_t_mix_erase": ({}, sup_t_mix_erase),
+    "sup_t_avg_drop": ({}, sup_t_avg_drop),
+    "fx_stain_512": ({}, fx_stain_512),
+    "fx_padded": ({}, fx_padded),
+    "dino_t_teacher_inline": (dict(teacher_side=False), lambda: _dino_step("vit_tiny")),
+    "dino_s_unfused_mlp": (dict(fused_mlp=False), lambda: _dino_step("vit_small")),
+    "dino_s_unfused_ln": (dict(fused_ln=False, cls_qlimit=False, varlen_attn=False), lambda: _dino_step("vit_small")),
+    "sup_ld_head": ({}, lambda: _sup_step(layer_decay=0.75, train_backbone=False)),
 }
 
 
