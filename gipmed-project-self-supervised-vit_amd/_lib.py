@@ -121,6 +121,8 @@ gv_attention_fwd_args = _struct("gv_attention_fwd_args", [
     ("qkv", vp), ("o", vp), ("lse", vp), ("n_img", i32), ("N", i32), ("H", i32), ("scale", f32), ("q_limit", i32)])
 gv_attention_bwd_args = _struct("gv_attention_bwd_args", [
     ("qkv", vp), ("o", vp), ("d_o", vp), ("lse", vp), ("dqkv", vp), ("n_img", i32), ("N", i32), ("H", i32), ("scale", f32), ("q_limit", i32)])
+gv_attention_bwd_stream_args = _struct("gv_attention_bwd_stream_args", [
+    ("qkv", vp), ("o", vp), ("d_o", vp), ("lse", vp), ("dqkv", vp), ("delta", vp), ("n_img", i32), ("N", i32), ("H", i32), ("scale", f32), ("q_limit", i32)])
 gv_attention_probs_args = _struct("gv_attention_probs_args", [
     ("qkv", vp), ("lse", vp), ("p", vp), ("n_img", i32), ("N", i32), ("H", i32), ("scale", f32), ("q_rows", i32)])
 gv_cls_rows_args = _struct("gv_cls_rows_args", [("x", vp), ("cls", vp), ("pos", vp), ("n_img", i32), ("N", i32), ("D", i32)])
@@ -214,7 +216,7 @@ ENTRY_POINTS = {
     "gv_patchify": gv_patchify_args, "gv_patchify_nchw": gv_patchify_nchw_args, "gv_crop_resize": gv_crop_resize_args, "gv_crop_augment": gv_crop_augment_args, "gv_crop_augment_stain": gv_crop_augment_stain_args, "gv_augment": gv_augment_args, "gv_layernorm_fwd": gv_layernorm_fwd_args, "gv_layernorm_bwd": gv_layernorm_bwd_args,
     "gv_colsum_finalize": gv_colsum_finalize_args, "gv_ln_finalize": gv_ln_finalize_args, "gv_colsum": gv_colsum_args, "gv_linear": gv_linear_args,
     "gv_linear_ln_fwd": gv_linear_ln_fwd_args, "gv_mlp_ln_fwd": gv_mlp_ln_fwd_args, "gv_linear_ln_bwd": gv_linear_ln_bwd_args, "gv_expand_rows": gv_expand_rows_args, "gv_linear_dw_group": gv_linear_dw_group_args,
-    "gv_attention_fwd": gv_attention_fwd_args, "gv_attention_fwd_stream": gv_attention_fwd_args, "gv_attention_fwd_varlen": gv_attention_fwd_varlen_args, "gv_attention_bwd": gv_attention_bwd_args, "gv_attention_bwd_varlen": gv_attention_bwd_varlen_args,
+    "gv_attention_fwd": gv_attention_fwd_args, "gv_attention_fwd_stream": gv_attention_fwd_args, "gv_attention_fwd_varlen": gv_attention_fwd_varlen_args, "gv_attention_bwd": gv_attention_bwd_args, "gv_attention_bwd_stream": gv_attention_bwd_stream_args, "gv_attention_bwd_varlen": gv_attention_bwd_varlen_args,
     "gv_attention_probs": gv_attention_probs_args, "gv_cls_rows": gv_cls_rows_args,
     "gv_tokens_bwd": gv_tokens_bwd_args, "gv_small_matmul": gv_small_matmul_args, "gv_l2norm_fwd": gv_l2norm_fwd_args,
     "gv_l2norm_bwd": gv_l2norm_bwd_args, "gv_weightnorm_fwd": gv_weightnorm_fwd_args, "gv_weightnorm_bwd": gv_weightnorm_bwd_args,

@@ -1,6 +1,6 @@
 // Streaming attention forward for sequences past one workgroup's LDS (N <= GV_ATTN_STREAM_MAX_N, head_dim 64): the forward of
 // attention.hip with K / V passed through LDS in 64-key blocks and an online softmax, so that inference runs on tiles up to
-// 512 px (1 025 tokens).  Forward only: nothing here is saved for, or read by, a backward past GV_ATTN_MAX_N tokens.
+// 512 px (1 025 tokens).  Its backward is attention_stream_bwd.hip (gv_attention_bwd_stream), which reads the o / lse left here.
 //
 // A workgroup = one (image, head) pair x one block of GV_ATTN_STREAM_QBLOCK = 128 query rows: 4 waves of 32 queries, Q fragments
 // in registers.  K / V key blocks are double buffered in the swizzled image of attn_tiles.h, filled by LDS-DMA: block j + 1 is

@@ -1,6 +1,6 @@
 // Which kernel an attention call gets and with what launch geometry -- gv_attention_fwd / _bwd / _probs, the varlen calls and
-// gv_attention_fwd_stream (include/gipvit.h).  This is the ONE place where the length classes, the per-class workgroup shapes, the
-// dynamic LDS sizes and the occupancy promises are stated: the kernels of attention.hip / attention_stream.hip take their
+// gv_attention_fwd_stream / gv_attention_bwd_stream (include/gipvit.h).  This is the ONE place where the length classes, the per-class workgroup shapes, the
+// dynamic LDS sizes and the occupancy promises are stated: the kernels of attention.hip / attention_stream.hip / attention_stream_bwd.hip take their
 // constants from the Cfg structs below, the launchers launch the Launch the same structs give.  Pure host C++17, no HIP: the
 // header compiles with a plain g++ (tests/attn_plan_main.cc replays tests/traces/attention_plans.json through it).
 #pragma once
@@ -13,7 +13,7 @@ constexpr int ROW = 128;                                    // bytes of one toke
 constexpr int ceil_div(int a, int b) { return (a + b - 1) / b; }
 struct Launch { long grid; int block, lds_bytes; };         // workgroups, threads per workgroup, dynamic LDS
 
-// what every entry point asks of its shape (max_n: GV_ATTN_MAX_N, or GV_ATTN_STREAM_MAX_N for the streaming forward)
+// what every entry point asks of its shape (max_n: GV_ATTN_MAX_N, or GV_ATTN_STREAM_MAX_N for the streaming calls)
 constexpr bool shape_ok(int n_img, int H, int N, int max_n) { return n_img > 0 && H > 0 && N > 0 && N <= max_n; }
 
 // ---------------------------------------------------------------------------------
@@ -134,6 +134,34 @@ struct StreamCfg {
     // q_limit > 0: whole query blocks that hold a row < q_limit
     static constexpr int query_blocks(int N, int q_limit) { return ceil_div(q_limit > 0 && q_limit < N ? q_limit : N, QB); }
     static Launch launch(int n_img, int H, int N, int q_limit) { return {(long)n_img * H * query_blocks(N, q_limit), THREADS, LDS}; }
+};
+
+// ---------------------------------------------------------------------------------
+// streaming backward (gv_attention_bwd_stream): two launches, the second behind the first on the stream
+//   dQ:       a workgroup = one pair x one block of QB query rows (the forward's shape), K / V double buffered in blocks of KB keys;
+//             it also writes delta.  Every query block of the sequence has a workgroup: those behind q_limit store zeros.
+//   dK / dV:  a workgroup = one pair x one block of KEYS keys, Q / dO (+ lse / delta) double buffered in blocks of QS query rows
+// ---------------------------------------------------------------------------------
+struct StreamBwdCfg {
+    static constexpr int QB = StreamCfg::QB, NW = StreamCfg::NW, KB = StreamCfg::KB;
+    static constexpr int IMG = KB * ROW;                        // one K or V block image (dQ launch)
+    static constexpr int LDS_DQ = 2 * 2 * IMG;                  // two stages of (K, V)
+    static constexpr int KEYS = 32 * NW;                        // dK / dV launch: 32 keys per wave
+    static constexpr int QS = 64;                               // query rows per stage
+    static constexpr int QIMG = QS * ROW;                       // one Q or dO stage image
+    static constexpr int ROWV = 2 * QS * 4;                     // lse and delta of a stage's rows, f32
+    static constexpr int STAGE = 2 * QIMG + ROWV;
+    static constexpr int LDS_DKV = 2 * STAGE;
+    static constexpr int THREADS = NW * 64;
+    static constexpr int OCC_DQ = 2, OCC_DKV = 2;               // waves per SIMD the register allocation leaves room for
+    static_assert(QB == 32 * NW && KB % 32 == 0 && QS % 32 == 0 && QS == 64, "32 rows per wave; one wave stages a stage's lse or delta");
+    static_assert(LDS_DQ * (OCC_DQ * 4 / NW) <= 160 * 1024 && LDS_DKV * (OCC_DKV * 4 / NW) <= 160 * 1024, "LDS of the promised workgroups per CU");
+    // query rows the call reads: whole QB-row blocks that hold a row < q_limit (what gv_attention_fwd_stream computed)
+    static constexpr int query_end(int N, int q_limit) {
+        return q_limit > 0 && ceil_div(q_limit, QB) * QB < N ? ceil_div(q_limit, QB) * QB : N;
+    }
+    static Launch launch_dq(int n_img, int H, int N) { return {(long)n_img * H * ceil_div(N, QB), THREADS, LDS_DQ}; }
+    static Launch launch_dkv(int n_img, int H, int N) { return {(long)n_img * H * ceil_div(N, KEYS), THREADS, LDS_DKV}; }
 };
 
 }  // namespace gvattn

@@ -1,5 +1,5 @@
 // The attention kernels' common LDS image and fragment helpers, and their entry points' common checks (attention.hip,
-// attention_stream.hip; both include attn_plan.h first).
+// attention_stream.hip, attention_stream_bwd.hip; each includes attn_plan.h first).
 //
 // LDS image: [rows = tokens][64 d] bf16, 128-B rows, 16-B chunk index XOR (row & 7).  Filled by LDS-DMA with the swizzle on
 // the per-lane SOURCE address.  The same image serves k-contiguous fragment reads (ds_read_b128) and hardware-transposed
@@ -10,7 +10,7 @@
 #include <initializer_list>
 
 // What every entry point checks first, in the order it always has: pointers, then the shape against the limit `max_n` of
-// include/gipvit.h.  full_text: the wording of gv_attention_probs and gv_attention_fwd_stream, which name every condition.
+// include/gipvit.h.  full_text: the wording of gv_attention_probs and the streaming calls, which name every condition.
 template <class A> int attn_check(const char* name, const A* a, bool pointers_ok, int max_n, bool full_text) {
     GV_REQUIRE(pointers_ok, GV_E_NULL, "%s: null pointer", name);
     GV_REQUIRE(gvattn::shape_ok(a->n_img, a->H, a->N, max_n), GV_E_SHAPE,

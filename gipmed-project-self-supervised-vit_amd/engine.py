@@ -338,13 +338,15 @@ class Segment:
 
 
 class VitGroup:
-    def __init__(self, arch: str, segments, img_size: int, device, save: bool, act=bf16, pool: str = "token"):
+    def __init__(self, arch: str, segments, img_size: int, device, save: bool, act=bf16, pool: str = "token", stream_bwd: bool = False):
         """segments: [(n_img, crop), ...] in feature-row order.  ``act``: element type of the activation / gradient buffers
         that feed GEMMs and attention -- bf16 on the training path, f32 in the fp32 operand mode (csrc/f32path.hip).
         ``pool``: "token" (the feature is the CLS row) or "avg" (the mean of the patch tokens, then fc_norm: every token of the
-        last block is computed and differentiated)."""
+        last block is computed and differentiated).  ``stream_bwd`` (the engines' ``long_seq``): the backward of a segment past
+        GV_ATTN_MAX_N tokens runs gv_attention_bwd_stream instead of being refused (VitRunner.require_trainable)."""
         assert act in (bf16, f32) and pool in POOLS
         self.act, self.pool = act, pool
+        self.stream_bwd = bool(stream_bwd)
         a = ARCHS[arch]
         D, depth, H = a["embed_dim"], a["depth"], a["num_heads"]
         self.save = save
@@ -376,6 +378,10 @@ class VitGroup:
             # buffers alternate between two sets by block parity, so a block's set stays untouched until that item has run
             self.gb3, self.gb4 = e((T, D), act), e((T, D), act)
             self.dh_b, self.dqkv_b = e((T, 4 * D), act), e((T, 3 * D), act)
+            # gv_attention_bwd_stream's delta scratch (written, then read, inside each call), sized for the longest long segment
+            long = [sg.n_img * H * sg.N for sg in self.segs if sg.N > L.GV_ATTN_MAX_N]
+            if self.stream_bwd and long:
+                self.delta = e((max(long),), f32)
 
         if pool == "avg":      # the pooled rows in front of fc_norm (its statistics: the segments' fstats) and their gradient
             self.pooled = e((self.n_img, D), f32)
@@ -679,9 +685,15 @@ class VitRunner:
 
     @staticmethod
     def require_trainable(G: VitGroup):
-        """The attention backward holds a whole sequence in LDS: a group with a segment past GV_ATTN_MAX_N tokens runs forward only
-        (gv_attention_fwd_stream).  Raised before anything is launched."""
+        """gv_attention_bwd holds a whole sequence in LDS: a group with a segment past GV_ATTN_MAX_N tokens runs forward only
+        (gv_attention_fwd_stream) -- unless it was built with ``stream_bwd`` (the engines' ``long_seq=True``), whose backward streams
+        (gv_attention_bwd_stream) up to GV_ATTN_STREAM_MAX_N tokens.  Raised before anything is launched."""
         long = [sg.N for sg in G.segs if sg.N > L.GV_ATTN_MAX_N]
+        if long and getattr(G, "stream_bwd", False):
+            if max(long) > L.GV_ATTN_STREAM_MAX_N:
+                raise ValueError(f"backward: {max(long)} tokens per image is past the {L.GV_ATTN_STREAM_MAX_N}-token limit of the streaming "
+                                 f"attention (images up to 512 px at patch 16)")
+            return
         if long:
             raise ValueError(f"backward: {long[0]} tokens per image ({G.segs[0].crop if len(G.segs) == 1 else 'multi-crop'} px) is past the "
                              f"{L.GV_ATTN_MAX_N}-token limit of the attention backward (images up to 256 px at patch 16); "
@@ -810,6 +822,22 @@ class VitRunner:
             for dY, X, dW, cs in probs:
                 ops.linear(dY, X, dW, dY.shape[1], X.shape[1], T, trans_a=True, trans_b=True, epilogue=ACC, colsum_a=cs, workspace=self.ws_side)
 
+        streams = any(sg.N > L.GV_ATTN_MAX_N for sg in G.segs)
+
+        def attn_bwd(i, dqkv, segs, **ql):
+            """Block i's attention backward (``ql``: its q_limit keyword, if any): the varlen call over all segments -- or, when a segment is past
+            GV_ATTN_MAX_N tokens, one call per segment as the forward makes them: gv_attention_bwd_stream for a long one,
+            gv_attention_bwd for a short one."""
+            if not streams:
+                ops.attention_bwd_varlen(G.qkv[i], G.o[i], G.do, dqkv, segs, H, self.scale, **ql)
+                return
+            for sg in G.segs:
+                bufs = (sg.rows(G.qkv[i]), sg.rows(G.o[i]), sg.rows(G.do), sg.lse[i], sg.n_img, sg.N, H, self.scale)
+                if sg.N > L.GV_ATTN_MAX_N:
+                    ops.attention_bwd_stream(*bufs, dqkv=sg.rows(dqkv), delta=G.delta, **ql)
+                else:
+                    ops.attention_bwd(*bufs, dqkv=sg.rows(dqkv), **ql)
+
         done_grp = [None, None]
         for i in reversed(range(self.depth)):
             b, st = f"blocks.{i}.", G.stats[i]
@@ -831,7 +859,7 @@ class VitRunner:
                 G.scatter_cls(G.c_do, G.do)           # (G.do was zeroed by prepare_backward)
                 G.scatter_cls(G.c_g, G.g)                 # (G.g was zeroed above)
                 # dO is zero behind every image's CLS row: the attention backward skips the other queries (their dQ rows come out zero)
-                ops.attention_bwd_varlen(G.qkv[i], G.o[i], G.do, dqkv, segs, H, self.scale, q_limit=1 if self.sw.cls_qlimit else 0)
+                attn_bwd(i, dqkv, segs, q_limit=1 if self.sw.cls_qlimit else 0)
                 ln_bwd(G.dxn, G.x[2 * i], st[0], st[1], W.f(b + "norm1.weight"), gb_next,
                        W.g(b + "norm1.weight"), W.g(b + "norm1.bias"), W.g(f"blocks.{i - 1}.mlp.fc2.bias") if i > 0 else None,
                        dx_of=(dqkv, W.w(b + "attn.qkv.weight"), 3 * D), gb_scale=None if (rs is None or i == 0) else rs[i - 1, 1])
@@ -857,7 +885,7 @@ class VitRunner:
             if dp:
                 drop_branch_grad(gb_att, i, 1, W.g(b + "attn.proj.bias"))
             ops.linear(gb_att, W.w(b + "attn.proj.weight"), G.do, T, D, D, trans_b=True)
-            ops.attention_bwd_varlen(G.qkv[i], G.o[i], G.do, dqkv, segs, H, self.scale)
+            attn_bwd(i, dqkv, segs)
             # the block's four dY operands are final once the attention backward has run: its weight gradients go to the side stream
             # BEFORE the last kernel of the block's dX chain (which only reads dqkv), one kernel earlier than the chain's end
             probs = [(gb_mlp, G.h[i], W.g(b + "mlp.fc2.weight"), None),
@@ -1103,6 +1131,22 @@ def accumulate_micro(acc: Dict[torch.Tensor, torch.Tensor], table, j: int, n: in
             t.copy_(acc[t] / n if mean else acc[t])
 
 
+def check_long_seq(long_seq: bool, precision: str, crops: Sequence[int]) -> bool:
+    """The engines' ``long_seq`` keyword (train.py --train-long-seq): training crops past GV_ATTN_MAX_N tokens, their attention
+    backward streamed (gv_attention_bwd_stream).  What it cannot do is refused here, before any device work."""
+    if not long_seq:
+        return False
+    if precision == "fp32":
+        raise ValueError(f"long_seq=True with precision='fp32': the streaming attention has no fp32 operand form (that mode stops at "
+                         f"{L.GV_ATTN_F32_MAX_N} tokens); long sequences train in the 16-bit mode")
+    for crop in crops:
+        n_tok = (crop // 16) ** 2 + 1
+        if n_tok > L.GV_ATTN_STREAM_MAX_N:
+            raise ValueError(f"long_seq=True with a {crop}-px crop: {n_tok} tokens per image is past the {L.GV_ATTN_STREAM_MAX_N}-token "
+                             f"limit of the streaming attention (images up to 512 px at patch 16)")
+    return True
+
+
 class TrainEngine:
     """What the two training engines share: the precision / clip-mode arguments and the loss scaler, the gradients handed out,
     and the clip / loss-scale part of the optimizer's arguments."""
@@ -1151,7 +1195,8 @@ class DinoEngine(TrainEngine):
                  momentum_teacher=0.996, student_temp=0.1, teacher_temp=0.04, center_momentum=0.9, clip_grad: float = 0.0,
                  mean=MEAN_RON, std=STD_RON, windows=None, device="cuda:0", reducer=None, precision: str = "bf16", clip_mode: str = "norm",
                  centering: str = "center", sinkhorn_iters: int = 3, koleo_weight: float = 0.0, ibot_weight: float = 0.0,
-                 ibot_mask_ratio: Tuple[float, float] = (0.1, 0.5), ibot_mask_prob: float = 0.5, drop: float = 0.0):
+                 ibot_mask_ratio: Tuple[float, float] = (0.1, 0.5), ibot_mask_prob: float = 0.5, drop: float = 0.0,
+                 long_seq: bool = False):
         """``precision``: "bf16" (the training path) or "fp32" (every GEMM / attention operand, the head activations, the
         weight-normalised prototype matrix and the logit gradient in f32 -- the verification mode of SURVEY 8d's fp32 column).
         ``clip_mode``: "norm" (global norm, the reference default) or "value" (element-wise clamp), train.py:1072-1077.
@@ -1164,7 +1209,10 @@ class DinoEngine(TrainEngine):
         patches, both networks run their last block on every token and the marked rows go through the same head a second time
         against the second EMA centre ``patch_center``.  ``ibot`` is the term's unweighted value, ``loss`` stays the DINO term.
         ``ibot_mask_ratio`` / ``ibot_mask_prob`` size the patch-row buffers (masking.max_rows).  ``drop``: the run's --drop, only
-        so that the combination is refused here."""
+        so that the combination is refused here.
+        ``long_seq``: crops past GV_ATTN_MAX_N tokens (above 256 px) may be trained on: the student's attention backward of such a
+        segment streams (gv_attention_bwd_stream, up to 512 px).  Groups without such a segment launch exactly what they do without it."""
+        self.long_seq = check_long_seq(long_seq, precision, (gsize,) + ((lsize,) if n_local else ()))
         self.ibot_weight = _check_ibot(ibot_weight, ibot_mask_ratio, ibot_mask_prob, gsize, drop, centering)
         if centering not in ("center", "sinkhorn_knopp"):
             raise ValueError(f"centering {centering!r}: 'center' or 'sinkhorn_knopp'")
@@ -1197,7 +1245,7 @@ class DinoEngine(TrainEngine):
         self.head = HeadRunner(D, out_dim, hidden, bottleneck, dev)
         B = batch
         segs = [(n_global * B, gsize)] + ([(n_local * B, lsize)] if n_local else [])
-        self.g_stu = VitGroup(arch, segs, img_size, dev, save=True, act=act)   # all student crops, tokens concatenated
+        self.g_stu = VitGroup(arch, segs, img_size, dev, save=True, act=act, stream_bwd=self.long_seq)   # all student crops, tokens concatenated
         self.g_teach = VitGroup(arch, [(n_global * B, gsize)], img_size, dev, save=False, act=act)
         self.s_wins = [self.gwins] + ([self.lwins] if n_local else [])
         self.hb_s = HeadBuffers(self.V * B, D, out_dim, hidden, bottleneck, dev, save=True, act=act)
@@ -1554,8 +1602,10 @@ class SupervisedEngine(TrainEngine):
                  eps=1e-8, smoothing=0.1, clip_grad: float = 0.0, mean=MEAN_RON, std=STD_RON, device="cuda:0", reducer=None,
                  opt: str = "adamw", momentum: float = 0.9, train_backbone: bool = True, model_ema_decay: Optional[float] = None,
                  precision: str = "bf16", clip_mode: str = "norm", loss: str = "lsce", bce_target_thresh: Optional[float] = None,
-                 layer_decay: Optional[float] = None, global_pool: Optional[str] = "token"):
-        """``global_pool`` (train.py:122 --gp -> create_model, train.py:490): "token" (None: the same) = the CLS token through the
+                 layer_decay: Optional[float] = None, global_pool: Optional[str] = "token", long_seq: bool = False):
+        """``long_seq``: images past GV_ATTN_MAX_N tokens (above 256 px) may be trained on: the attention backward streams
+        (gv_attention_bwd_stream, up to 512 px).  An engine at a smaller image launches exactly what it does without it.
+        ``global_pool`` (train.py:122 --gp -> create_model, train.py:490): "token" (None: the same) = the CLS token through the
         final norm; "avg" = timm's mean-pooled model: no final norm, the mean of the patch tokens through ``fc_norm``, so
         ``feats`` is the pooled, normalised feature and the last block runs on every token (gv_token_mean_fwd / _bwd).
         ``precision``: "bf16" (the training path: bf16 GEMM / attention operands, f32 accumulation and residual stream) or
@@ -1569,6 +1619,7 @@ class SupervisedEngine(TrainEngine):
         ``lr * layer_decay ** (depth + 2 - id)`` and makes ``optimizer_step`` ONE gv_adamw_ema_ranges launch over a range table
         (adamw / adam / sgd) or hands gv_lamb a per-tensor rate; ``layer_scales`` / ``mean_lr`` show the result."""
         self.pool = resolve_pool(global_pool)
+        self.long_seq = check_long_seq(long_seq, precision, (img_size,))
         if loss not in ("lsce", "soft_ce", "bce"):
             raise ValueError(f"loss {loss!r}: 'lsce', 'soft_ce' or 'bce' (train.py:832-842)")
         if bce_target_thresh is not None and loss != "bce":
@@ -1592,7 +1643,7 @@ class SupervisedEngine(TrainEngine):
         self.W = Weights(self.arena, "", fp32=fp32)
         self.Wema = Weights(self.arena, "", teacher=True, fp32=fp32) if model_ema_decay is not None else None
         self.vit = VitRunner(arch, img_size, dev, fp32=fp32)
-        self.grp = VitGroup(arch, [(batch, img_size)], img_size, dev, save=True, act=act, pool=self.pool)
+        self.grp = VitGroup(arch, [(batch, img_size)], img_size, dev, save=True, act=act, pool=self.pool, stream_bwd=self.long_seq)
         e = lambda shape, dt: _empty(shape, dt, dev)
         self.feats, self.dfeats = e((batch, D), act), e((batch, D), act)
         self.logits, self.dlogits, self.prob = e((batch, num_classes), f32), e((batch, num_classes), f32), e((batch, num_classes), f32)

@@ -513,6 +513,27 @@ def attention_bwd(qkv, o, d_o, lse, n_img: int, N: int, H: int, scale: float, dq
     return dqkv
 
 
+def attention_bwd_stream(qkv, o, d_o, lse, n_img: int, N: int, H: int, scale: float, dqkv=None, delta=None, q_limit: int = 0):
+    """``attention_bwd`` for N up to ``_lib.GV_ATTN_STREAM_MAX_N`` tokens, on the o / lse that ``attention_fwd_stream`` left
+    (gv_attention_bwd_stream: a dQ launch over query blocks, then a dK / dV launch over key blocks).  16-bit only.  ``delta``: f32
+    scratch of n_img * H * N elements, allocated when none is given.  ``q_limit`` > 0: d_o is zero behind the first q_limit query
+    rows; only the whole blocks of ``_lib.GV_ATTN_STREAM_QBLOCK`` query rows that hold a row < q_limit are read, dQ behind them is
+    zero."""
+    if qkv.dtype != bf16:
+        raise TypeError(f"attention_bwd_stream: qkv must be {bf16}, got {qkv.dtype} (there is no fp32 operand form: that mode stops at "
+                        f"N = {L.GV_ATTN_F32_MAX_N})")
+    dqkv = torch.empty_like(qkv) if dqkv is None else dqkv
+    if not (o.dtype == d_o.dtype == dqkv.dtype == qkv.dtype):
+        raise TypeError("attention_bwd_stream: qkv / o / d_o / dqkv must share one dtype")
+    delta = torch.empty(n_img * H * N, dtype=f32, device=qkv.device) if delta is None else delta
+    if delta.dtype != f32 or lse.dtype != f32 or delta.numel() < n_img * H * N:
+        raise TypeError(f"attention_bwd_stream: lse and delta must be float32, delta of at least {n_img * H * N} elements")
+    a = L.gv_attention_bwd_stream_args(qkv.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), delta.data_ptr(),
+                                       n_img, N, H, scale, q_limit)
+    L.call("gv_attention_bwd_stream", a, _stream())
+    return dqkv
+
+
 def attention_bwd_varlen(qkv, o, d_o, dqkv, segments, H: int, scale: float, q_limit: int = 0):
     """Backward of all segments of a token-concatenated row space in one call: ``segments`` = [(n_img, N, lse), ...] as for
     attention_fwd_varlen; qkv / dqkv [T, 3 H 64], o / d_o [T, H 64].  bf16: gv_attention_bwd_varlen; the fp32 operand mode runs

@@ -576,8 +576,8 @@ int gv_attention_fwd(const gv_attention_fwd_args* a, void* stream);
  * q_limit > 0: only whole blocks of GV_ATTN_STREAM_QBLOCK query rows that hold a row < q_limit are computed; o / lse rows behind
  * the last such block are left untouched (the CLS-only last block asks for 1).  0 = every query.
  * No atomics: the result of an (image, head) pair depends neither on the launch geometry nor on the other pairs of the launch.
- * One plain launch (no cooperative launch, nothing waits on another workgroup), 32 KB of LDS.  There is no backward and no _f32
- * form: training, attention maps (gv_attention_probs) and the fp32 operand mode keep their limits.                              */
+ * One plain launch (no cooperative launch, nothing waits on another workgroup), 32 KB of LDS.  Its backward is gv_attention_bwd_stream
+ * (below).  There is no _f32 form: attention maps (gv_attention_probs) and the fp32 operand mode keep their limits.             */
 #define GV_ATTN_MAX_N 288            /* gv_attention_fwd / _bwd / _probs and the varlen calls */
 #define GV_ATTN_F32_MAX_N 260        /* the _f32 entry points */
 #define GV_ATTN_STREAM_MAX_N 1040
@@ -609,6 +609,32 @@ typedef struct {
                            * gv_attention_fwd with the same q_limit leaves).  0 = every query.                                      */
 } gv_attention_bwd_args;
 int gv_attention_bwd(const gv_attention_bwd_args* a, void* stream);
+
+/* Streaming backward: gv_attention_bwd for 1 <= N <= GV_ATTN_STREAM_MAX_N, on the o / lse that gv_attention_fwd_stream left (16-bit
+ * operands, head_dim 64; there is no _f32 form).  Checks, their order and their wording are the streaming forward's: a null pointer
+ * (delta included) GV_E_NULL, any other N GV_E_SHAPE with the limit in gv_last_error(), scale <= 0 GV_E_SHAPE, a buffer that is not
+ * 16-byte aligned GV_E_ALIGN -- all before any launch.
+ * Two plain launches on the stream, the second behind the first:
+ *   1. per (pair, block of GV_ATTN_STREAM_QBLOCK query rows): delta[q] = sum_d dO[q][d] O[q][d] in f32, stored to `delta`; K / V stream
+ *      through LDS in key blocks; dQ accumulates in f32 over all key blocks and is rounded once, at the store (the q third of dqkv);
+ *   2. per (pair, block of 128 keys): Q / dO rows stream through LDS with their lse / delta; dK and dV accumulate in f32 over all
+ *      query rows and are rounded once, at the store (the k and v thirds).
+ * Both recompute P = exp(scale q.k - lse[q]) from the f32 lse and round P and dS = P (dP - delta) scale to the 16-bit format before
+ * their products, as gv_attention_bwd does.  Keys >= N are never counted, query rows >= N never read or stored.
+ * No atomics, no cooperative launch, nothing waits on another workgroup: the only dependency between workgroups (delta) is the launch
+ * boundary.  The result of an (image, head) pair depends neither on the launch geometry nor on the other pairs; a second call on the
+ * same buffers gives the same bits.
+ * q_limit > 0: with qe = min(N, q_limit rounded up to GV_ATTN_STREAM_QBLOCK), only query rows < qe are read (qkv's q, o, d_o, lse --
+ * what gv_attention_fwd_stream with the same q_limit leaves); the caller guarantees d_o is zero in [q_limit, qe).  dQ rows >= qe are
+ * written as zeros, dK / dV are the sums over the rows < qe.  0 = every query.                                                 */
+typedef struct {
+    const void* qkv; const void* o; const void* d_o; const float* lse;
+    void* dqkv;           /* 16-bit [n_img*N, 3, H, 64] */
+    float* delta;         /* scratch f32 [n_img, H, N]: written, then read, inside the call */
+    int32_t n_img, N, H; float scale;
+    int32_t q_limit;
+} gv_attention_bwd_stream_args;
+int gv_attention_bwd_stream(const gv_attention_bwd_stream_args* a, void* stream);
 
 /* Varlen backward: the segment table of gv_attention_fwd_varlen (segment i: n_img[i] images of N[i] tokens, rows back to back in
  * qkv / o / d_o / dqkv; lse[i] as the forward left it).  One CALL for the multi-crop row space; inside, each length class runs as

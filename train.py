@@ -95,6 +95,10 @@ def build_parser():
                    "in optical-density space on every crop, in the same pass (gv_crop_augment_stain): per stain (haematoxylin, eosin, residual) "
                    "alpha ~ U(1 - SIGMA, 1 + SIGMA), beta ~ U(-SIGMA, SIGMA); 0 = off, Tellez et al. use 0.05 (light) and 0.2 (strong)")
     g.add_argument("--stain-prob", type=float, default=1.0, metavar="P", help="--stain-jitter: probability that a crop is jittered, 0 < P <= 1")
+    g.add_argument("--train-long-seq", action="store_true", help="train on crops past 288 tokens (tiles above 256 px, up to 512 px = 1 025 tokens): "
+                   "the attention backward of such a crop streams K / V and Q / dO through LDS (gv_attention_bwd_stream) instead of holding the "
+                   "sequence in one workgroup; covers --img-size and the DINO --global-crop-size / --local-crop-size.  16-bit mode only; "
+                   "attention maps keep their 288-token limit")
     g.add_argument("--stain-normalize", type=str, default="none", metavar="{none,macenko}", help="stain normalisation of every INFERENCE pass of the run "
                    "(validation, --extract_features, the k-NN / linear / MIL monitors' bank and query passes): per slide, Macenko's H&E vectors and "
                    "99th-percentile concentrations are estimated on the device from the slide's first chunk and the slide is mapped onto Macenko's "
@@ -438,7 +442,7 @@ def check_supported(args, log=_logger.warning):
 
 
 ATTN_TRAIN_MAX_TOKENS = 288     # gv_attention_bwd / gv_attention_probs hold one sequence in LDS (include/gipvit.h)
-ATTN_STREAM_MAX_TOKENS = 1040   # gv_attention_fwd_stream: forward only
+ATTN_STREAM_MAX_TOKENS = 1040   # gv_attention_fwd_stream; gv_attention_bwd_stream behind --train-long-seq
 ATTN_F32_MAX_TOKENS = 260       # the fp32 operand mode's attention
 
 
@@ -458,8 +462,10 @@ def check_token_limits(args):
     """Image sizes against the attention kernels' sequence limits, before any device work: a run that TRAINS needs every crop within
     288 tokens (256 px at patch 16); --extract_features on the supervised route is forward-only and goes up to 512 px
     (gv_attention_fwd_stream); --extract-attention, --dino --extract_features (it builds the DINO training engine) and
-    --precision fp32 keep the 288- / 260-token limits."""
+    --precision fp32 keep the 288- / 260-token limits.  --train-long-seq lifts the limit of a training run to 1 040 tokens (512 px:
+    gv_attention_bwd_stream), in the 16-bit mode; everything else keeps its limit and, without the flag, its message."""
     tokens = lambda px: (px // 16) ** 2 + 1
+    long_seq = getattr(args, "train_long_seq", False)
     if args.dino:
         sizes = [("--global-crop-size", args.global_crop_size)] + ([("--local-crop-size", args.local_crop_size)] if args.local_crops_number else [])
     else:
@@ -469,7 +475,14 @@ def check_token_limits(args):
         if args.dino and args.extract_features and n > ATTN_TRAIN_MAX_TOKENS:
             raise SystemExit(f"--dino --extract_features with {flag} {px}: {n} tokens per image, the DINO route builds its training engine and stops at "
                              f"{ATTN_TRAIN_MAX_TOKENS} tokens (256 px at patch 16); extract features above that on the supervised route")
-        if not args.extract_features and n > ATTN_TRAIN_MAX_TOKENS:
+        if not args.extract_features and long_seq:
+            if n > ATTN_STREAM_MAX_TOKENS:
+                raise SystemExit(f"--train-long-seq with {flag} {px}: {n} tokens per image, the streaming attention stops at {ATTN_STREAM_MAX_TOKENS} "
+                                 f"tokens (512 px at patch 16)")
+            if args.precision == "fp32" and n > ATTN_F32_MAX_TOKENS:
+                raise SystemExit(f"--train-long-seq --precision fp32 with {flag} {px}: {n} tokens per image, the fp32 operand mode's attention stops at "
+                                 f"{ATTN_F32_MAX_TOKENS} tokens (256 px) and has no streaming form; long sequences train in the 16-bit mode")
+        elif not args.extract_features and n > ATTN_TRAIN_MAX_TOKENS:
             raise SystemExit(f"{flag} {px}: {n} tokens per image, training stops at {ATTN_TRAIN_MAX_TOKENS} tokens (256 px at patch 16: the attention "
                              f"backward holds a whole sequence in LDS); larger tiles run forward-only -- --extract_features, up to 512 px")
         if args.extract_features and args.extract_attention and n > ATTN_TRAIN_MAX_TOKENS:
@@ -662,7 +675,11 @@ def build_engine(args, run, img_from_input_size):
     from gipvit.engine import DinoEngine, SupervisedEngine
     arch, B, tile = run.arch, run.B, run.tile
     common = dict(arch=arch, batch=B, lr=run.lr, weight_decay=args.weight_decay, betas=run.betas, eps=run.eps, clip_grad=args.clip_grad or 0.0,
-                  mean=run.mean, std=run.std, device=run.dev, reducer=run.reducer, precision=args.precision, clip_mode=args.clip_mode)
+                  mean=run.mean, std=run.std, device=run.dev, reducer=run.reducer, precision=args.precision, clip_mode=args.clip_mode,
+                  long_seq=getattr(args, "train_long_seq", False))
+    if common["long_seq"] and run.primary:
+        _logger.info("--train-long-seq: crops past %d tokens train with the streaming attention backward (gv_attention_bwd_stream, up to %d tokens)",
+                     ATTN_TRAIN_MAX_TOKENS, ATTN_STREAM_MAX_TOKENS)
     ema_decay = args.model_ema_decay if args.model_ema else None                 # train.py:615-622
     if args.dino:
         if args.model_ema and run.primary:
