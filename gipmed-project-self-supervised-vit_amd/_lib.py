@@ -217,7 +217,7 @@ ENTRY_POINTS = {
     "gv_colsum_finalize": gv_colsum_finalize_args, "gv_ln_finalize": gv_ln_finalize_args, "gv_colsum": gv_colsum_args, "gv_linear": gv_linear_args,
     "gv_linear_ln_fwd": gv_linear_ln_fwd_args, "gv_mlp_ln_fwd": gv_mlp_ln_fwd_args, "gv_linear_ln_bwd": gv_linear_ln_bwd_args, "gv_expand_rows": gv_expand_rows_args, "gv_linear_dw_group": gv_linear_dw_group_args,
     "gv_attention_fwd": gv_attention_fwd_args, "gv_attention_fwd_stream": gv_attention_fwd_args, "gv_attention_fwd_varlen": gv_attention_fwd_varlen_args, "gv_attention_bwd": gv_attention_bwd_args, "gv_attention_bwd_stream": gv_attention_bwd_stream_args, "gv_attention_bwd_varlen": gv_attention_bwd_varlen_args,
-    "gv_attention_probs": gv_attention_probs_args, "gv_cls_rows": gv_cls_rows_args,
+    "gv_attention_probs": gv_attention_probs_args, "gv_attention_probs_stream": gv_attention_probs_args, "gv_cls_rows": gv_cls_rows_args,
     "gv_tokens_bwd": gv_tokens_bwd_args, "gv_small_matmul": gv_small_matmul_args, "gv_l2norm_fwd": gv_l2norm_fwd_args,
     "gv_l2norm_bwd": gv_l2norm_bwd_args, "gv_weightnorm_fwd": gv_weightnorm_fwd_args, "gv_weightnorm_bwd": gv_weightnorm_bwd_args,
     "gv_dino_loss": gv_dino_loss_args, "gv_center_update": gv_center_update_args, "gv_softmax_lsce": gv_softmax_lsce_args,

@@ -464,49 +464,10 @@ int launch_fwd_any(const gv_attention_fwd_args* a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------
-// attention probabilities (get_last_selfattention, vit.pyc@L255-262): P = exp(scale q.k - lse[q]) with the forward's lse,
-// one pass, no row reduction.  S = Q K^T with queries on MFMA rows and keys on lanes: for a fixed (g, r) the 16 lanes li hold
-// 16 consecutive keys of one query row, so each store instruction writes 4 rows x 64 contiguous bytes with 4-byte stores --
-// P rows start anywhere (N = 257: 1 028-byte rows), nothing is assumed about their alignment.  Each element is computed and
-// stored as soon as its MFMA tile is done: no score registers are held across key tiles.
+// attention probabilities (get_last_selfattention, vit.pyc@L255-262): P = exp(scale q.k - lse[q]) with the forward's lse.
+// The arithmetic, the store pattern and probs_tile are attn_probs_tile.h's, shared with gv_attention_probs_stream.
 // ---------------------------------------------------------------------------------
-constexpr float LOG2E = 1.4426950408889634f;
-
-// one 16-query tile of one (image, head) pair against every key tile; kf(kt, ks) returns the K fragment of key row kt*16 + li.
-// UNR: key tiles unrolled (NKT where the fragments sit in registers; 2 where they come from LDS: fully unrolled, the LDS reads
-// of every tile are hoisted and 172 registers leave 2 waves per SIMD)
-template <int NKT, int UNR, class KF>
-__device__ __forceinline__ void probs_tile(const gv_attention_probs_args& a, const bf16* qbase, long ld, long pair, int q0, int li, int g, KF&& kf) {
-    const int N = a.N, QR = a.q_rows;
-    int qrow = q0 + li;
-    qrow = qrow < QR ? qrow : QR - 1;
-    bf16x8 qf[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) qf[ks] = *(const bf16x8*)(qbase + (long)qrow * ld + ks * 32 + g * 8);
-    // rows of this lane's accumulator: q0 + 4g + r; lse rows >= q_rows are never read
-    float nl[4];
-    bool qok[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int q = q0 + 4 * g + r;
-        qok[r] = q < QR;
-        nl[r] = -a.lse[pair * N + (qok[r] ? q : QR - 1)] * LOG2E;
-    }
-    const float c = a.scale * LOG2E;
-    float* prow = a.p + (pair * QR + q0 + 4 * g) * (long)N;
-#pragma unroll UNR
-    for (int kt = 0; kt < NKT; ++kt) {
-        f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) s = MFMA16(qf[ks], kf(kt, ks), s);
-        const int key = kt * 16 + li;
-        if (key < N) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (qok[r]) prow[(long)r * N + key] = __builtin_amdgcn_exp2f(fmaf(s[r], c, nl[r]));
-        }
-    }
-}
+#include "attn_probs_tile.h"
 
 // all query rows: one workgroup per (image, head) pair, K staged once into the swizzled LDS image by LDS-DMA, the pair's
 // 16-query tiles spread over the waves

@@ -1,6 +1,7 @@
 // Which kernel an attention call gets and with what launch geometry -- gv_attention_fwd / _bwd / _probs, the varlen calls and
-// gv_attention_fwd_stream / gv_attention_bwd_stream (include/gipvit.h).  This is the ONE place where the length classes, the per-class workgroup shapes, the
-// dynamic LDS sizes and the occupancy promises are stated: the kernels of attention.hip / attention_stream.hip / attention_stream_bwd.hip take their
+// gv_attention_fwd_stream / gv_attention_bwd_stream / gv_attention_probs_stream (include/gipvit.h).  This is the ONE place where the
+// length classes, the per-class workgroup shapes, the dynamic LDS sizes and the occupancy promises are stated: the kernels of
+// attention.hip / attention_stream.hip / attention_stream_bwd.hip / attention_probs_stream.hip take their
 // constants from the Cfg structs below, the launchers launch the Launch the same structs give.  Pure host C++17, no HIP: the
 // header compiles with a plain g++ (tests/attn_plan_main.cc replays tests/traces/attention_plans.json through it).
 #pragma once
@@ -162,6 +163,29 @@ struct StreamBwdCfg {
     }
     static Launch launch_dq(int n_img, int H, int N) { return {(long)n_img * H * ceil_div(N, QB), THREADS, LDS_DQ}; }
     static Launch launch_dkv(int n_img, int H, int N) { return {(long)n_img * H * ceil_div(N, KEYS), THREADS, LDS_DKV}; }
+};
+
+// ---------------------------------------------------------------------------------
+// streaming attention probabilities (gv_attention_probs_stream): the sequence is never resident
+//   row form   (q_rows <= PROBS_ROW_Q, the CLS row): a workgroup = one pair; its 16-key tiles are dealt to the ROW_NW waves in
+//              chunks of ROW_CH tiles whose K fragments come straight from global, all issued before the chunk's first MFMA.  No LDS.
+//   block form (more rows): a workgroup = one pair x one block of QB query rows (the streaming forward's shape, Q fragments in
+//              registers), K double buffered in blocks of KB keys.  Only the blocks that hold a row < q_rows are launched.
+// ---------------------------------------------------------------------------------
+struct ProbsStreamCfg {
+    static constexpr int ROW_NW = 4, ROW_CH = 8;                // row form: waves per workgroup, 16-key tiles per chunk (64 registers)
+    static constexpr int ROW_THREADS = ROW_NW * 64, ROW_OCC = 2;
+    static constexpr int QB = StreamCfg::QB, NW = StreamCfg::NW, KB = StreamCfg::KB;
+    static constexpr int IMG = KB * ROW;                        // one K block image
+    static constexpr int LDS = 2 * IMG;                         // two stages of K
+    static constexpr int THREADS = NW * 64, OCC = 4;            // four workgroups per CU cover each other's barriers and stores
+    static_assert(QB == 32 * NW && KB % 16 == 0 && LDS * OCC <= 160 * 1024, "32 rows per wave; key tiles; LDS of the promised workgroups per CU");
+    static constexpr bool by_row(int q_rows) { return probs_by_row(q_rows); }
+    static constexpr int query_blocks(int q_rows) { return ceil_div(q_rows, QB); }
+    static Launch launch(int n_img, int H, int q_rows) {
+        const long pairs = (long)n_img * H;
+        return by_row(q_rows) ? Launch{pairs, ROW_THREADS, 0} : Launch{pairs * query_blocks(q_rows), THREADS, LDS};
+    }
 };
 
 }  // namespace gvattn

@@ -1,5 +1,5 @@
 // The attention kernels' common LDS image and fragment helpers, and their entry points' common checks (attention.hip,
-// attention_stream.hip, attention_stream_bwd.hip; each includes attn_plan.h first).
+// attention_stream.hip, attention_stream_bwd.hip, attention_probs_stream.hip; each includes attn_plan.h first).
 //
 // LDS image: [rows = tokens][64 d] bf16, 128-B rows, 16-B chunk index XOR (row & 7).  Filled by LDS-DMA with the swizzle on
 // the per-lane SOURCE address.  The same image serves k-contiguous fragment reads (ds_read_b128) and hardware-transposed

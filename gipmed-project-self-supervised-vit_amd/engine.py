@@ -338,15 +338,19 @@ class Segment:
 
 
 class VitGroup:
-    def __init__(self, arch: str, segments, img_size: int, device, save: bool, act=bf16, pool: str = "token", stream_bwd: bool = False):
+    def __init__(self, arch: str, segments, img_size: int, device, save: bool, act=bf16, pool: str = "token", stream_bwd: bool = False,
+                 stream_maps: bool = False):
         """segments: [(n_img, crop), ...] in feature-row order.  ``act``: element type of the activation / gradient buffers
         that feed GEMMs and attention -- bf16 on the training path, f32 in the fp32 operand mode (csrc/f32path.hip).
         ``pool``: "token" (the feature is the CLS row) or "avg" (the mean of the patch tokens, then fc_norm: every token of the
         last block is computed and differentiated).  ``stream_bwd`` (the engines' ``long_seq``): the backward of a segment past
-        GV_ATTN_MAX_N tokens runs gv_attention_bwd_stream instead of being refused (VitRunner.require_trainable)."""
+        GV_ATTN_MAX_N tokens runs gv_attention_bwd_stream instead of being refused (VitRunner.require_trainable).  ``stream_maps``
+        (FeatureExtractor's ``long_maps``): the attention maps of such a segment come from gv_attention_probs_stream instead of
+        being refused (VitRunner.require_attention_maps)."""
         assert act in (bf16, f32) and pool in POOLS
         self.act, self.pool = act, pool
         self.stream_bwd = bool(stream_bwd)
+        self.stream_maps = bool(stream_maps)
         a = ARCHS[arch]
         D, depth, H = a["embed_dim"], a["depth"], a["num_heads"]
         self.save = save
@@ -587,8 +591,11 @@ class VitRunner:
                     attn_fwd = ops.attention_fwd_stream if sg.N > L.GV_ATTN_MAX_N else ops.attention_fwd
                     attn_fwd(sg.rows(G.qkv[s]), sg.n_img, sg.N, H, self.scale, o=sg.rows(G.o[s]), lse=sg.lse[s], q_limit=ql)
             if cap is not None and cap.attn is not None and i == self.depth - 1:
+                # past GV_ATTN_MAX_N (a ``stream_maps`` group: require_attention_maps) the map comes from the streaming call, on the lse
+                # the streaming forward has just left (q_limit = 1 leaves the first GV_ATTN_STREAM_QBLOCK rows: the CLS row is among them)
                 sg = G.segs[0]
-                ops.attention_probs(G.qkv[s], sg.lse[s], sg.n_img, sg.N, H, self.scale, cap.attn_rows, p=cap.attn)
+                attn_probs = ops.attention_probs_stream if sg.N > L.GV_ATTN_MAX_N else ops.attention_probs
+                attn_probs(G.qkv[s], sg.lse[s], sg.n_img, sg.N, H, self.scale, cap.attn_rows, p=cap.attn)
             if cls_tail and i == self.depth - 1:
                 self._last_block_tail_fwd(W, G, i, xa, on_side)
                 break
@@ -701,8 +708,15 @@ class VitRunner:
 
     @staticmethod
     def require_attention_maps(G: VitGroup):
-        """gv_attention_probs stops at GV_ATTN_MAX_N tokens, as the kernels it restates."""
+        """gv_attention_probs stops at GV_ATTN_MAX_N tokens, as the kernels it restates -- unless the group was built with
+        ``stream_maps`` (FeatureExtractor's ``long_maps=True``), whose maps come from gv_attention_probs_stream up to
+        GV_ATTN_STREAM_MAX_N tokens.  Raised before anything is launched."""
         long = [sg.N for sg in G.segs if sg.N > L.GV_ATTN_MAX_N]
+        if long and getattr(G, "stream_maps", False):
+            if max(long) > L.GV_ATTN_STREAM_MAX_N:
+                raise ValueError(f"attention maps: {max(long)} tokens per image is past the {L.GV_ATTN_STREAM_MAX_N}-token limit of "
+                                 f"gv_attention_probs_stream (images up to 512 px at patch 16)")
+            return
         if long:
             raise ValueError(f"attention maps: {long[0]} tokens per image is past the {L.GV_ATTN_MAX_N}-token limit of gv_attention_probs "
                              f"(images up to 256 px at patch 16); features and intermediate layers work up to {L.GV_ATTN_STREAM_MAX_N} tokens")
@@ -1824,10 +1838,14 @@ class FeatureExtractor:
     extractor then evaluates those live parameters instead of owning a copy (validation between epochs)."""
 
     def __init__(self, arch="vit_small", img_size=256, batch=256, num_classes=0, mean=MEAN_RON, std=STD_RON, device="cuda:0",
-                 weights: Optional[Weights] = None, precision: str = "bf16", global_pool: Optional[str] = "token"):
+                 weights: Optional[Weights] = None, precision: str = "bf16", global_pool: Optional[str] = "token", long_maps: bool = False):
         """``precision``: as for the engines; with ``weights`` it follows the owning engine's mode.  ``global_pool``: as
         SupervisedEngine's -- "avg" returns the mean of the patch tokens through ``fc_norm`` (the weights must be an avg
-        model's); the attention maps do not change with it, ``intermediate_layers`` is refused (no final norm)."""
+        model's); the attention maps do not change with it, ``intermediate_layers`` is refused (no final norm).
+        ``long_maps``: ``run_with_attention`` and ``last_selfattention`` also work past GV_ATTN_MAX_N tokens (above 256 px, up to
+        512 px), through gv_attention_probs_stream; at or below that limit the keyword changes no launch.  Mind the size of a
+        full map: N x N f32 is 4.2 MB per head and tile at 512 px (1 025 tokens; ViT-S: 25 MB per tile) -- ``cls_only`` /
+        ``run_with_attention`` return 4.1 KB per head and tile.  precision='fp32' keeps its construction-time limit."""
         self.pool = resolve_pool(global_pool)
         fp32, act = operand_mode(precision)
         if weights is not None:
@@ -1852,7 +1870,8 @@ class FeatureExtractor:
         has_fc_norm = self.W.prefix + "fc_norm.weight" in self.arena.specs
         if has_fc_norm != (self.pool == "avg"):
             raise ValueError(f"global_pool={self.pool!r} over the weights of a {'mean-pooled' if has_fc_norm else 'CLS-token'} model")
-        self.grp = VitGroup(arch, [(batch, img_size)], img_size, dev, save=False, act=act, pool=self.pool)
+        self.long_maps = bool(long_maps)
+        self.grp = VitGroup(arch, [(batch, img_size)], img_size, dev, save=False, act=act, pool=self.pool, stream_maps=self.long_maps)
         self.feats = _empty((batch, self.D), act, dev)
         self.logits = _empty((batch, num_classes), f32, dev) if num_classes else None
         self._pad: Dict[str, torch.Tensor] = {}          # the zero-padded last batch per input form (_batches)

@@ -161,6 +161,7 @@ class VitModel:
         self._params = OrderedDict((n, Param(n, a.view(a.p, n))) for n in a.specs)
         self.head = _Head(self._params["head.weight"], self._params["head.bias"])
         self.training = True
+        self.long_maps = False    # create_model(long_maps=True): attention maps past GV_ATTN_MAX_N tokens (FeatureExtractor's keyword)
         self._fx = None           # forward-only runner over the engine's live weights (get_last_selfattention / get_intermediate_layers)
 
     def parameters(self):
@@ -239,12 +240,13 @@ class VitModel:
         if self._fx is None:
             from .engine import FeatureExtractor
             e = self.engine
-            self._fx = FeatureExtractor(self.arch, e.img, e.B, 0, e.mean, e.std, e.dev, weights=e.W, global_pool=e.pool)
+            self._fx = FeatureExtractor(self.arch, e.img, e.B, 0, e.mean, e.std, e.dev, weights=e.W, global_pool=e.pool, long_maps=self.long_maps)
         return self._fx
 
     def get_last_selfattention(self, x: torch.Tensor) -> torch.Tensor:
         """vit.pyc@L255-262: blocks[:-1], then the last block's softmax attention -> f32 [batch, num_heads, N, N].  Evaluation
-        semantics (no stochastic depth, no dropout: the reference under ``model.eval()``); any batch size; images of img_size."""
+        semantics (no stochastic depth, no dropout: the reference under ``model.eval()``); any batch size; images of img_size.
+        Above 256 px (up to 512) only for a model built with ``create_model(..., long_maps=True)``."""
         return self._extractor().last_selfattention(self._images(x))
 
     def get_intermediate_layers(self, x: torch.Tensor, n: int = 1):
@@ -264,12 +266,13 @@ class VitModel:
 def create_model(model_name: str, pretrained: bool = False, in_chans: int = 3, num_classes: Optional[int] = None,
                  drop_rate: float = 0.0, drop_path_rate: Optional[float] = None, checkpoint_path: str = "",
                  img_size: int = 256, batch: int = 8, device: str = "cuda:0", seed: int = 0, global_pool: Optional[str] = None,
-                 **engine_kwargs) -> VitModel:
+                 long_maps: bool = False, **engine_kwargs) -> VitModel:
     """Counterpart of ``timm.create_model`` as the reference calls it (train.py:482-495) for the ViT names it documents.
     Unsupported requests fail here instead of being ignored: other channel counts, dropout (not built; stochastic depth is),
     ``pretrained`` without a checkpoint file (there is no network).  ``num_classes=None`` keeps the checkpoint-less default
     of the reference's runs (2 classes, train_instruct.txt:16-34).  ``global_pool`` (train.py:490 ``global_pool=args.gp``): None
-    or "token" = the CLS token, "avg" = mean of the patch tokens + fc_norm; "" and anything else: ValueError."""
+    or "token" = the CLS token, "avg" = mean of the patch tokens + fc_norm; "" and anything else: ValueError.  ``long_maps``: this build's keyword, not the
+    engine's -- ``get_last_selfattention`` also works at ``img_size`` above 256 px, up to 512 (FeatureExtractor's ``long_maps``)."""
     from .engine import SupervisedEngine
     arch = resolve_arch(model_name)
     if in_chans != 3:
@@ -285,6 +288,7 @@ def create_model(model_name: str, pretrained: bool = False, in_chans: int = 3, n
              else init_vit_state(arch, img_size, C, seed=seed, global_pool=pool))
     eng.load_state(state)
     model = VitModel(eng, arch)
+    model.long_maps = bool(long_maps)
     # stochastic depth: the training loop hands the next step's draws to the engine -- engine.set_drop_path(model.drop_path.sample())
     # dropout: like the stochastic-depth draws, the training loop hands each step its seed -- engine.set_dropout(model.drop_rate, seed)
     model.drop_rate = float(drop_rate or 0.0)

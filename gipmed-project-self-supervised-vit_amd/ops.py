@@ -454,21 +454,38 @@ def attention_fwd_stream(qkv, n_img: int, N: int, H: int, scale: float, o=None, 
     return _attention_fwd("attention_fwd_stream", "gv_attention_fwd_stream", qkv, n_img, N, H, scale, o, lse, q_limit)
 
 
+def _attention_probs(name, entry, qkv, lse, n_img, N, H, scale, q_rows, p):
+    """attention_probs / attention_probs_stream: the same buffers and argument struct through the entry point ``entry``"""
+    if p is None:
+        p = torch.empty(n_img, H, q_rows, N, dtype=f32, device=qkv.device)
+    if p.dtype != f32 or lse.dtype != f32:
+        raise TypeError(f"{name}: p and lse must be float32, got {p.dtype} / {lse.dtype}")
+    if not p.is_contiguous() or p.numel() != n_img * H * q_rows * N:
+        raise ValueError(f"{name}: p must be a contiguous buffer of {n_img} x {H} x {q_rows} x {N}, got {tuple(p.shape)}")
+    if qkv.numel() < n_img * N * 3 * H * 64 or lse.numel() < n_img * H * N:
+        raise ValueError(f"{name}: qkv / lse are smaller than n_img * N rows")
+    a = L.gv_attention_probs_args(qkv.data_ptr(), lse.data_ptr(), p.data_ptr(), n_img, N, H, scale, q_rows)
+    L.call(entry, a, _stream())
+    return p
+
+
 def attention_probs(qkv, lse, n_img: int, N: int, H: int, scale: float, q_rows: int, p=None):
     """The softmax matrix of the attention that ``attention_fwd`` computed from the same ``qkv`` and left ``lse`` for:
     f32 [n_img, H, q_rows, N], query rows 0..q_rows-1 of every image (1 = the CLS row; lse must be valid for them); see
     gv_attention_probs.  ``p``: a caller buffer of that many elements (contiguous), written in place."""
-    if p is None:
-        p = torch.empty(n_img, H, q_rows, N, dtype=f32, device=qkv.device)
-    if p.dtype != f32 or lse.dtype != f32:
-        raise TypeError(f"attention_probs: p and lse must be float32, got {p.dtype} / {lse.dtype}")
-    if not p.is_contiguous() or p.numel() != n_img * H * q_rows * N:
-        raise ValueError(f"attention_probs: p must be a contiguous buffer of {n_img} x {H} x {q_rows} x {N}, got {tuple(p.shape)}")
-    if qkv.numel() < n_img * N * 3 * H * 64 or lse.numel() < n_img * H * N:
-        raise ValueError("attention_probs: qkv / lse are smaller than n_img * N rows")
-    a = L.gv_attention_probs_args(qkv.data_ptr(), lse.data_ptr(), p.data_ptr(), n_img, N, H, scale, q_rows)
-    L.call("gv_attention_probs" + _sfx(qkv), a, _stream())
-    return p
+    return _attention_probs("attention_probs", "gv_attention_probs" + _sfx(qkv), qkv, lse, n_img, N, H, scale, q_rows, p)
+
+
+def attention_probs_stream(qkv, lse, n_img: int, N: int, H: int, scale: float, q_rows: int, p=None):
+    """``attention_probs`` for N up to ``_lib.GV_ATTN_STREAM_MAX_N`` tokens, on the ``lse`` that ``attention_fwd_stream`` left
+    (gv_attention_probs_stream: the sequence is never resident; the same bits as ``attention_probs`` given the same lse).  16-bit
+    only: there is no ``_f32`` form, the fp32 operand mode keeps its ``_lib.GV_ATTN_F32_MAX_N``."""
+    if qkv.dtype == f32:
+        raise ValueError(f"attention_probs_stream: there is no gv_attention_probs_stream_f32 form (the fp32 operand mode stops at "
+                         f"N = {L.GV_ATTN_F32_MAX_N}: use attention_probs)")
+    if qkv.dtype != bf16:
+        raise TypeError(f"attention_probs_stream: qkv must be {bf16}, got {qkv.dtype}")
+    return _attention_probs("attention_probs_stream", "gv_attention_probs_stream", qkv, lse, n_img, N, H, scale, q_rows, p)
 
 
 def _varlen(entry, a, fields, segments, H, scale, q_limit, per_segment, mismatch):

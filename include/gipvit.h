@@ -577,7 +577,7 @@ int gv_attention_fwd(const gv_attention_fwd_args* a, void* stream);
  * the last such block are left untouched (the CLS-only last block asks for 1).  0 = every query.
  * No atomics: the result of an (image, head) pair depends neither on the launch geometry nor on the other pairs of the launch.
  * One plain launch (no cooperative launch, nothing waits on another workgroup), 32 KB of LDS.  Its backward is gv_attention_bwd_stream
- * (below).  There is no _f32 form: attention maps (gv_attention_probs) and the fp32 operand mode keep their limits.             */
+ * (below), its attention maps are gv_attention_probs_stream's.  There is no _f32 form: the fp32 operand mode keeps its limit.        */
 #define GV_ATTN_MAX_N 288            /* gv_attention_fwd / _bwd / _probs and the varlen calls */
 #define GV_ATTN_F32_MAX_N 260        /* the _f32 entry points */
 #define GV_ATTN_STREAM_MAX_N 1040
@@ -666,6 +666,25 @@ typedef struct {
 } gv_attention_probs_args;
 int gv_attention_probs(const gv_attention_probs_args* a, void* stream);
 int gv_attention_probs_f32(const gv_attention_probs_args* a, void* stream);   /* every 16-bit buffer as f32 */
+
+/* Streaming probabilities: gv_attention_probs for 1 <= N <= GV_ATTN_STREAM_MAX_N, on the qkv and the lse that gv_attention_fwd_stream
+ * left (16-bit operands, head_dim 64; there is no _f32 form).  Same argument struct, same contract:
+ *     p[img, h, q, key] = exp(scale * q.k - lse[img, h, q])     for q < q_rows, key < N,   1 <= q_rows <= N
+ * p is f32 [n_img, H, q_rows, N], compact, no alignment assumed (at N = 1 025 a row is 4 100 bytes: 4-byte stores).
+ * Checks, their order and their wording are the streaming forward's: a null pointer GV_E_NULL, any other N GV_E_SHAPE with the limit
+ * in gv_last_error(), q_rows outside 1..N GV_E_SHAPE, scale <= 0 GV_E_SHAPE, a qkv that is not 16-byte aligned GV_E_ALIGN -- all
+ * before any launch.
+ * Only lse rows [0, q_rows) are read: the rows behind them may hold anything (after a forward with q_limit = 1 they do; that forward
+ * computes the first GV_ATTN_STREAM_QBLOCK rows, so q_rows up to that many are served by it).  Keys >= N are never written, nothing
+ * before p[0] or behind p[n_img*H*q_rows*N - 1] is touched.
+ * The arithmetic is gv_attention_probs': s = the f32 result of two 16x16x32 MFMAs (d = 0..31, then 32..63), p = exp2(fma(s,
+ * scale log2e, -lse log2e)).  Given the same lse buffer the two calls write the same bits at every N <= GV_ATTN_MAX_N, and a row of p
+ * depends neither on q_rows, nor on which of the two forms ran, nor on the launch geometry, nor on the other pairs of the launch:
+ *   q_rows <= 16 (the CLS row): a workgroup per (image, head) pair reads every K element once, straight from global; no LDS;
+ *   more rows: a workgroup per (pair, block of GV_ATTN_STREAM_QBLOCK query rows), of which only ceil(q_rows / QBLOCK) are launched;
+ *              K streams through LDS in key blocks (16 KB), each 16 x 16 tile is stored as soon as it is computed.
+ * One plain launch: no atomics, no cooperative launch, nothing waits on another workgroup.                                     */
+int gv_attention_probs_stream(const gv_attention_probs_args* a, void* stream);
 
 /* ---- token assembly (vit.pyc@L235-246 prepare_tokens: CLS row) ---------
  * x[i*N + 0, :] = cls[:] + pos[0, :] for every image i.                    */

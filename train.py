@@ -98,7 +98,7 @@ def build_parser():
     g.add_argument("--train-long-seq", action="store_true", help="train on crops past 288 tokens (tiles above 256 px, up to 512 px = 1 025 tokens): "
                    "the attention backward of such a crop streams K / V and Q / dO through LDS (gv_attention_bwd_stream) instead of holding the "
                    "sequence in one workgroup; covers --img-size and the DINO --global-crop-size / --local-crop-size.  16-bit mode only; "
-                   "attention maps keep their 288-token limit")
+                   "attention maps keep their 288-token limit (their own opt-in: --long-attention-maps)")
     g.add_argument("--stain-normalize", type=str, default="none", metavar="{none,macenko}", help="stain normalisation of every INFERENCE pass of the run "
                    "(validation, --extract_features, the k-NN / linear / MIL monitors' bank and query passes): per slide, Macenko's H&E vectors and "
                    "99th-percentile concentrations are estimated on the device from the slide's first chunk and the slide is mapped onto Macenko's "
@@ -164,6 +164,10 @@ def build_parser():
     g.add_argument("--extract-attention", action="store_true", help="with --extract_features: also write <slide>_attention.pt, f32 "
                    "[n_tiles, heads, N] = the CLS query's last-block attention over every token (get_last_selfattention row 0); "
                    "[:, :, 1:] reshaped to (img/16, img/16) is DINO's attention map")
+    g.add_argument("--long-attention-maps", action="store_true", help="with --extract_features --extract-attention: attention maps of tiles above "
+                   "256 px, up to 512 px = 1 025 tokens (gv_attention_probs_stream: the CLS row is recomputed from the streaming forward's "
+                   "log-sum-exp without holding the sequence in one workgroup).  16-bit mode only; not for --dino --extract_features, "
+                   "which extracts such maps on the supervised route from an --initial-checkpoint")
     g.add_argument("--device", default="cuda", help="must be a GPU: the hot path has no CPU fallback")
     g.add_argument("--precision", default="bf16", choices=("bf16", "fp32"), help="bf16: bf16 GEMM / attention operands, f32 accumulation, f32 "
                    "residual stream and master weights (the training path).  fp32: every operand f32 -- the reference's arithmetic "
@@ -442,7 +446,7 @@ def check_supported(args, log=_logger.warning):
 
 
 ATTN_TRAIN_MAX_TOKENS = 288     # gv_attention_bwd / gv_attention_probs hold one sequence in LDS (include/gipvit.h)
-ATTN_STREAM_MAX_TOKENS = 1040   # gv_attention_fwd_stream; gv_attention_bwd_stream behind --train-long-seq
+ATTN_STREAM_MAX_TOKENS = 1040   # gv_attention_fwd_stream; gv_attention_bwd_stream behind --train-long-seq, gv_attention_probs_stream behind --long-attention-maps
 ATTN_F32_MAX_TOKENS = 260       # the fp32 operand mode's attention
 
 
@@ -463,9 +467,14 @@ def check_token_limits(args):
     288 tokens (256 px at patch 16); --extract_features on the supervised route is forward-only and goes up to 512 px
     (gv_attention_fwd_stream); --extract-attention, --dino --extract_features (it builds the DINO training engine) and
     --precision fp32 keep the 288- / 260-token limits.  --train-long-seq lifts the limit of a training run to 1 040 tokens (512 px:
-    gv_attention_bwd_stream), in the 16-bit mode; everything else keeps its limit and, without the flag, its message."""
+    gv_attention_bwd_stream), in the 16-bit mode; --long-attention-maps lifts the limit of --extract-attention on the supervised route to the
+    same 1 040 tokens (gv_attention_probs_stream), in the 16-bit mode; everything else keeps its limit and, without the flags, its message."""
     tokens = lambda px: (px // 16) ** 2 + 1
     long_seq = getattr(args, "train_long_seq", False)
+    long_maps = getattr(args, "long_attention_maps", False)
+    if long_maps and not (args.extract_features and args.extract_attention):
+        raise SystemExit("--long-attention-maps lifts the limit of --extract_features --extract-attention (attention maps of tiles above 256 px): "
+                         "it needs both")
     if args.dino:
         sizes = [("--global-crop-size", args.global_crop_size)] + ([("--local-crop-size", args.local_crop_size)] if args.local_crops_number else [])
     else:
@@ -485,7 +494,10 @@ def check_token_limits(args):
         elif not args.extract_features and n > ATTN_TRAIN_MAX_TOKENS:
             raise SystemExit(f"{flag} {px}: {n} tokens per image, training stops at {ATTN_TRAIN_MAX_TOKENS} tokens (256 px at patch 16: the attention "
                              f"backward holds a whole sequence in LDS); larger tiles run forward-only -- --extract_features, up to 512 px")
-        if args.extract_features and args.extract_attention and n > ATTN_TRAIN_MAX_TOKENS:
+        if long_maps and n > ATTN_STREAM_MAX_TOKENS:
+            raise SystemExit(f"--long-attention-maps with {flag} {px}: {n} tokens per image, the streaming attention maps stop at "
+                             f"{ATTN_STREAM_MAX_TOKENS} tokens (512 px at patch 16)")
+        if args.extract_features and args.extract_attention and n > ATTN_TRAIN_MAX_TOKENS and not long_maps:
             raise SystemExit(f"--extract-attention with {flag} {px}: {n} tokens per image, attention maps stop at {ATTN_TRAIN_MAX_TOKENS} tokens "
                              f"(256 px at patch 16); the features themselves work up to 512 px")
         if args.extract_features and n > ATTN_STREAM_MAX_TOKENS:
@@ -731,15 +743,16 @@ def build_evaluation(args, args_text, run):
     eval_B = min(256, max(run.B, 32))
     teacher = lambda: Weights(eng.arena, "backbone.", teacher=True, fp32=args.precision == "fp32")
     r = SimpleNamespace(val=None, ema=None, mon=None, norm={})
+    long_maps = bool(getattr(args, "long_attention_maps", False))     # --long-attention-maps: the extractors' maps past GV_ATTN_MAX_N tokens
     if run.data.inf is not None:
         if args.dino:       # features come from the teacher backbone (the model DINO users evaluate)
-            r.val = FeatureExtractor(arch, tile, eval_B, 0, mean, std, dev, weights=teacher())
+            r.val = FeatureExtractor(arch, tile, eval_B, 0, mean, std, dev, weights=teacher(), long_maps=long_maps)
             if tile != img:
                 raise SystemExit(f"--extract_features with --dino: tile size {tile} must equal the teacher's image size {img}")
         else:
-            r.val = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.W, global_pool=eng.pool)
+            r.val = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.W, global_pool=eng.pool, long_maps=long_maps)
             if run.ema_decay is not None:
-                r.ema = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.Wema, global_pool=eng.pool)
+                r.ema = FeatureExtractor(arch, img, eval_B, nc, mean, std, dev, weights=eng.Wema, global_pool=eng.pool, long_maps=long_maps)
     if run.data.bank is not None:   # the teacher backbone at its own image size; larger tiles contribute their centred window (gipvit/knn.py)
         r.mon = FeatureExtractor(arch, img, eval_B, 0, mean, std, dev, weights=teacher())
     if args.stain_normalize == "macenko":
