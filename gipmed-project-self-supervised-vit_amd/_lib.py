@@ -190,6 +190,16 @@ gv_mil_predict_args = _struct("gv_mil_predict_args", [
     ("params", vp), ("x", vp), ("bag_ptr", vp), ("labels", vp), ("bags", vp), ("prob", vp), ("loss", vp), ("attn", vp), ("score", vp),
     ("workspace", vp), ("workspace_bytes", i64), ("ldx", i64), ("N", i32), ("F", i32), ("L", i32), ("C", i32), ("n_all_bags", i32), ("n_bags", i32),
     ("max_bag", i32), ("accumulate", i32)])
+gv_surv_train_args = _struct("gv_surv_train_args", [
+    ("params", vp), ("m", vp), ("v", vp), ("x", vp), ("bag_ptr", vp), ("time", vp), ("event", vp), ("bags", vp), ("loss_sum", vp),
+    ("workspace", vp), ("workspace_bytes", i64), ("ldx", i64), ("N", i32), ("F", i32), ("L", i32), ("n_all_bags", i32), ("n_bags", i32),
+    ("batch", i32), ("max_bag", i32), ("step0", i32), ("lr", f32), ("lr_scale", f32), ("wd", f32), ("beta1", f32), ("beta2", f32), ("eps", f32)])
+gv_surv_predict_args = _struct("gv_surv_predict_args", [
+    ("params", vp), ("x", vp), ("bag_ptr", vp), ("bags", vp), ("risk", vp), ("attn", vp), ("score", vp),
+    ("workspace", vp), ("workspace_bytes", i64), ("ldx", i64), ("N", i32), ("F", i32), ("L", i32), ("n_all_bags", i32), ("n_bags", i32),
+    ("max_bag", i32)])
+gv_cox_eval_args = _struct("gv_cox_eval_args", [
+    ("risk", vp), ("time", vp), ("event", vp), ("loss", vp), ("counts", vp), ("workspace", vp), ("workspace_bytes", i64), ("n", i32)])
 gv_sinkhorn_args = _struct("gv_sinkhorn_args", [
     ("teacher", vp), ("shift", vp), ("a", vp), ("b", vp), ("colsum", vp), ("sk_center", vp), ("workspace", vp), ("workspace_bytes", i64),
     ("hyper", vp), ("R", i32), ("K", i32), ("first", i32), ("teacher_temp", f32)])
@@ -237,6 +247,7 @@ ENTRY_POINTS = {
     "gv_weightnorm_fwd_f32": gv_weightnorm_fwd_args, "gv_dino_loss_f32": gv_dino_loss_args,
     "gv_knn_vote": gv_knn_vote_args, "gv_linprobe_train": gv_linprobe_train_args, "gv_linprobe_predict": gv_linprobe_predict_args,
     "gv_mil_train": gv_mil_train_args, "gv_mil_predict": gv_mil_predict_args,
+    "gv_surv_train": gv_surv_train_args, "gv_surv_predict": gv_surv_predict_args, "gv_cox_eval": gv_cox_eval_args,
     "gv_token_mean_fwd": gv_token_mean_fwd_args, "gv_token_mean_bwd": gv_token_mean_bwd_args, "gv_token_mean_bwd_f32": gv_token_mean_bwd_args,
     "gv_sinkhorn_shift": gv_sinkhorn_args, "gv_sinkhorn_cols": gv_sinkhorn_args, "gv_sinkhorn_rows": gv_sinkhorn_args, "gv_sinkhorn_finish": gv_sinkhorn_args,
     "gv_koleo_fwd": gv_koleo_args, "gv_koleo_bwd": gv_koleo_args, "gv_koleo_fwd_f32": gv_koleo_args, "gv_koleo_bwd_f32": gv_koleo_args,
@@ -246,6 +257,7 @@ ENTRY_POINTS = {
 }
 PLAIN_SYMBOLS = ("gv_version", "gv_last_error", "gv_target", "gv_act_format", "gv_linear_workspace_bytes", "gv_workspace_bytes", "gv_linear_timing", "gv_linear_timing_read",
                  "gv_linear_ln_blocks", "gv_knn_workspace_bytes", "gv_linprobe_workspace_bytes", "gv_mil_workspace_bytes",
+                 "gv_surv_workspace_bytes", "gv_cox_eval_workspace_bytes",
                  "gv_sinkhorn_workspace_bytes", "gv_koleo_workspace_bytes", "gv_mask_tokens_workspace_bytes", "gv_ibot_loss_workspace_bytes")
 
 
@@ -293,6 +305,10 @@ def _load():
     lib.gv_linprobe_workspace_bytes.restype = C.c_int64
     lib.gv_mil_workspace_bytes.argtypes = [C.c_int32] * 5
     lib.gv_mil_workspace_bytes.restype = C.c_int64
+    lib.gv_surv_workspace_bytes.argtypes = [C.c_int32] * 4
+    lib.gv_surv_workspace_bytes.restype = C.c_int64
+    lib.gv_cox_eval_workspace_bytes.argtypes = [C.c_int32]
+    lib.gv_cox_eval_workspace_bytes.restype = C.c_int64
     lib.gv_sinkhorn_workspace_bytes.argtypes = [C.c_int32] * 2
     lib.gv_sinkhorn_workspace_bytes.restype = C.c_int64
     lib.gv_koleo_workspace_bytes.argtypes = [C.c_int32] * 3

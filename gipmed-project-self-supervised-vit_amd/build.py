@@ -16,7 +16,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libgipvit_hip.so")
 # (library, object directory, extra flags)
 VARIANTS = {"bf16": (LIB, OBJ, []), "f16": (os.path.join(HERE, "libgipvit_hip_f16.so"), os.path.join(CSRC, "_obj_f16"), ["-DGV_ACT_F16"])}
-SOURCES = ["abi", "gemm", "panel", "layernorm", "rowops", "patch", "augment", "stainnorm", "attention", "attention_stream", "attention_stream_bwd", "attention_probs_stream", "f32path", "dino_loss", "optim", "knn", "pool", "linprobe", "mil", "dinov2_terms", "ibot"]
+SOURCES = ["abi", "gemm", "panel", "layernorm", "rowops", "patch", "augment", "stainnorm", "attention", "attention_stream", "attention_stream_bwd", "attention_probs_stream", "f32path", "dino_loss", "optim", "knn", "pool", "linprobe", "mil", "survival", "dinov2_terms", "ibot"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result"]
 
 

@@ -148,6 +148,49 @@ def _read_labels(root: str, target: Optional[str]) -> Dict[str, Tuple[int, Optio
     return out
 
 
+def read_survival(root: str) -> Dict[str, Tuple[float, int]]:
+    """labels.csv as a survival table: slide name -> (time, event), event 1 = observed, 0 = censored.  The time column is
+    ``time`` or the reference's ``Time (months)``; the status column is ``censored`` / ``Censored`` (1 = censored, the reference's
+    convention, datasets.py:146-156) or ``event`` (1 = event).  A row with an empty, non-numeric, non-finite or negative cell is
+    skipped; a file without those columns gives an empty table."""
+    out: Dict[str, Tuple[float, int]] = {}
+    lp = os.path.join(root, "labels.csv")
+    if not os.path.exists(lp):
+        return out
+    with open(lp) as f:
+        rows = list(csv.reader(f))
+    if not rows:
+        return out
+    hdr = [h.strip() for h in rows[0]]
+    tcol = next((hdr.index(h) for h in ("time", "Time (months)") if h in hdr), None)
+    ccol = next((hdr.index(h) for h in ("censored", "Censored") if h in hdr), None)
+    ecol = hdr.index("event") if "event" in hdr else None
+    scol = ecol if ecol is not None else ccol
+    if tcol is None or scol is None:
+        return out
+    for r in rows[1:]:
+        if len(r) <= max(tcol, scol) or not r[0].strip():
+            continue
+        try:
+            t, s = float(r[tcol].strip()), float(r[scol].strip())
+        except ValueError:
+            continue
+        if not (np.isfinite(t) and t >= 0) or s not in (0.0, 1.0):
+            continue
+        out[r[0].strip()] = (t, int(s) if ecol is not None else 1 - int(s))
+    return out
+
+
+def synthetic_survival(names: Sequence[str], seed: int) -> Dict[str, Tuple[float, int]]:
+    """A survival table for synthetic slides, a function of the slide's ordinal and the seed alone: the time (months, f32) is
+    drawn from PCG64([seed, ordinal]), every second slide is censored (so both states are present from two slides on)."""
+    out = {}
+    for k, name in enumerate(names):
+        t = np.random.Generator(np.random.PCG64([seed, k])).uniform(1.0, 60.0)
+        out[name] = (float(np.float32(t)), int(k % 2 == 0))
+    return out
+
+
 def scan_slides(root: str, target: Optional[str] = None):
     """-> [(slide name, [tile paths sorted by index], label, fold)] for every ``<root>/<slide>/`` with tile files."""
     labels = _read_labels(root, target)

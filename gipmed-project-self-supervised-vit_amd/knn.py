@@ -65,18 +65,21 @@ def centred_window(data: torch.Tensor, img: int) -> torch.Tensor:
     return data
 
 
-def collect_features(loader, C: int, features, who: str, normaliser=None):
+def collect_features(loader, C: int, features, who: str, normaliser=None, keep=None):
     """-> (features f32 [N, D] device, labels int64 [N], slide ordinal int64 [N], slides left out) over the slides whose label
     is inside [0, C); ``features(data)`` maps one chunk of tiles to its f32 [n, D] rows.  ``normaliser``: a
     gipvit.stainnorm.SlideNormaliser over the runner behind ``features`` -- every chunk is announced to it first (a slide begins
-    behind the previous ``Is Last Batch``), so the bank and the query pass see stain-normalised tiles; None: nothing changes."""
+    behind the previous ``Is Last Batch``), so the bank and the query pass see stain-normalised tiles; None: nothing changes.
+    ``keep``: a predicate over the slide's position in ``loader.image_file_names`` that decides in place of the label (the
+    survival probe keeps the slides its table has); None: nothing changes."""
     if hasattr(loader, "reset_counter"):
         loader.reset_counter()
     feats, labels, slides, skipped, ordinal = [], [], [], 0, 0
     first = True
     for mb in loader:
         y = int(mb["Label"].reshape(-1)[0])
-        if 0 <= y < C:
+        ok = 0 <= y < C if keep is None else bool(keep(ordinal))
+        if ok:
             if normaliser is not None:
                 normaliser.begin(mb["Data"], first)
                 first = False
@@ -85,13 +88,13 @@ def collect_features(loader, C: int, features, who: str, normaliser=None):
             labels.append(np.full(f.shape[0], y, dtype=np.int64))
             slides.append(np.full(f.shape[0], ordinal, dtype=np.int64))
         if mb["Is Last Batch"]:
-            skipped += not 0 <= y < C
+            skipped += not ok
             ordinal += 1
             first = True
     if normaliser is not None:
         normaliser.end()
     if not feats:
-        raise ValueError(f"{who}: no slide with a label in [0, {C}) in the loader")
+        raise ValueError(f"{who}: no slide with a label in [0, {C}) in the loader" if keep is None else f"{who}: no slide of the loader is kept")
     return torch.cat(feats), np.concatenate(labels), np.concatenate(slides), skipped
 
 

@@ -780,6 +780,94 @@ def mil_predict(params, x, bag_ptr, hidden: int, num_classes: int, max_bag: int,
     return out
 
 
+_surv_workspace: dict = {}  # device -> uint8 scratch of surv_train / surv_predict, grown on demand and kept
+_cox_workspace: dict = {}   # device -> uint8 scratch of cox_eval
+
+
+def _surv_scratch(dev, batch: int, max_bag: int, Lh: int, F: int):
+    need = L.lib.gv_surv_workspace_bytes(batch, max_bag, Lh, F)
+    if need < 0:
+        raise L.GipvitError(f"gv_surv_workspace_bytes: {L.lib.gv_last_error().decode()}")
+    ws = _surv_workspace.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _surv_workspace[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _cox_scratch(dev, n: int):
+    need = L.lib.gv_cox_eval_workspace_bytes(n)
+    if need < 0:
+        raise L.GipvitError(f"gv_cox_eval_workspace_bytes: {L.lib.gv_last_error().decode()}")
+    ws = _cox_workspace.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _cox_workspace[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _surv_table(who: str, time, event, n: int, dev):
+    _chk(time, f32, "time"); _chk(event, torch.int32, "event")
+    for t, nm in ((time, "time"), (event, "event")):
+        if t.dim() != 1 or t.shape[0] != n or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{who}: {nm} must be a contiguous vector [{n}] on {dev}, got {tuple(t.shape)} on {t.device}")
+
+
+def surv_train(params, m, v, x, bag_ptr, time, event, bags, loss_sum, hidden: int, batch: int, max_bag: int, step0: int, lr: float,
+               lr_scale: float = 1.0, wd: float = 0.0, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8):
+    """Adam steps of the gated-attention survival model on frozen features under Cox's partial likelihood (gv_surv_train), in
+    place: params / m / v f32 [P] packed as the MIL probe's at C = 1, x f32 [N, F], bag_ptr int32 [n_all + 1], time f32 [n_all],
+    event int32 [n_all] (1 = observed, 0 = censored), bags int32 [n_bags] (the visiting order), loss_sum f32 [2] (accumulated:
+    the sum of the event terms, the events).  ``step0``: Adam steps taken before this call."""
+    F, n_all = _mil_inputs("surv_train", params, x, bag_ptr, None, bags, hidden, 1)
+    if time is None or event is None or bags is None:
+        raise ValueError("surv_train: time, event and bags are required")
+    _surv_table("surv_train", time, event, n_all, x.device)
+    for t, nm, shape in ((m, "m", tuple(params.shape)), (v, "v", tuple(params.shape)), (loss_sum, "loss_sum", (2,))):
+        _chk(t, f32, nm)
+        if tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"surv_train: {nm} must be a contiguous f32 {list(shape)} on {x.device}, got {tuple(t.shape)} on {t.device}")
+    ws = _surv_scratch(x.device, batch, max_bag, hidden, F)
+    a = L.gv_surv_train_args(params.data_ptr(), m.data_ptr(), v.data_ptr(), x.data_ptr(), bag_ptr.data_ptr(), time.data_ptr(), event.data_ptr(),
+                             bags.data_ptr(), loss_sum.data_ptr(), ws.data_ptr(), ws.numel(), x.stride(0), x.shape[0], F, hidden, n_all, bags.shape[0],
+                             batch, max_bag, step0, lr, lr_scale, wd, beta1, beta2, eps)
+    L.call("gv_surv_train", a, _stream())
+
+
+def surv_predict(params, x, bag_ptr, hidden: int, max_bag: int, bags=None, want_attn: bool = False, want_score: bool = False):
+    """The model's bag risks (gv_surv_predict) -> dict(risk f32 [n_bags], 0 for a bad bag; with ``want_attn`` / ``want_score``
+    attn / score f32 [N]: a_i after and s_i before the bag's softmax, zero in rows no predicted bag covers)."""
+    F, n_all = _mil_inputs("surv_predict", params, x, bag_ptr, None, bags, hidden, 1)
+    n_bags = n_all if bags is None else bags.shape[0]
+    ws = _surv_scratch(x.device, max(1, min(n_bags, 64)), max_bag, hidden, F)
+    risk = torch.empty(n_bags, dtype=f32, device=x.device)
+    attn = torch.zeros(x.shape[0], dtype=f32, device=x.device) if want_attn else None
+    score = torch.zeros(x.shape[0], dtype=f32, device=x.device) if want_score else None
+    a = L.gv_surv_predict_args(params.data_ptr(), x.data_ptr(), bag_ptr.data_ptr(), _p(bags), risk.data_ptr(), _p(attn), _p(score),
+                               ws.data_ptr(), ws.numel(), x.stride(0), x.shape[0], F, hidden, n_all, n_bags, max_bag)
+    L.call("gv_surv_predict", a, _stream())
+    out = dict(risk=risk)
+    if attn is not None:
+        out["attn"] = attn
+    if score is not None:
+        out["score"] = score
+    return out
+
+
+def cox_eval(risk, time, event):
+    """Cohort evaluation (gv_cox_eval) of risk f32 [n], time f32 [n], event int32 [n] -> (loss f64 [1]: the sum of the event
+    terms of Cox's partial likelihood in fp64, counts int64 [6]: events, comparable, concordant, discordant, tied, excluded)."""
+    _chk(risk, f32, "risk")
+    if risk.dim() != 1 or not risk.shape[0] or not risk.is_contiguous():
+        raise ValueError(f"cox_eval: risk must be a contiguous f32 vector, got {tuple(risk.shape)}")
+    n = risk.shape[0]
+    _surv_table("cox_eval", time, event, n, risk.device)
+    ws = _cox_scratch(risk.device, n)
+    loss = torch.empty(1, dtype=torch.float64, device=risk.device)
+    counts = torch.empty(6, dtype=torch.int64, device=risk.device)
+    a = L.gv_cox_eval_args(risk.data_ptr(), time.data_ptr(), event.data_ptr(), loss.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), n)
+    L.call("gv_cox_eval", a, _stream())
+    return loss, counts
+
+
 def weightnorm_fwd(v, g, w, rows: int, C: int):
     L.call("gv_weightnorm_fwd" + _sfx(w), L.gv_weightnorm_fwd_args(v.data_ptr(), g.data_ptr(), w.data_ptr(), rows, C), _stream())
 

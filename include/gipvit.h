@@ -1129,6 +1129,95 @@ int gv_mil_predict(const gv_mil_predict_args* a, void* stream);
  * call would refuse.  Touches no GPU.                                                                                          */
 int64_t gv_mil_workspace_bytes(int32_t batch, int32_t max_bag, int32_t L, int32_t C, int32_t F);
 
+/* ---- slide-level survival probe on frozen features (gipvit/survival.py, csrc/survival.hip): the ABMIL body above with one
+ * risk output, trained on Cox's partial likelihood with right-censoring.
+ * MODEL: gv_mil_train's at C = 1.  Per bag t_i, g_i, s_i, a, z as above; the bag's RISK is theta = Wc . z + bc.  The packed
+ * layout is the MIL one at C = 1: P = (2 L + 1) F + 3 L + 2 values,  VU [2 L, F] | Wc [1, F] | bv [L] | bu [L] | w [L] | bc | bw.
+ * STEP LOSS: Cox partial likelihood, Breslow ties.  G = the step's good bags in step order, e_i in {0, 1} (1 = the event was
+ * observed, 0 = censored), t_i the time as f32, E = #{i in G : e_i = 1}:
+ *     l        = (1/E) sum_{i in G, e_i = 1} [ log sum_{j in G, t_j >= t_i} exp(theta_j) - theta_i ]
+ *     dtheta_k = (1/E) [ sum_{i in G, e_i = 1, t_i <= t_k} exp(theta_k - M) / S_i  -  e_k ]
+ *     S_i = sum_{j in G, t_j >= t_i} exp(theta_j - M),   M = max_{j in G} theta_j
+ * in f32 with expf / logf, the sums over j and over i in step order.  Times are compared exactly as given; equal times are in
+ * each other's risk set; a bag listed twice is two tied entries.  A step with E = 0 changes nothing (parameters and moments
+ * keep their bits, Adam's step count still advances) and adds nothing to loss_sum.  loss_sum is f32 [2], accumulated (the
+ * caller zeroes it): {sum of the event terms log S_i + M - theta_i, E}; the epoch loss is their quotient.
+ * THE RISK BIAS bc: l does not depend on bc, so its loss gradient is identically zero, and the step gives it a gradient of
+ * EXACTLY zero (not the sum of the dtheta_k, rounding noise that Adam would normalise to +-lr): with wd = 0 bc keeps its bits,
+ * with decay it only decays.  bw is treated as the MIL probe treats it.
+ * ADAM is gv_mil_train's: the decay is added to the gradient, step k of the call is Adam's step step0 + k + 1, the bias
+ * corrections are computed on the host in double, lr lr_scale is the rate.
+ * gv_surv_train performs ceil(n_bags / batch) steps over bags[], all enqueued on the stream.  A step is four launches, every
+ * dependency a launch boundary (no grid barrier, no atomics): the MIL gate; a pool launch (a workgroup per bag) that stops at
+ * theta_b and z_b and, because dz_b = dtheta_b Wc at C = 1, leaves the unit-gradient ds~_i = a_i (u_i - sum_j a_j u_j), u_i =
+ * Wc . x_i, and dbw~ = sum_i ds~_i; the Cox launch (a workgroup per bag: l and dtheta from the step's <= 64 risks, then the
+ * bag's ds~ rows and dbw~ scaled by dtheta_b); the MIL update with dl_b = dtheta_b and the gradient of bc forced to zero.  Every
+ * sum has an order fixed by the data layout: results are bitwise the same run to run.  Every load is bounds-checked, padding is
+ * zero-filled, rows of x that no bag covers are never read.
+ * A BAD BAG contributes nothing and is never used as an index: any of gv_mil_train's conditions on geometry, a time that is
+ * not finite or is negative, an event flag outside {0, 1}.
+ * Limits: gv_mil_train's at C = 1 (F a multiple of 4 in 4..4096, L a multiple of 16 in 16..256, 1 <= batch <= 64, 1 <= max_bag
+ * <= 4096, the same alignment rules), workspace of gv_surv_workspace_bytes(batch, max_bag, L, F) bytes. */
+typedef struct {
+    float*         params;   /* f32 [P], the layout above                                                */
+    float*         m;        /* f32 [P] Adam's first moment                                              */
+    float*         v;        /* f32 [P] Adam's second moment                                             */
+    const float*   x;        /* f32 [N, F], row stride ldx                                               */
+    const int32_t* bag_ptr;  /* i32 [n_all_bags + 1]                                                     */
+    const float*   time;     /* f32 [n_all_bags]: time to the event or to censoring                      */
+    const int32_t* event;    /* i32 [n_all_bags]: 1 = event observed, 0 = censored                       */
+    const int32_t* bags;     /* i32 [n_bags]: the visiting order, any multiset of bag indices            */
+    float*         loss_sum; /* f32 [2], accumulated: {sum of the event terms, events}                   */
+    void*          workspace; int64_t workspace_bytes;
+    int64_t ldx;
+    int32_t N, F, L, n_all_bags, n_bags, batch, max_bag;
+    int32_t step0;           /* Adam steps taken before this call                                        */
+    float   lr, lr_scale, wd, beta1, beta2, eps;
+} gv_surv_train_args;
+int gv_surv_train(const gv_surv_train_args* a, void* stream);
+/* risk[j] = theta of bag bags[j] (bags NULL: of bag j) for j < n_bags, 0 for a bad bag (geometry only: no time is read);
+ * optionally attn[r] = a_i and score[r] = s_i for every row r of those bags, as gv_mil_predict writes them.  Any n_bags >= 1
+ * (groups of 64 bags), workspace of gv_surv_workspace_bytes(min(n_bags, 64), max_bag, L, F) bytes.                            */
+typedef struct {
+    const float*   params;   /* f32 [P]                                                                  */
+    const float*   x;        /* f32 [N, F], row stride ldx                                               */
+    const int32_t* bag_ptr;  /* i32 [n_all_bags + 1]                                                     */
+    const int32_t* bags;     /* i32 [n_bags]; may be NULL                                                */
+    float*         risk;     /* f32 [n_bags]                                                             */
+    float*         attn;     /* f32 [N]; may be NULL                                                     */
+    float*         score;    /* f32 [N]; may be NULL                                                     */
+    void*          workspace; int64_t workspace_bytes;
+    int64_t ldx;
+    int32_t N, F, L, n_all_bags, n_bags, max_bag;
+} gv_surv_predict_args;
+int gv_surv_predict(const gv_surv_predict_args* a, void* stream);
+/* scratch bytes of a gv_surv_train call (gv_surv_predict: batch = min(n_bags, 64)); -1 with gv_last_error() set for arguments
+ * the call would refuse.  Touches no GPU.                                                                                     */
+int64_t gv_surv_workspace_bytes(int32_t batch, int32_t max_bag, int32_t L, int32_t F);
+/* COHORT EVALUATION over any risk f32 [n], time f32 [n], event i32 [n], 1 <= n <= 65536.  An entry with a non-finite risk, a
+ * time that is not finite or is negative, or a flag outside {0, 1} is excluded and counted.  Over the valid entries:
+ *   loss[0] = sum_{e_i = 1} [ log S_i + M - theta_i ] IN FP64 (exp / log in double), S_i and M as above.  A row's sum S_i is
+ *     taken by one workgroup of 256 threads, thread t adding the entries t, t + 256, .. in order and the 256 partial sums going
+ *     through one fixed tree: the order depends on n alone, not on the launch geometry.  The rows' terms are stored and then
+ *     added in index order.
+ *   CONCORDANCE (Harrell) over ordered pairs (i, j) of valid entries: a pair is COMPARABLE iff e_i = 1 and t_i < t_j (strict),
+ *     and then concordant / discordant / tied as theta_i >, <, = theta_j;  C = (concordant + tied / 2) / comparable.  Pairs
+ *     with equal times are NOT counted, whichever of the two had the event -- this differs from lifelines' concordance_index,
+ *     which counts an equal-time pair when exactly one of the two is an event.
+ *   counts int64 [6] = events, comparable, concordant, discordant, tied, excluded: exact integers.
+ * Two calls give the same bits.  Workspace (8-byte aligned) of gv_cox_eval_workspace_bytes(n) bytes.                          */
+typedef struct {
+    const float*   risk;     /* f32 [n]                                                                  */
+    const float*   time;     /* f32 [n]                                                                  */
+    const int32_t* event;    /* i32 [n]                                                                  */
+    double*        loss;     /* f64 [1]: the sum of the event terms                                      */
+    int64_t*       counts;   /* i64 [6]: events, comparable, concordant, discordant, tied, excluded      */
+    void*          workspace; int64_t workspace_bytes;
+    int32_t n;
+} gv_cox_eval_args;
+int gv_cox_eval(const gv_cox_eval_args* a, void* stream);
+int64_t gv_cox_eval_workspace_bytes(int32_t n);
+
 /* ---- DINOv2 loss options (csrc/dinov2_terms.hip): Sinkhorn-Knopp centring of the teacher and the KoLeo regulariser.
  *
  * Sinkhorn-Knopp over the teacher logits T f32 [R, K] (R = G * B local rows), in the log domain: a [K] (= log u) and b [R] start

@@ -156,6 +156,16 @@ def build_parser():
     g.add_argument("--mil-batch", type=int, default=8, help="--mil-probe: slides per step (1..64)")
     g.add_argument("--mil-layers", type=int, default=1, help="--mil-probe: the CLS tokens of the last N blocks are the features")
     g.add_argument("--mil-rate", type=int, default=0, help="--mil-probe: 0 = probe after the last epoch only, N >= 1 = every N epochs and the last")
+    g.add_argument("--surv-probe", action="store_true", help="DINO: slide-level survival probe on the teacher's frozen features (the MIL probe's "
+                   "gated ABMIL with one risk output, trained on Cox's partial likelihood with right-censoring, gv_surv_train; time and status come "
+                   "from labels.csv: time | 'Time (months)' and censored | Censored | event): eval_surv_cindex / eval_surv_loss in summary.csv")
+    g.add_argument("--surv-hidden", type=int, default=128, help="--surv-probe: width of the gated attention (a multiple of 16 in 16..256)")
+    g.add_argument("--surv-lr", type=float, default=5e-4, help="--surv-probe: Adam's rate (cosine schedule per epoch)")
+    g.add_argument("--surv-wd", type=float, default=1e-4, help="--surv-probe: weight decay, added to the gradient")
+    g.add_argument("--surv-epochs", type=int, default=50, help="--surv-probe: passes over the bank's slides")
+    g.add_argument("--surv-batch", type=int, default=32, help="--surv-probe: slides per step (1..64); a step's slides are each other's risk sets")
+    g.add_argument("--surv-layers", type=int, default=1, help="--surv-probe: the CLS tokens of the last N blocks are the features")
+    g.add_argument("--surv-rate", type=int, default=0, help="--surv-probe: 0 = probe after the last epoch only, N >= 1 = every N epochs and the last")
     g.add_argument("--tile-size", type=int, default=256)
     g.add_argument("--batches-per-epoch", type=int, default=100, help="synthetic source only")
     g.add_argument("--synthetic-slides", type=int, default=4, help="synthetic source only: slides of the inference set")
@@ -194,6 +204,7 @@ def parse_args(argv=None):
 SUPPORTED_OPTS = ("sgd", "adam", "adamw", "lamb")  # modes of gv_adamw_ema (sgd = momentum + nesterov, timm's default for 'sgd') + gv_lamb
 SUPPORTED_SCHEDS = ("cosine", "step")               # gipvit/sched.py
 LOWER_IS_BETTER = ("loss", "linear_loss", "mil_loss")     # train.py:866: the --eval-metric values where the lower checkpoint is the better one
+SURV_LOWER_IS_BETTER = ("surv_loss",)                     # the survival probe's, consulted beside it
 
 
 def dino_loss_options(args) -> dict:
@@ -396,6 +407,8 @@ def check_supported(args, log=_logger.warning):
         if resolve_eval_metric(args.eval_metric, bool(args.knn_monitor), bool(args.linear_probe), True) not in names:
             raise SystemExit(f"--eval-metric {args.eval_metric}: the monitors of this run report {names} (a bare name is the k-NN monitor's "
                              "when that is on, else the linear probe's, else the MIL probe's)")
+    if getattr(args, "surv_probe", False):
+        check_surv_probe(args)
     check_ibot(args)
     # the DINOv2 loss options belong to the DINO step
     if not args.dino and (args.centering != "center" or args.koleo_weight != 0):
@@ -507,14 +520,59 @@ def check_token_limits(args):
                              f"{ATTN_F32_MAX_TOKENS} tokens (256 px); larger tiles run in the 16-bit mode")
 
 
+def check_surv_probe(args):
+    """--surv-probe's refusals, all before any GPU work (the MIL probe's, and a survival table to train on)."""
+    if not args.dino:
+        raise SystemExit("--surv-probe scores the DINO teacher's frozen features: it needs --dino (a supervised run has validate())")
+    if args.surv_hidden % 16 or not 16 <= args.surv_hidden <= 256:
+        raise SystemExit(f"--surv-hidden {args.surv_hidden}: a multiple of 16 in 16 .. 256 (gv_surv_train)")
+    if not (math.isfinite(args.surv_lr) and args.surv_lr > 0):
+        raise SystemExit(f"--surv-lr {args.surv_lr}: a positive finite rate")
+    if not args.surv_wd >= 0:
+        raise SystemExit(f"--surv-wd {args.surv_wd}: weight decay must be >= 0")
+    if args.surv_epochs < 1:
+        raise SystemExit(f"--surv-epochs {args.surv_epochs}: at least one pass over the bank's slides")
+    if not 1 <= args.surv_batch <= 64:
+        raise SystemExit(f"--surv-batch {args.surv_batch}: 1 .. 64 slides per step (gv_surv_train)")
+    from gipvit.archs import ARCHS, resolve_arch       # plain tables: nothing is loaded for them
+    spec = ARCHS[resolve_arch(args.model)]
+    if not 1 <= args.surv_layers <= spec["depth"]:
+        raise SystemExit(f"--surv-layers {args.surv_layers}: the last 1 .. {spec['depth']} blocks of {args.model}")
+    if args.surv_layers * spec["embed_dim"] > 4096:
+        raise SystemExit(f"--surv-layers {args.surv_layers}: {args.surv_layers * spec['embed_dim']} features per tile at width {spec['embed_dim']}, "
+                         "gv_surv_train stops at 4096")
+    if args.surv_rate < 0:
+        raise SystemExit(f"--surv-rate {args.surv_rate}: 0 = after the last epoch only, N >= 1 = every N epochs and the last")
+    if args.test_fold in (-1, "-1"):
+        raise SystemExit("--test_fold -1 with --surv-probe: no evaluation fold is left to score the slides of")
+    if args.tile_size < args.global_crop_size:
+        raise SystemExit(f"--surv-probe: the teacher sees {args.global_crop_size}-px images, the centred window of a {args.tile_size}-px "
+                         "tile (--tile-size) cannot be smaller than that")
+    if args.num_tiles > 4096:
+        raise SystemExit(f"--num_tiles {args.num_tiles} with --surv-probe: a slide's bag holds at most 4096 tiles (gv_surv_train)")
+    if args.knn_bank_tiles is not None and args.knn_bank_tiles > 4096:
+        raise SystemExit(f"--knn-bank-tiles {args.knn_bank_tiles} with --surv-probe: a slide's bag holds at most 4096 tiles (gv_surv_train)")
+    names = monitor_metric_names(args)
+    if resolve_eval_metric(args.eval_metric, bool(args.knn_monitor), bool(args.linear_probe), bool(args.mil_probe), surv=True) not in names:
+        raise SystemExit(f"--eval-metric {args.eval_metric}: the monitors of this run report {names} (a bare name is the k-NN monitor's when that "
+                         "is on, else the linear probe's, else the MIL probe's; the survival probe's are surv_cindex and surv_loss)")
+    if args.dataset not in ("", "synthetic") and (args.dataset.startswith("tiles:") or args.data_dir) and not args.extract_features:
+        from gipvit import data as D                   # (numpy and torch only: no library is loaded)
+        root = args.dataset[6:] if args.dataset.startswith("tiles:") else args.data_dir
+        if not D.read_survival(root):
+            raise SystemExit(f"--surv-probe: {os.path.join(root, 'labels.csv')} yields no survival table (a time | 'Time (months)' column, a "
+                             "censored | Censored | event column, and at least one row with valid cells)")
+
+
 def monitor_metric_names(args):
     """The metrics the monitors of a --dino run report, in the fixed order of their summary.csv columns: the k-NN monitor's, then
-    the linear probe's, then the MIL probe's; the AUCs only with more than one class."""
+    the linear probe's, then the MIL probe's, then the survival probe's; the AUCs only with more than one class."""
     many = (args.num_classes or 2) > 1
     knn = (["knn_top1"] + (["knn_auc_per_patch", "knn_auc_per_slide"] if many else [])) if args.knn_monitor else []
     probe = (["linear_top1", "linear_loss"] + (["linear_auc_per_patch", "linear_auc_per_slide"] if many else [])) if args.linear_probe else []
     mil = (["mil_top1", "mil_loss"] + (["mil_auc_per_slide"] if many else [])) if getattr(args, "mil_probe", False) else []
-    return knn + probe + mil
+    surv = ["surv_cindex", "surv_loss"] if getattr(args, "surv_probe", False) else []
+    return knn + probe + mil + surv
 
 
 def summary_row(epoch, train_metrics, eval_metrics, monitor_names, lr) -> "OrderedDict":
@@ -528,13 +586,13 @@ def summary_row(epoch, train_metrics, eval_metrics, monitor_names, lr) -> "Order
     return row
 
 
-def resolve_eval_metric(name: str, knn: bool, probe: bool, mil: bool = False) -> str:
-    """--eval-metric among the metrics of a --dino run's monitors: a name that already starts knn_ / linear_ / mil_ is taken as
-    given, a bare one is the k-NN monitor's when that is on ('top1' -> 'knn_top1'), else the linear probe's when that is on, else
-    the MIL probe's when it is the only monitor."""
-    if name.startswith("knn_") or name.startswith("linear_") or name.startswith("mil_"):
+def resolve_eval_metric(name: str, knn: bool, probe: bool, mil: bool = False, *, surv: bool = False) -> str:
+    """--eval-metric among the metrics of a --dino run's monitors: a name that already starts knn_ / linear_ / mil_ / surv_ is
+    taken as given, a bare one is the k-NN monitor's when that is on ('top1' -> 'knn_top1'), else the linear probe's when that is
+    on, else the MIL probe's, else the survival probe's when it is the only monitor."""
+    if name.startswith("knn_") or name.startswith("linear_") or name.startswith("mil_") or name.startswith("surv_"):
         return name
-    return ("knn_" + name) if knn else ("linear_" + name) if probe else ("mil_" + name) if mil else name
+    return ("knn_" + name) if knn else ("linear_" + name) if probe else ("mil_" + name) if mil else ("surv_" + name) if surv else name
 
 
 def mix_active(args) -> bool:
@@ -656,7 +714,7 @@ def build_loaders(args, run, transform, hook_format):
         transform = None
     if hook_format == "f32_nchw" and run.primary:
         _logger.info("transform hook returns float32 [3, H, W]: batches are float32 NCHW, patchified without the fused normalise")
-    inf = bank = query = None
+    inf = bank = query = surv_table = None
     bank_tiles, monitors_on = args.knn_bank_tiles or args.num_tiles, bool(monitor_metric_names(args)) and not args.extract_features
     if synthetic:
         source = D.SyntheticTiles(B, tile, args.batches_per_epoch, args.num_classes or 2, seed=args.seed + rank)
@@ -665,6 +723,8 @@ def build_loaders(args, run, transform, hook_format):
         if monitors_on:      # (--extract_features runs alone)
             bank = D.SyntheticSlides(args.synthetic_slides, min(bank_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 77)
             query = D.SyntheticSlides(args.synthetic_slides, min(args.num_tiles, 2 * B), tile, args.tiles_per_iter, seed=args.seed + 99)
+            if getattr(args, "surv_probe", False):
+                surv_table = D.synthetic_survival(bank.image_file_names, args.seed)
     elif args.dataset.startswith("tiles:") or args.data_dir:
         root = args.dataset[6:] if args.dataset.startswith("tiles:") else args.data_dir
         train_slides, eval_slides, want_eval = select_slides(args, D.scan_slides(root, args.target), run.primary)
@@ -674,10 +734,12 @@ def build_loaders(args, run, transform, hook_format):
             inf = infer(args.num_tiles, args.seed, eval_slides)
         if monitors_on:      # (--extract_features runs alone)
             bank, query = infer(bank_tiles, args.seed + 1, train_slides), infer(args.num_tiles, args.seed, eval_slides)
+            if getattr(args, "surv_probe", False):
+                surv_table = D.read_survival(root)
     else:
         raise SystemExit(f"--dataset {args.dataset}: whole-slide datasets need openslide and are outside this build "
                          "(SURVEY section 2 #15); use 'synthetic' or 'tiles:<dir>' with pre-extracted tile_<i>.data files")
-    return SimpleNamespace(source=source, augmenter=augmenter, inf=inf, bank=bank, query=query)
+    return SimpleNamespace(source=source, augmenter=augmenter, inf=inf, bank=bank, query=query, surv_table=surv_table)
 
 
 def build_engine(args, run, img_from_input_size):
@@ -763,21 +825,23 @@ def build_evaluation(args, args_text, run):
             _logger.info("stain normalisation: macenko (beta %.3g alpha %.3g, %s of a slide's first chunk) on every inference pass%s; "
                          "training batches are not normalised", args.stain_norm_beta, args.stain_norm_alpha,
                          f"the first {args.stain_norm_tiles} tiles" if args.stain_norm_tiles else "every tile", "" if r.norm else " (this run has none)")
-    monitors = build_monitors(args, r.mon, run.primary, r.norm.get("mon"))
-    eval_metric = resolve_eval_metric(args.eval_metric, *(any(m.prefix == p for m in monitors) for p in ("knn_", "linear_", "mil_")))   # 'top1' -> knn_top1
+    monitors = build_monitors(args, r.mon, run.primary, r.norm.get("mon"), **({"surv_table": run.data.surv_table} if getattr(args, "surv_probe", False) else {}))
+    eval_metric = resolve_eval_metric(args.eval_metric, *(any(m.prefix == p for m in monitors) for p in ("knn_", "linear_", "mil_")),
+                                      surv=any(m.prefix == "surv_" for m in monitors))   # 'top1' -> knn_top1
     saver = output_dir = None
     if run.primary:
         exp = args.experiment or "-".join([time.strftime("%Y%m%d-%H%M%S"), args.model.replace("/", "_"), str(img)])
         output_dir = os.path.join(args.output or "./output/train", exp, args.subexperiment or "")
-        decreasing = eval_metric in LOWER_IS_BETTER or not (monitors or (run.data.inf is not None and not args.dino))       # train.py:866
+        decreasing = eval_metric in LOWER_IS_BETTER or eval_metric in SURV_LOWER_IS_BETTER or not (monitors or (run.data.inf is not None and not args.dino))       # train.py:866
         saver = CheckpointSaver(output_dir, args.model, vars(args), decreasing=decreasing, max_history=args.checkpoint_hist)
         with open(os.path.join(output_dir, "args.yaml"), "w") as f:
             f.write(args_text)
     return r, monitors, eval_metric, saver, output_dir
 
 
-def build_monitors(args, runner, primary=True, normaliser=None):
-    """The run's monitors on ``runner``, in the fixed order k-NN, linear probe, MIL probe.  ``normaliser``: the keyword exists with --stain-normalize only."""
+def build_monitors(args, runner, primary=True, normaliser=None, surv_table=None):
+    """The run's monitors on ``runner``, in the fixed order k-NN, linear probe, MIL probe, survival probe.  ``normaliser``: the keyword exists with
+    --stain-normalize only; ``surv_table``: slide name -> (time, event), with --surv-probe only."""
     if runner is None:
         return []
     from gipvit.knn import KnnMonitor as Knn            # (imported late: they load the library)
@@ -793,8 +857,12 @@ def build_monitors(args, runner, primary=True, normaliser=None):
     if args.mil_probe:          # slide-level ABMIL on the same runner's CLS tokens, one bag per slide (gipvit/mil.py)
         monitors.append(Mil(runner, hidden=args.mil_hidden, lr=args.mil_lr, weight_decay=args.mil_wd, epochs=args.mil_epochs, batch=args.mil_batch,
                             n_last=args.mil_layers, seed=args.seed, **kw))
+    if getattr(args, "surv_probe", False):      # the same body with one risk output under Cox's partial likelihood (gipvit/survival.py)
+        from gipvit.survival import SurvivalProbe as Surv
+        monitors.append(Surv(runner, surv_table, hidden=args.surv_hidden, lr=args.surv_lr, weight_decay=args.surv_wd, epochs=args.surv_epochs,
+                             batch=args.surv_batch, n_last=args.surv_layers, seed=args.seed, **kw))
     assert [n for m in monitors for n in m.metric_names()] == monitor_metric_names(args)        # the flag-level statements the refusals and the saver use
-    assert [m.prefix + x for m in monitors for x in m.lower_is_better] == [n for n in monitor_metric_names(args) if n in LOWER_IS_BETTER]
+    assert [m.prefix + x for m in monitors for x in m.lower_is_better] == [n for n in monitor_metric_names(args) if n in LOWER_IS_BETTER or n in SURV_LOWER_IS_BETTER]
     return monitors
 
 
@@ -802,7 +870,7 @@ def monitor_due(args, prefix: str, epoch: int) -> bool:
     """The monitor with this metric prefix runs after ``epoch``: k-NN every --knn-rate epochs; a probe after the last and, at a rate >= 1, every rate epochs."""
     if prefix == "knn_":
         return (epoch + 1) % args.knn_rate == 0
-    rate = args.linprobe_rate if prefix == "linear_" else args.mil_rate
+    rate = args.linprobe_rate if prefix == "linear_" else args.surv_rate if prefix == "surv_" else args.mil_rate
     return epoch == args.epochs - 1 or (rate >= 1 and (epoch + 1) % rate == 0)
 
 
@@ -962,7 +1030,7 @@ def end_of_epoch(args, run, epoch, train_metrics):
     if eval_metric in eval_metrics:
         save_metric, name = eval_metrics[eval_metric], "eval " + eval_metric          # train.py:970-973
     elif eval_metric in monitor_names or (not eval_metrics and run.monitors):
-        save_metric, name = None, "eval " + eval_metric                               # not evaluated this epoch (--knn-rate / --linprobe-rate / --mil-rate)
+        save_metric, name = None, "eval " + eval_metric                               # not evaluated this epoch (--knn-rate / --linprobe-rate / --mil-rate / --surv-rate)
     elif eval_metrics:
         who = ("validate() reports" if not run.monitors else "the k-NN monitor reports" if [m.prefix for m in run.monitors] == ["knn_"]
                else "the monitors of this run report")
