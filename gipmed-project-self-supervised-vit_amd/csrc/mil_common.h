@@ -1,5 +1,8 @@
 // What the attention-MIL probe (mil.hip) and the survival probe (survival.hip) share: the launch parameters, the bag test, the gate
-// and update kernels, the block reductions, the argument checks and the workspace layout.  See mil.hip for the step.
+// and update kernels, the block reductions, the two halves every pool kernel has (bag_softmax_pool: scores, softmax and z;
+// bag_score_grad: from a vector to ds and dbw), the argument and Adam checks, the workspace layout and the step driver's pieces
+// (mil_set_step, mil_each_group, the gate and update launches).  A head's own file keeps its pool kernel's middle (logits and
+// loss, or the risk), its other launches and its entry points.  See mil.hip for the step.
 #pragma once
 #include "gv_common.h"
 #include <math.h>
@@ -177,6 +180,91 @@ __device__ __forceinline__ float mil_block_max(float v, float* red, int t) {
     return red[0];
 }
 
+// (b), the front of a pool kernel, one workgroup of 256 per good bag: the scores (the gate's partials added in chunk order, plus
+// bw), a_i = softmax over the bag's own rows, left in sS, and z = sum_i a_i x_i, left in sZ.  Predict stores score / attn where
+// they are asked for, training stores z.  LDS: sS [MMAXBAG], sZ [MMAXF] and zpart [4 * 256] 16-byte aligned, red [256].
+template <bool TRAIN>
+__device__ __forceinline__ void bag_softmax_pool(const MilP& p, int b, int start, int n, float bw, float* sS, float* sZ, float* zpart,
+                                                 float* red) {
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int F = p.F;
+    const long slot0 = (long)b * p.max_bag;
+    float mx = -INFINITY;
+    for (int i = t; i < n; i += 256) {
+        float s = bw;
+        for (int ch = 0; ch < p.nch; ++ch) s += p.SP[(slot0 + i) * MMAXCH + ch];
+        sS[i] = s;
+        mx = fmaxf(mx, s);
+        if (!TRAIN && p.score) p.score[start + i] = s;
+    }
+    mx = mil_block_max(mx, red, t);
+    float ps = 0.f;
+    for (int i = t; i < n; i += 256) {               // rows past the bag are not in the sum
+        const float e = expf(sS[i] - mx);
+        sS[i] = e;
+        ps += e;
+    }
+    const float den = mil_block_sum(ps, red, t);
+    for (int i = t; i < n; i += 256) {
+        const float a = sS[i] / den;
+        sS[i] = a;
+        if (!TRAIN && p.attn) p.attn[start + i] = a;
+    }
+    __syncthreads();
+    // z = sum_i a_i x_i: 256 columns at a time, wave w the rows w, w + 4, .. in order, the four waves' sums then added in order
+    for (int c0 = 0; c0 < F; c0 += 256) {
+        const int col = c0 + lane * 4;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        if (col < F) {
+            const float* xp = p.x + (long)start * p.ldx + col;
+#pragma unroll 4
+            for (int i = wave; i < n; i += 4) {
+                const f32x4 xv = *(const f32x4*)(xp + (long)i * p.ldx);
+                const float a = sS[i];
+                acc[0] = fmaf(a, xv[0], acc[0]); acc[1] = fmaf(a, xv[1], acc[1]);
+                acc[2] = fmaf(a, xv[2], acc[2]); acc[3] = fmaf(a, xv[3], acc[3]);
+            }
+        }
+        *(f32x4*)(zpart + wave * 256 + lane * 4) = acc;
+        __syncthreads();
+        if (c0 + t < F) sZ[c0 + t] = ((zpart[t] + zpart[256 + t]) + zpart[512 + t]) + zpart[768 + t];
+        __syncthreads();
+    }
+    if (TRAIN)
+        for (int f = t; f < F; f += 256) p.Z[(long)b * F + f] = sZ[f];
+}
+
+// (b), the back of a training pool kernel: with a vector d in sZ (its stores fenced by the caller's barrier), sV[i] = d . x_i
+// per row (sV [MMAXBAG]), then ds_i = a_i (sV[i] - sum_j a_j sV[j]) into DS and their sum into DBW[b]
+__device__ __forceinline__ void bag_score_grad(const MilP& p, int b, int start, int n, const float* sS, float* sV, const float* sZ, float* red) {
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int F = p.F;
+    const long slot0 = (long)b * p.max_bag;
+    for (int i = wave; i < n; i += 4) {
+        const float* xp = p.x + (long)(start + i) * p.ldx;
+        float acc = 0.f;
+        for (int f = lane * 4; f < F; f += 256) {
+            const f32x4 xv = *(const f32x4*)(xp + f);
+            acc = fmaf(sZ[f], xv[0], acc); acc = fmaf(sZ[f + 1], xv[1], acc);
+            acc = fmaf(sZ[f + 2], xv[2], acc); acc = fmaf(sZ[f + 3], xv[3], acc);
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) sV[i] = acc;
+    }
+    __syncthreads();
+    float pd = 0.f;
+    for (int i = t; i < n; i += 256) pd = fmaf(sS[i], sV[i], pd);
+    const float dot = mil_block_sum(pd, red, t);
+    float pb = 0.f;
+    for (int i = t; i < n; i += 256) {
+        const float ds = sS[i] * (sV[i] - dot);
+        p.DS[slot0 + i] = ds;
+        pb += ds;
+    }
+    const float dbw = mil_block_sum(pb, red, t);
+    if (t == 0) p.DBW[b] = dbw;
+}
+
 // (c) the weight gradients of one (F slice, hidden block) and their Adam step.  SURV (survival.hip): C = 1, DL[b] is the Cox
 // d theta_b, a step without an event changes nothing, the risk bias gets a gradient of exactly zero (the partial likelihood does
 // not depend on it) and loss_sum[1] counts the events.
@@ -347,7 +435,8 @@ MilWs mil_workspace(int batch, int max_bag, int L, int F) {
     return w;
 }
 
-int mil_check_common(const char* who, const float* x, int64_t ldx, int F, int N, int n_all, int n_bags, const void* params,
+// wsfn: the function that tells this caller's workspace size, named in the two workspace messages
+int mil_check_common(const char* who, const char* wsfn, const float* x, int64_t ldx, int F, int N, int n_all, int n_bags, const void* params,
                      const void* ws, int64_t have, int64_t need) {
     GV_REQUIRE(N >= 1 && n_all >= 1 && n_bags >= 1, GV_E_SHAPE, "%s: need N >= 1, n_all_bags >= 1 and n_bags >= 1 (got N = %d, n_all_bags = %d, n_bags = %d)",
                who, N, n_all, n_bags);
@@ -355,10 +444,56 @@ int mil_check_common(const char* who, const float* x, int64_t ldx, int F, int N,
     GV_REQUIRE(ldx % 4 == 0, GV_E_ALIGN, "%s: ldx must be a multiple of 4 (got %lld)", who, (long long)ldx);
     GV_REQUIRE(gv_aligned(x, 16), GV_E_ALIGN, "%s: x must be 16-byte aligned", who);
     GV_REQUIRE(gv_aligned(params, 16), GV_E_ALIGN, "%s: params must be 16-byte aligned", who);
-    GV_REQUIRE(ws, GV_E_NULL, "%s: null workspace (%lld bytes needed, gv_mil_workspace_bytes)", who, (long long)need);
-    GV_REQUIRE(have >= need, GV_E_SHAPE, "%s: workspace of %lld bytes, %lld needed (gv_mil_workspace_bytes)", who, (long long)have, (long long)need);
+    GV_REQUIRE(ws, GV_E_NULL, "%s: null workspace (%lld bytes needed, %s)", who, (long long)need, wsfn);
+    GV_REQUIRE(have >= need, GV_E_SHAPE, "%s: workspace of %lld bytes, %lld needed (%s)", who, (long long)have, (long long)need, wsfn);
     GV_REQUIRE(gv_aligned(ws, 16), GV_E_ALIGN, "%s: workspace must be 16-byte aligned", who);
     return GV_OK;
+}
+
+int mil_check_adam(const char* who, const float* m, const float* v, int step0, float lr, float lr_scale, float wd, float beta1, float beta2,
+                   float eps) {
+    GV_REQUIRE(gv_aligned(m, 16) && gv_aligned(v, 16), GV_E_ALIGN, "%s: m and v must be 16-byte aligned", who);
+    GV_REQUIRE(step0 >= 0, GV_E_SHAPE, "%s: need step0 >= 0 (got %d)", who, step0);
+    GV_REQUIRE(isfinite(lr) && lr > 0.f, GV_E_SHAPE, "%s: need lr finite and > 0 (got %g)", who, (double)lr);
+    GV_REQUIRE(isfinite(lr_scale) && lr_scale >= 0.f, GV_E_SHAPE, "%s: need lr_scale finite and >= 0 (got %g)", who, (double)lr_scale);
+    GV_REQUIRE(isfinite(wd) && wd >= 0.f, GV_E_SHAPE, "%s: need wd finite and >= 0 (got %g)", who, (double)wd);
+    GV_REQUIRE(beta1 >= 0.f && beta1 < 1.f, GV_E_SHAPE, "%s: need 0 <= beta1 < 1 (got %g)", who, (double)beta1);
+    GV_REQUIRE(beta2 >= 0.f && beta2 < 1.f, GV_E_SHAPE, "%s: need 0 <= beta2 < 1 (got %g)", who, (double)beta2);
+    GV_REQUIRE(isfinite(eps) && eps > 0.f, GV_E_SHAPE, "%s: need eps finite and > 0 (got %g)", who, (double)eps);
+    return GV_OK;
+}
+
+// Adam step `step` (1-based): the bias corrections in double (beta as the float the kernel multiplies by)
+void mil_set_step(MilP& p, float lr, float lr_scale, float beta1, float beta2, int64_t step) {
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    p.step_size = (float)((double)lr * (double)lr_scale / (bc1 > 0.0 ? bc1 : 1.0));
+    p.rsq_bc2 = (float)(1.0 / sqrt(bc2 > 0.0 ? bc2 : 1.0));
+}
+
+// predict: groups of at most 64 bags share the workspace
+int mil_predict_group(int n_bags) { return n_bags < MMAXBATCH ? (n_bags < 1 ? 1 : n_bags) : MMAXBATCH; }
+
+// the bags [0, n_bags) of a call in groups of `batch` (the last group takes the bags that are left): p.off and p.m, then launch()
+template <class Fn>
+void mil_each_group(MilP& p, int n_bags, int batch, Fn launch) {
+    for (int s0 = 0; s0 < n_bags; s0 += batch) {
+        p.off = s0;
+        p.m = n_bags - s0 < batch ? n_bags - s0 : batch;
+        launch();
+    }
+}
+
+template <bool TRAIN>
+void mil_launch_gate(const MilP& p, void* stream) {
+    hipLaunchKernelGGL(mil_gate_kernel<TRAIN>, dim3((unsigned)((p.max_bag + MT - 1) / MT), (unsigned)p.m, (unsigned)p.nch), dim3(256), 0,
+                       (hipStream_t)stream, p);
+}
+
+// (c)'s grid: 32-column slices of F by the 64-column blocks of [dt | dg | du] and one more row for dWc, the biases and the loss
+template <bool SURV>
+void mil_launch_update(const MilP& p, void* stream) {
+    const int ny = (3 * p.L + MT - 1) / MT;
+    hipLaunchKernelGGL(mil_update_kernel<SURV>, dim3((unsigned)((p.F + MFS - 1) / MFS), (unsigned)(ny + 1)), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 void mil_fill(MilP& p, const float* x, int64_t ldx, const int* bag_ptr, const int* labels, const int* bags, int N, int F, int L, int C,

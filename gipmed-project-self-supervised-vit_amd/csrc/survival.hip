@@ -3,12 +3,15 @@
 // The Cox loss couples the bags of a step (a bag's gradient depends on every other bag's risk), so the step is cut into four
 // launches, every dependency a launch boundary (no grid barrier, no atomics):
 //   mil_gate_kernel    unchanged (mil_common.h).
-//   surv_pool_kernel   one workgroup per bag: scores, softmax, z and the risk theta_b = Wc . z + bc.  With one output dz_b =
+//   surv_pool_kernel   one workgroup per bag: scores, softmax, z (bag_softmax_pool, mil_common.h, as in mil_pool_kernel) and the
+//                      risk theta_b = Wc . z + bc, this kernel's own middle.  With one output dz_b =
 //                      dtheta_b Wc, so the backward down to the scores is linear in dtheta_b: the launch leaves the unit-gradient
-//                      ds~_i = a_i (u_i - sum_j a_j u_j), u_i = Wc . x_i, and dbw~ = sum_i ds~_i.  Predict stops after theta.
+//                      ds~_i = a_i (u_i - sum_j a_j u_j), u_i = Wc . x_i, and dbw~ = sum_i ds~_i (bag_score_grad on Wc).  Predict
+//                      stops after theta.
 //   surv_cox_kernel    one workgroup per bag, each from the step's <= 64 risks (O(m^2), the same arithmetic in every workgroup):
 //                      M, S_i, its own dtheta_b and event term, then ds_i = dtheta_b ds~_i over the bag's rows and dbw_b.
 //   mil_update_kernel  <SURV>: DL[b] = dtheta_b, the gradient of bc forced to zero, nothing at all in a step without an event.
+// The entry points are the MIL probe's step driver (mil_common.h) with one more launch and the time / event / EV pointers.
 // Sums run in step order (j, i), row order or over a fixed tree: results are bitwise the same run to run.
 // gv_cox_eval: the cohort's partial likelihood in fp64 and the pair counts of Harrell's C, all pairs, a workgroup per row.
 #include "mil_common.h"
@@ -41,51 +44,7 @@ __global__ __launch_bounds__(256) void surv_pool_kernel(MilP p) {
         }
         return;
     }
-    const long slot0 = (long)b * p.max_bag;
-    const float bw = p.P[p.oB + 3 * L + 1];
-    float mx = -INFINITY;
-    for (int i = t; i < n; i += 256) {
-        float s = bw;
-        for (int ch = 0; ch < p.nch; ++ch) s += p.SP[(slot0 + i) * MMAXCH + ch];
-        sS[i] = s;
-        mx = fmaxf(mx, s);
-        if (!TRAIN && p.score) p.score[start + i] = s;
-    }
-    mx = mil_block_max(mx, red, t);
-    float ps = 0.f;
-    for (int i = t; i < n; i += 256) {               // rows past the bag are not in the sum
-        const float e = expf(sS[i] - mx);
-        sS[i] = e;
-        ps += e;
-    }
-    const float den = mil_block_sum(ps, red, t);
-    for (int i = t; i < n; i += 256) {
-        const float a = sS[i] / den;
-        sS[i] = a;
-        if (!TRAIN && p.attn) p.attn[start + i] = a;
-    }
-    __syncthreads();
-    // z = sum_i a_i x_i: 256 columns at a time, wave w the rows w, w + 4, .. in order, the four waves' sums then added in order
-    for (int c0 = 0; c0 < F; c0 += 256) {
-        const int col = c0 + lane * 4;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        if (col < F) {
-            const float* xp = p.x + (long)start * p.ldx + col;
-#pragma unroll 4
-            for (int i = wave; i < n; i += 4) {
-                const f32x4 xv = *(const f32x4*)(xp + (long)i * p.ldx);
-                const float a = sS[i];
-                acc[0] = fmaf(a, xv[0], acc[0]); acc[1] = fmaf(a, xv[1], acc[1]);
-                acc[2] = fmaf(a, xv[2], acc[2]); acc[3] = fmaf(a, xv[3], acc[3]);
-            }
-        }
-        *(f32x4*)(zpart + wave * 256 + lane * 4) = acc;
-        __syncthreads();
-        if (c0 + t < F) sZ[c0 + t] = ((zpart[t] + zpart[256 + t]) + zpart[512 + t]) + zpart[768 + t];
-        __syncthreads();
-    }
-    if (TRAIN)
-        for (int f = t; f < F; f += 256) p.Z[(long)b * F + f] = sZ[f];
+    bag_softmax_pool<TRAIN>(p, b, start, n, p.P[p.oB + 3 * L + 1], sS, sZ, zpart, red);
     // the risk: a lane's columns in order, then the wave's fixed tree (the MIL probe's logit at C = 1)
     const float* Wc = p.P + p.oWc;
     if (wave == 0) {
@@ -106,29 +65,7 @@ __global__ __launch_bounds__(256) void surv_pool_kernel(MilP p) {
     __syncthreads();
     for (int f = t; f < F; f += 256) sZ[f] = Wc[f];
     __syncthreads();
-    for (int i = wave; i < n; i += 4) {              // u_i = Wc . x_i
-        const float* xp = p.x + (long)(start + i) * p.ldx;
-        float acc = 0.f;
-        for (int f = lane * 4; f < F; f += 256) {
-            const f32x4 xv = *(const f32x4*)(xp + f);
-            acc = fmaf(sZ[f], xv[0], acc); acc = fmaf(sZ[f + 1], xv[1], acc);
-            acc = fmaf(sZ[f + 2], xv[2], acc); acc = fmaf(sZ[f + 3], xv[3], acc);
-        }
-        acc = wave_sum(acc);
-        if (lane == 0) sU[TRAIN ? i : 0] = acc;
-    }
-    __syncthreads();
-    float pd = 0.f;
-    for (int i = t; i < n; i += 256) pd = fmaf(sS[i], sU[TRAIN ? i : 0], pd);
-    const float dot = mil_block_sum(pd, red, t);
-    float pb = 0.f;
-    for (int i = t; i < n; i += 256) {
-        const float ds = sS[i] * (sU[TRAIN ? i : 0] - dot);
-        p.DS[slot0 + i] = ds;
-        pb += ds;
-    }
-    const float dbw = mil_block_sum(pb, red, t);
-    if (t == 0) p.DBW[b] = dbw;
+    bag_score_grad(p, b, start, n, sS, sU, sZ, red);              // u_i = Wc . x_i, then the unit-gradient ds~_i and dbw~
 }
 
 // (c) bag b of the step: Cox's dtheta_b and event term from the step's risks, then the bag's rows scaled
@@ -327,38 +264,23 @@ extern "C" int gv_surv_train(const gv_surv_train_args* a, void* stream) {
     int rc = mil_check_shape(who, a->batch, a->max_bag, a->L, 1, a->F);
     if (rc != GV_OK) return rc;
     const MilWs w = mil_workspace(a->batch, a->max_bag, a->L, a->F);
-    if ((rc = mil_check_common(who, a->x, a->ldx, a->F, a->N, a->n_all_bags, a->n_bags, a->params, a->workspace, a->workspace_bytes,
-                               surv_workspace_floats(w) * 4)) != GV_OK)
+    if ((rc = mil_check_common(who, "gv_surv_workspace_bytes", a->x, a->ldx, a->F, a->N, a->n_all_bags, a->n_bags, a->params, a->workspace,
+                               a->workspace_bytes, surv_workspace_floats(w) * 4)) != GV_OK)
         return rc;
-    GV_REQUIRE(gv_aligned(a->m, 16) && gv_aligned(a->v, 16), GV_E_ALIGN, "%s: m and v must be 16-byte aligned", who);
-    GV_REQUIRE(a->step0 >= 0, GV_E_SHAPE, "%s: need step0 >= 0 (got %d)", who, a->step0);
-    GV_REQUIRE(isfinite(a->lr) && a->lr > 0.f, GV_E_SHAPE, "%s: need lr finite and > 0 (got %g)", who, (double)a->lr);
-    GV_REQUIRE(isfinite(a->lr_scale) && a->lr_scale >= 0.f, GV_E_SHAPE, "%s: need lr_scale finite and >= 0 (got %g)", who, (double)a->lr_scale);
-    GV_REQUIRE(isfinite(a->wd) && a->wd >= 0.f, GV_E_SHAPE, "%s: need wd finite and >= 0 (got %g)", who, (double)a->wd);
-    GV_REQUIRE(a->beta1 >= 0.f && a->beta1 < 1.f, GV_E_SHAPE, "%s: need 0 <= beta1 < 1 (got %g)", who, (double)a->beta1);
-    GV_REQUIRE(a->beta2 >= 0.f && a->beta2 < 1.f, GV_E_SHAPE, "%s: need 0 <= beta2 < 1 (got %g)", who, (double)a->beta2);
-    GV_REQUIRE(isfinite(a->eps) && a->eps > 0.f, GV_E_SHAPE, "%s: need eps finite and > 0 (got %g)", who, (double)a->eps);
+    if ((rc = mil_check_adam(who, a->m, a->v, a->step0, a->lr, a->lr_scale, a->wd, a->beta1, a->beta2, a->eps)) != GV_OK) return rc;
     MilP p = {};
     mil_fill(p, a->x, a->ldx, a->bag_ptr, nullptr, a->bags, a->N, a->F, a->L, 1, a->n_all_bags, a->max_bag, a->params, a->workspace, w);
     p.time = a->time; p.event = a->event; p.EV = (float*)a->workspace + w.total;
     p.Pm = a->m; p.Pv = a->v; p.loss = a->loss_sum;
     p.wd = a->wd; p.beta1 = a->beta1; p.beta2 = a->beta2; p.eps = a->eps;
-    const int ny = (3 * a->L + MT - 1) / MT;
     int64_t step = a->step0;
-    for (int s0 = 0; s0 < a->n_bags; s0 += a->batch) {       // the last step takes the bags that are left
-        ++step;
-        p.off = s0;
-        p.m = a->n_bags - s0 < a->batch ? a->n_bags - s0 : a->batch;
-        // the bias corrections in double (beta as the float the kernel multiplies by)
-        const double bc1 = 1.0 - pow((double)a->beta1, (double)step), bc2 = 1.0 - pow((double)a->beta2, (double)step);
-        p.step_size = (float)((double)a->lr * (double)a->lr_scale / (bc1 > 0.0 ? bc1 : 1.0));
-        p.rsq_bc2 = (float)(1.0 / sqrt(bc2 > 0.0 ? bc2 : 1.0));
-        hipLaunchKernelGGL(mil_gate_kernel<true>, dim3((unsigned)((a->max_bag + MT - 1) / MT), (unsigned)p.m, (unsigned)p.nch), dim3(256), 0,
-                           (hipStream_t)stream, p);
+    mil_each_group(p, a->n_bags, a->batch, [&] {
+        mil_set_step(p, a->lr, a->lr_scale, a->beta1, a->beta2, ++step);
+        mil_launch_gate<true>(p, stream);
         hipLaunchKernelGGL(surv_pool_kernel<true>, dim3((unsigned)p.m), dim3(256), 0, (hipStream_t)stream, p);
         hipLaunchKernelGGL(surv_cox_kernel, dim3((unsigned)p.m), dim3(256), 0, (hipStream_t)stream, p);
-        hipLaunchKernelGGL(mil_update_kernel<true>, dim3((unsigned)((a->F + MFS - 1) / MFS), (unsigned)(ny + 1)), dim3(256), 0, (hipStream_t)stream, p);
-    }
+        mil_launch_update<true>(p, stream);
+    });
     GV_LAUNCH_CHECK(who);
     return GV_OK;
 }
@@ -366,23 +288,20 @@ extern "C" int gv_surv_train(const gv_surv_train_args* a, void* stream) {
 extern "C" int gv_surv_predict(const gv_surv_predict_args* a, void* stream) {
     const char* who = "gv_surv_predict";
     GV_REQUIRE(a && a->params && a->x && a->bag_ptr && a->risk, GV_E_NULL, "%s: null pointer (params, x, bag_ptr and risk are required)", who);
-    const int M = a->n_bags < MMAXBATCH ? (a->n_bags < 1 ? 1 : a->n_bags) : MMAXBATCH;      // groups of at most 64 bags share the workspace
+    const int M = mil_predict_group(a->n_bags);
     int rc = mil_check_shape(who, M, a->max_bag, a->L, 1, a->F);
     if (rc != GV_OK) return rc;
     const MilWs w = mil_workspace(M, a->max_bag, a->L, a->F);
-    if ((rc = mil_check_common(who, a->x, a->ldx, a->F, a->N, a->n_all_bags, a->n_bags, a->params, a->workspace, a->workspace_bytes,
-                               surv_workspace_floats(w) * 4)) != GV_OK)
+    if ((rc = mil_check_common(who, "gv_surv_workspace_bytes", a->x, a->ldx, a->F, a->N, a->n_all_bags, a->n_bags, a->params, a->workspace,
+                               a->workspace_bytes, surv_workspace_floats(w) * 4)) != GV_OK)
         return rc;
     MilP p = {};
     mil_fill(p, a->x, a->ldx, a->bag_ptr, nullptr, a->bags, a->N, a->F, a->L, 1, a->n_all_bags, a->max_bag, const_cast<float*>(a->params), a->workspace, w);
     p.prob = a->risk; p.attn = a->attn; p.score = a->score;
-    for (int s0 = 0; s0 < a->n_bags; s0 += M) {
-        p.off = s0;
-        p.m = a->n_bags - s0 < M ? a->n_bags - s0 : M;
-        hipLaunchKernelGGL(mil_gate_kernel<false>, dim3((unsigned)((a->max_bag + MT - 1) / MT), (unsigned)p.m, (unsigned)p.nch), dim3(256), 0,
-                           (hipStream_t)stream, p);
+    mil_each_group(p, a->n_bags, M, [&] {
+        mil_launch_gate<false>(p, stream);
         hipLaunchKernelGGL(surv_pool_kernel<false>, dim3((unsigned)p.m), dim3(256), 0, (hipStream_t)stream, p);
-    }
+    });
     GV_LAUNCH_CHECK(who);
     return GV_OK;
 }

@@ -3,6 +3,7 @@ HIP stream.  PyTorch is plumbing here (device memory, streams); all arithmetic
 runs in libgipvit_hip.so.  Every function launches asynchronously."""
 from __future__ import annotations
 
+import functools
 from typing import Optional, Sequence
 
 import torch
@@ -592,7 +593,25 @@ def l2norm_bwd(dy, y, inv_norm, dx, rows: int, C: int):
     L.call("gv_l2norm_bwd" + _sfx(y), L.gv_l2norm_bwd_args(dy.data_ptr(), y.data_ptr(), inv_norm.data_ptr(), dx.data_ptr(), rows, C), _stream())
 
 
-_knn_workspace: dict = {}        # device -> uint8 scratch of knn_vote, grown on demand and kept
+_KINDS = ("knn", "linprobe", "mil", "surv", "cox_eval")
+_workspaces = {k: {} for k in _KINDS}    # kind -> {device -> uint8 scratch of that kind's calls, grown on demand and kept}
+
+
+def _scratch(kind: str, dev, *dims):
+    """The per-device scratch of ``kind`` (one of _KINDS), at least gv_<kind>_workspace_bytes(*dims) bytes."""
+    need = getattr(L.lib, f"gv_{kind}_workspace_bytes")(*dims)
+    if need < 0:
+        raise L.GipvitError(f"gv_{kind}_workspace_bytes: {L.lib.gv_last_error().decode()}")
+    kept = _workspaces[kind]
+    ws = kept.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = kept[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+# the names the buffers and their helpers had when every kind kept its own: the same dicts, _scratch with the kind filled in
+_knn_workspace, _linprobe_workspace, _mil_workspace, _surv_workspace, _cox_workspace = (_workspaces[k] for k in _KINDS)
+_linprobe_scratch, _mil_scratch, _surv_scratch, _cox_scratch = (functools.partial(_scratch, k) for k in _KINDS[1:])
 
 
 def knn_vote(q, bank, labels, k: int, temp: float, C: int, *, n_split: int = 0, want_topk: bool = False):
@@ -611,12 +630,7 @@ def knn_vote(q, bank, labels, k: int, temp: float, C: int, *, n_split: int = 0, 
     if not temp > 0:
         raise ValueError(f"knn_vote: temp must be > 0 (got {temp})")
     (Q, D), Nb = q.shape, bank.shape[0]
-    need = L.lib.gv_knn_workspace_bytes(Q, Nb, k, n_split)
-    if need < 0:
-        raise L.GipvitError(f"gv_knn_workspace_bytes: {L.lib.gv_last_error().decode()}")
-    ws = _knn_workspace.get(q.device)
-    if ws is None or ws.numel() < need:
-        ws = _knn_workspace[q.device] = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ws = _scratch("knn", q.device, Q, Nb, k, n_split)
     votes = torch.empty(Q, C, dtype=f32, device=q.device)
     top_sim = torch.empty(Q, k, dtype=f32, device=q.device) if want_topk else None
     top_idx = torch.empty(Q, k, dtype=torch.int32, device=q.device) if want_topk else None
@@ -624,19 +638,6 @@ def knn_vote(q, bank, labels, k: int, temp: float, C: int, *, n_split: int = 0, 
                            Q, Nb, D, k, C, n_split, q.stride(0), bank.stride(0), 1.0 / temp)
     L.call("gv_knn_vote", a, _stream())
     return (votes, top_sim, top_idx) if want_topk else votes
-
-
-_linprobe_workspace: dict = {}   # device -> uint8 scratch of linprobe_train / linprobe_predict, grown on demand and kept
-
-
-def _linprobe_scratch(dev, M: int, H: int, C: int, F: int):
-    need = L.lib.gv_linprobe_workspace_bytes(M, H, C, F)
-    if need < 0:
-        raise L.GipvitError(f"gv_linprobe_workspace_bytes: {L.lib.gv_last_error().decode()}")
-    ws = _linprobe_workspace.get(dev)
-    if ws is None or ws.numel() < need:
-        ws = _linprobe_workspace[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return ws
 
 
 def _linprobe_heads(who: str, W, b, x):
@@ -666,7 +667,7 @@ def linprobe_train(W, b, mW, mb, lr, wd, x, labels, rows, loss_sum, batch: int, 
         raise ValueError(f"linprobe_train: labels must be a contiguous int32 [{x.shape[0]}] on {x.device}, got {tuple(labels.shape)}")
     if rows.dim() != 1 or not rows.is_contiguous() or rows.device != x.device:
         raise ValueError(f"linprobe_train: rows must be a contiguous int32 vector on {x.device}, got {tuple(rows.shape)}")
-    ws = _linprobe_scratch(x.device, batch, H, C, F)
+    ws = _scratch("linprobe", x.device, batch, H, C, F)
     a = L.gv_linprobe_train_args(W.data_ptr(), b.data_ptr(), mW.data_ptr(), mb.data_ptr(), lr.data_ptr(), wd.data_ptr(), x.data_ptr(),
                                  labels.data_ptr(), rows.data_ptr(), loss_sum.data_ptr(), ws.data_ptr(), ws.numel(), x.stride(0),
                                  x.shape[0], F, H, C, rows.shape[0], batch, lr_scale, momentum)
@@ -682,26 +683,13 @@ def linprobe_predict(W, b, x, labels=None):
         _chk(labels, torch.int32, "labels")
         if labels.dim() != 1 or labels.shape[0] != Q or not labels.is_contiguous() or labels.device != x.device:
             raise ValueError(f"linprobe_predict: labels must be a contiguous int32 [{Q}] on {x.device}, got {tuple(labels.shape)}")
-    ws = _linprobe_scratch(x.device, max(1, min(Q, 4096)), H, C, F)
+    ws = _scratch("linprobe", x.device, max(1, min(Q, 4096)), H, C, F)
     prob = torch.empty(Q, H, C, dtype=f32, device=x.device)
     loss = torch.empty(H, dtype=f32, device=x.device) if labels is not None else None
     a = L.gv_linprobe_predict_args(W.data_ptr(), b.data_ptr(), x.data_ptr(), _p(labels), prob.data_ptr(), _p(loss), ws.data_ptr(), ws.numel(),
                                    x.stride(0), Q, F, H, C)
     L.call("gv_linprobe_predict", a, _stream())
     return prob if labels is None else (prob, loss)
-
-
-_mil_workspace: dict = {}   # device -> uint8 scratch of mil_train / mil_predict, grown on demand and kept
-
-
-def _mil_scratch(dev, batch: int, max_bag: int, Lh: int, C: int, F: int):
-    need = L.lib.gv_mil_workspace_bytes(batch, max_bag, Lh, C, F)
-    if need < 0:
-        raise L.GipvitError(f"gv_mil_workspace_bytes: {L.lib.gv_last_error().decode()}")
-    ws = _mil_workspace.get(dev)
-    if ws is None or ws.numel() < need:
-        ws = _mil_workspace[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return ws
 
 
 def _mil_inputs(who: str, params, x, bag_ptr, labels, bags, Lh: int, C: int):
@@ -728,6 +716,22 @@ def _mil_inputs(who: str, params, x, bag_ptr, labels, bags, Lh: int, C: int):
     return F, n_all
 
 
+def _mil_state(who: str, params, m, v, loss_sum, width: int, dev):
+    """The moments against the packed parameters, and the loss_sum row of ``width`` sums."""
+    for t, nm, shape in ((m, "m", tuple(params.shape)), (v, "v", tuple(params.shape)), (loss_sum, "loss_sum", (width,))):
+        _chk(t, f32, nm)
+        if tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{who}: {nm} must be a contiguous f32 {list(shape)} on {dev}, got {tuple(t.shape)} on {t.device}")
+
+
+def _tile_outputs(out: dict, x, want_attn: bool, want_score: bool):
+    """The tail of a predict's dict: attn / score f32 [N] zeros where asked for, after what ``out`` already holds -> (attn, score)."""
+    for nm, want in (("attn", want_attn), ("score", want_score)):
+        if want:
+            out[nm] = torch.zeros(x.shape[0], dtype=f32, device=x.device)
+    return out.get("attn"), out.get("score")
+
+
 def mil_train(params, m, v, x, bag_ptr, labels, bags, loss_sum, hidden: int, num_classes: int, batch: int, max_bag: int, step0: int, lr: float,
               lr_scale: float = 1.0, wd: float = 0.0, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8):
     """Adam steps of the gated-attention MIL model on frozen features (gv_mil_train), in place: params / m / v f32 [P] packed as
@@ -737,11 +741,8 @@ def mil_train(params, m, v, x, bag_ptr, labels, bags, loss_sum, hidden: int, num
     F, n_all = _mil_inputs("mil_train", params, x, bag_ptr, labels, bags, hidden, num_classes)
     if labels is None or bags is None:
         raise ValueError("mil_train: labels and bags are required")
-    for t, nm, shape in ((m, "m", tuple(params.shape)), (v, "v", tuple(params.shape)), (loss_sum, "loss_sum", (1,))):
-        _chk(t, f32, nm)
-        if tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
-            raise ValueError(f"mil_train: {nm} must be a contiguous f32 {list(shape)} on {x.device}, got {tuple(t.shape)} on {t.device}")
-    ws = _mil_scratch(x.device, batch, max_bag, hidden, num_classes, F)
+    _mil_state("mil_train", params, m, v, loss_sum, 1, x.device)
+    ws = _scratch("mil", x.device, batch, max_bag, hidden, num_classes, F)
     a = L.gv_mil_train_args(params.data_ptr(), m.data_ptr(), v.data_ptr(), x.data_ptr(), bag_ptr.data_ptr(), labels.data_ptr(), bags.data_ptr(),
                             loss_sum.data_ptr(), ws.data_ptr(), ws.numel(), x.stride(0), x.shape[0], F, hidden, num_classes, n_all, bags.shape[0],
                             batch, max_bag, step0, lr, lr_scale, wd, beta1, beta2, eps)
@@ -763,45 +764,14 @@ def mil_predict(params, x, bag_ptr, hidden: int, num_classes: int, max_bag: int,
     accumulate = loss is not None
     if labels is not None and loss is None:
         loss = torch.empty(1, dtype=f32, device=x.device)
-    ws = _mil_scratch(x.device, max(1, min(n_bags, 64)), max_bag, hidden, num_classes, F)
+    ws = _scratch("mil", x.device, max(1, min(n_bags, 64)), max_bag, hidden, num_classes, F)
     prob = torch.empty(n_bags, num_classes, dtype=f32, device=x.device)
-    attn = torch.zeros(x.shape[0], dtype=f32, device=x.device) if want_attn else None
-    score = torch.zeros(x.shape[0], dtype=f32, device=x.device) if want_score else None
+    out = dict(prob=prob) if loss is None else dict(prob=prob, loss=loss)
+    attn, score = _tile_outputs(out, x, want_attn, want_score)
     a = L.gv_mil_predict_args(params.data_ptr(), x.data_ptr(), bag_ptr.data_ptr(), _p(labels), _p(bags), prob.data_ptr(), _p(loss), _p(attn), _p(score),
                               ws.data_ptr(), ws.numel(), x.stride(0), x.shape[0], F, hidden, num_classes, n_all, n_bags, max_bag, int(accumulate))
     L.call("gv_mil_predict", a, _stream())
-    out = dict(prob=prob)
-    if loss is not None:
-        out["loss"] = loss
-    if attn is not None:
-        out["attn"] = attn
-    if score is not None:
-        out["score"] = score
     return out
-
-
-_surv_workspace: dict = {}  # device -> uint8 scratch of surv_train / surv_predict, grown on demand and kept
-_cox_workspace: dict = {}   # device -> uint8 scratch of cox_eval
-
-
-def _surv_scratch(dev, batch: int, max_bag: int, Lh: int, F: int):
-    need = L.lib.gv_surv_workspace_bytes(batch, max_bag, Lh, F)
-    if need < 0:
-        raise L.GipvitError(f"gv_surv_workspace_bytes: {L.lib.gv_last_error().decode()}")
-    ws = _surv_workspace.get(dev)
-    if ws is None or ws.numel() < need:
-        ws = _surv_workspace[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return ws
-
-
-def _cox_scratch(dev, n: int):
-    need = L.lib.gv_cox_eval_workspace_bytes(n)
-    if need < 0:
-        raise L.GipvitError(f"gv_cox_eval_workspace_bytes: {L.lib.gv_last_error().decode()}")
-    ws = _cox_workspace.get(dev)
-    if ws is None or ws.numel() < need:
-        ws = _cox_workspace[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return ws
 
 
 def _surv_table(who: str, time, event, n: int, dev):
@@ -821,11 +791,8 @@ def surv_train(params, m, v, x, bag_ptr, time, event, bags, loss_sum, hidden: in
     if time is None or event is None or bags is None:
         raise ValueError("surv_train: time, event and bags are required")
     _surv_table("surv_train", time, event, n_all, x.device)
-    for t, nm, shape in ((m, "m", tuple(params.shape)), (v, "v", tuple(params.shape)), (loss_sum, "loss_sum", (2,))):
-        _chk(t, f32, nm)
-        if tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
-            raise ValueError(f"surv_train: {nm} must be a contiguous f32 {list(shape)} on {x.device}, got {tuple(t.shape)} on {t.device}")
-    ws = _surv_scratch(x.device, batch, max_bag, hidden, F)
+    _mil_state("surv_train", params, m, v, loss_sum, 2, x.device)
+    ws = _scratch("surv", x.device, batch, max_bag, hidden, F)
     a = L.gv_surv_train_args(params.data_ptr(), m.data_ptr(), v.data_ptr(), x.data_ptr(), bag_ptr.data_ptr(), time.data_ptr(), event.data_ptr(),
                              bags.data_ptr(), loss_sum.data_ptr(), ws.data_ptr(), ws.numel(), x.stride(0), x.shape[0], F, hidden, n_all, bags.shape[0],
                              batch, max_bag, step0, lr, lr_scale, wd, beta1, beta2, eps)
@@ -837,18 +804,12 @@ def surv_predict(params, x, bag_ptr, hidden: int, max_bag: int, bags=None, want_
     attn / score f32 [N]: a_i after and s_i before the bag's softmax, zero in rows no predicted bag covers)."""
     F, n_all = _mil_inputs("surv_predict", params, x, bag_ptr, None, bags, hidden, 1)
     n_bags = n_all if bags is None else bags.shape[0]
-    ws = _surv_scratch(x.device, max(1, min(n_bags, 64)), max_bag, hidden, F)
-    risk = torch.empty(n_bags, dtype=f32, device=x.device)
-    attn = torch.zeros(x.shape[0], dtype=f32, device=x.device) if want_attn else None
-    score = torch.zeros(x.shape[0], dtype=f32, device=x.device) if want_score else None
-    a = L.gv_surv_predict_args(params.data_ptr(), x.data_ptr(), bag_ptr.data_ptr(), _p(bags), risk.data_ptr(), _p(attn), _p(score),
+    ws = _scratch("surv", x.device, max(1, min(n_bags, 64)), max_bag, hidden, F)
+    out = dict(risk=torch.empty(n_bags, dtype=f32, device=x.device))
+    attn, score = _tile_outputs(out, x, want_attn, want_score)
+    a = L.gv_surv_predict_args(params.data_ptr(), x.data_ptr(), bag_ptr.data_ptr(), _p(bags), out["risk"].data_ptr(), _p(attn), _p(score),
                                ws.data_ptr(), ws.numel(), x.stride(0), x.shape[0], F, hidden, n_all, n_bags, max_bag)
     L.call("gv_surv_predict", a, _stream())
-    out = dict(risk=risk)
-    if attn is not None:
-        out["attn"] = attn
-    if score is not None:
-        out["score"] = score
     return out
 
 
@@ -860,7 +821,7 @@ def cox_eval(risk, time, event):
         raise ValueError(f"cox_eval: risk must be a contiguous f32 vector, got {tuple(risk.shape)}")
     n = risk.shape[0]
     _surv_table("cox_eval", time, event, n, risk.device)
-    ws = _cox_scratch(risk.device, n)
+    ws = _scratch("cox_eval", risk.device, n)
     loss = torch.empty(1, dtype=torch.float64, device=risk.device)
     counts = torch.empty(6, dtype=torch.int64, device=risk.device)
     a = L.gv_cox_eval_args(risk.data_ptr(), time.data_ptr(), event.data_ptr(), loss.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), n)

@@ -20,9 +20,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .knn import FeatureMonitor, collect_features
-from .linprobe import epoch_permutations, lr_scale_at
-from .mil import BETA1, BETA2, EPS, MAX_BAG, MAX_BATCH, MAX_FEATURES, MAX_HIDDEN, bag_table, init_params, param_views
+from .knn import collect_features
+from .mil import BETA1, BETA2, EPS, MAX_BAG, MAX_BATCH, MAX_FEATURES, MAX_HIDDEN, BagProbe, bag_table, init_params, param_views
 
 f32 = torch.float32
 MAX_COHORT = 65536          # gv_cox_eval's largest cohort
@@ -71,41 +70,21 @@ def surv_metrics(risk, time, event) -> "OrderedDict[str, float]":
     return OrderedDict(surv_cindex=cindex_reference(risk, time, event)[0], surv_loss=total / events if events else float("nan"))
 
 
-class SurvivalProbe(FeatureMonitor):
+class SurvivalProbe(BagProbe):
     """``runner``: an ``engine.FeatureExtractor`` of a CLS-token model; ``table``: slide name -> (time, event), event 1 =
     observed.  ``fit(bank_loader)`` then ``evaluate(query_loader)``.  ``train(feats, bag_ptr, time, event)`` is the device run on
     its own: features read back from <slide>_features.pt files train without an encoder (``runner`` and ``table`` may then be
     None with ``features=F``)."""
     prefix, metrics, auc_metrics, lower_is_better = "surv_", ("cindex", "loss"), (), ("loss",)
+    loss_width = 2
 
     def __init__(self, runner, table, hidden: int = 128, lr: float = 5e-4, weight_decay: float = 1e-4, epochs: int = 50, batch: int = 32,
                  n_last: int = 1, seed: int = 0, primary: bool = True, log: Optional[logging.Logger] = None, features: Optional[int] = None,
                  normaliser=None, num_classes: int = 1):
-        super().__init__(runner, 1, primary, log, normaliser)         # (num_classes: the monitors' common keyword; one risk output)
-        if hidden % 16 or not 16 <= hidden <= MAX_HIDDEN:
-            raise ValueError(f"SurvivalProbe: hidden must be a multiple of 16 in 16..{MAX_HIDDEN} (got {hidden})")
-        if not (math.isfinite(lr) and lr > 0) or not weight_decay >= 0:
-            raise ValueError(f"SurvivalProbe: need a positive finite lr and weight_decay >= 0 (got {lr}, {weight_decay})")
-        if epochs < 1 or not 1 <= batch <= MAX_BATCH:
-            raise ValueError(f"SurvivalProbe: need epochs >= 1 and 1 <= batch <= {MAX_BATCH} (got {epochs}, {batch})")
-        if runner is not None:
-            depth = runner.vit.depth
-            if not 1 <= n_last <= depth:
-                raise ValueError(f"SurvivalProbe: n_last must be in 1..{depth}, the model's depth (got {n_last})")
-            if table is None:
-                raise ValueError("SurvivalProbe: with a runner, pass the survival table (slide name -> (time, event))")
-            self.F = n_last * runner.D
-        elif features is None:
-            raise ValueError("SurvivalProbe: without a runner, pass features=F (the width of the saved feature rows)")
-        else:
-            self.F = int(features)
-        if self.F % 4 or not 4 <= self.F <= MAX_FEATURES:
-            raise ValueError(f"SurvivalProbe: {self.F} features per tile; the kernels take a multiple of 4 in 4..{MAX_FEATURES}")
+        # (num_classes: the monitors' common keyword; one risk output)
+        super().__init__(runner, 1, hidden, lr, weight_decay, epochs, batch, n_last, seed, primary, log, features, normaliser,
+                         runner_needs=None if table is not None else "with a runner, pass the survival table (slide name -> (time, event))")
         self.table = dict(table or {})
-        self.L, self.lr, self.wd, self.epochs, self.batch = hidden, float(lr), float(weight_decay), epochs, batch
-        self.n_last, self.seed = n_last, seed
-        self.params = None
-        self.train_loss = None
         self._warned = False
 
     def _collect(self, loader):
@@ -117,16 +96,6 @@ class SurvivalProbe(FeatureMonitor):
         ptr = bag_table(slides)
         rows = [self.table[names[int(slides[s])]] for s in ptr[:-1]]
         return feats, ptr, np.array([r[0] for r in rows], dtype=np.float32), np.array([r[1] for r in rows], dtype=np.int32), skipped
-
-    def _check_bags(self, who: str, feats, bag_ptr):
-        if feats.dim() != 2 or feats.shape[1] != self.F:
-            raise ValueError(f"SurvivalProbe.{who}: features of shape {tuple(feats.shape)}, expected [N, {self.F}]")
-        ptr = np.asarray(bag_ptr).reshape(-1).astype(np.int64)
-        if len(ptr) < 2 or ptr[0] != 0 or ptr[-1] != feats.shape[0] or (np.diff(ptr) < 1).any():
-            raise ValueError(f"SurvivalProbe.{who}: bag_ptr must rise from 0 to {feats.shape[0]}, the feature rows, with no empty bag")
-        if np.diff(ptr).max() > MAX_BAG:
-            raise ValueError(f"SurvivalProbe.{who}: a bag of {int(np.diff(ptr).max())} tiles; the kernels stop at {MAX_BAG} per slide")
-        return ptr.astype(np.int32)
 
     def fit(self, bank_loader) -> int:
         """Train a fresh model on the bank's slides.  -> the number of training slides."""
@@ -142,7 +111,6 @@ class SurvivalProbe(FeatureMonitor):
         """The Adam run itself on device features f32 [N, F], the bag table [n + 1] and the host time / event vectors [n]: fresh
         parameters, one permutation of the bags per epoch, the cosine factor constant within an epoch.  Leaves ``params``
         (packed, device), the moments ``m`` / ``v`` and ``train_loss`` ([epochs]: the epoch's event terms over its events)."""
-        from . import ops
         ptr = self._check_bags("train", feats, bag_ptr)
         time, event = np.asarray(time, dtype=np.float32).reshape(-1), np.asarray(event).reshape(-1)
         n = len(ptr) - 1
@@ -150,24 +118,20 @@ class SurvivalProbe(FeatureMonitor):
             raise ValueError(f"SurvivalProbe.train: need {n} finite times >= 0 and {n} event flags in {{0, 1}}")
         if not event.any():
             raise ValueError("SurvivalProbe.train: the bank has no event (every slide is censored): the partial likelihood has no term")
-        dev = feats.device
-        self.params = init_params(self.L, 1, self.F, self.seed).to(dev)
-        self.m, self.v = torch.zeros_like(self.params), torch.zeros_like(self.params)
-        order = torch.from_numpy(epoch_permutations(n, self.epochs, self.seed).astype(np.int32)).to(dev)
-        ptr_d, t_d, e_d = torch.from_numpy(ptr).to(dev), torch.from_numpy(time).to(dev), torch.from_numpy(event.astype(np.int32)).to(dev)
-        loss = torch.zeros(self.epochs, 2, dtype=f32, device=dev)      # row e: epoch e's loss_sum
-        max_bag, steps = int(np.diff(ptr).max()), -(-n // self.batch)
-        for e in range(self.epochs):
-            ops.surv_train(self.params, self.m, self.v, feats, ptr_d, t_d, e_d, order[e], loss[e], self.L, self.batch, max_bag, e * steps,
-                           self.lr, lr_scale_at(e, self.epochs), self.wd, BETA1, BETA2, EPS)
-        sums = loss.double().cpu().numpy()                             # (the copy synchronises)
-        self.train_loss = [float(s / k) if k else float("nan") for s, k in sums]
+        self._run_epochs(feats, ptr, [time, event.astype(np.int32)])
+
+    def _epoch(self, feats, ptr, targets, bags, loss_sum, max_bag, step0, scale):
+        from . import ops
+        ops.surv_train(self.params, self.m, self.v, feats, ptr, targets[0], targets[1], bags, loss_sum, self.L, self.batch, max_bag, step0, self.lr,
+                       scale, self.wd, BETA1, BETA2, EPS)
+
+    def _epoch_losses(self, sums, n):
+        return [float(s / k) if k else float("nan") for s, k in sums]
 
     def predict(self, feats: torch.Tensor, bag_ptr, tiles: bool = False):
         """-> ops.surv_predict's dict for the bags of ``feats``."""
         from . import ops
-        if self.params is None:
-            raise RuntimeError("SurvivalProbe.predict: fit first")
+        self._fitted("predict")
         ptr = self._check_bags("predict", feats, bag_ptr)
         return ops.surv_predict(self.params, feats, torch.from_numpy(ptr).to(feats.device), self.L, int(np.diff(ptr).max()), want_attn=tiles,
                                 want_score=tiles)
@@ -195,17 +159,3 @@ class SurvivalProbe(FeatureMonitor):
             self.log.info("survival probe: %d query slides (%d events), %d tiles (%d left out): %s", len(time), int(event.sum()), feats.shape[0],
                           skipped, "  ".join(f"{n} {v:.4f}" for n, v in metrics.items()))
         return metrics
-
-    def tile_attention(self, loader):
-        """Per slide of the loader that was kept, in order: (attn f32 [n_tiles], score f32 [n_tiles]) host tensors -- the tile
-        weights after and before the slide's softmax."""
-        feats, ptr, _, _, _ = self._collect(loader)
-        out = self.predict(feats, ptr, tiles=True)
-        attn, score = out["attn"].cpu(), out["score"].cpu()
-        return [(attn[ptr[i]:ptr[i + 1]].clone(), score[ptr[i]:ptr[i + 1]].clone()) for i in range(len(ptr) - 1)]
-
-    def state_dict(self) -> "OrderedDict[str, torch.Tensor]":
-        """Host tensors under the names and shapes of the nn.Linear layers of an ABMIL module with one output."""
-        if self.params is None:
-            raise RuntimeError("SurvivalProbe.state_dict: fit first")
-        return OrderedDict((k, v.clone()) for k, v in param_views(self.params.detach().cpu(), self.L, 1, self.F).items())

@@ -32,12 +32,8 @@ def _poisoned_workspace(dev, Q, Nb, k, n_split=0):
     """The scratch ops.knn_vote keeps per device, all-ones (similarity NaN, index -1) for the next call: made large enough here, so
     that the call takes this buffer and not fresh, mostly zero, torch.empty memory.  The merge takes a list entry as an index only
     inside [0, Nb) (csrc/knn.hip), so a slot the scan never stored shows as a missing neighbour / NaN similarity, never as a read."""
-    from gipvit import _lib, ops
-    need = _lib.lib.gv_knn_workspace_bytes(Q, Nb, k, n_split)
-    ws = ops._knn_workspace.get(dev)
-    if ws is None or ws.numel() < need:
-        ws = ops._knn_workspace[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
-    ws.fill_(255)
+    from gipvit import ops
+    ops._scratch("knn", dev, Q, Nb, k, n_split).fill_(255)
 
 
 def _vote(dev, q, bank, labels, k, C, n_split=0, want_topk=True):

@@ -27,8 +27,7 @@ def _poison_workspace(dev, M, H, C, F):
     """The scratch ops.linprobe_* keep per device, all-ones bit patterns (NaN) for the next call: a slot the first launch never
     wrote would show as a NaN in the result."""
     from gipvit import ops
-    ops._linprobe_scratch(dev, M, H, C, F)                                  # (grown if need be)
-    ops._linprobe_workspace[dev].fill_(255)
+    ops._scratch("linprobe", dev, M, H, C, F).fill_(255)                    # (grown if need be)
 
 
 def _train_gpu(dev, s, x_dev=None, perms=None):

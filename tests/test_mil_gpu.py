@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 import torch
 
+from probe_bits_cases import mil_train_gpu as _train_gpu, pad as _pad
 from test_mil_host import (BETA1, BETA2, CASES, CASE_IDS, EPS, NAMES, NEEDLE, case_reference, cosine_scale, draw_params, mil_predict_reference,
                            mil_reference, needle_bags, needle_check, pack)
 
@@ -38,40 +39,11 @@ def _poison_workspace(dev, batch, max_bag, L, C, F):
     """The scratch ops.mil_* keep per device, all-ones bit patterns (NaN) for the next call: a slot a launch reads without an
     earlier launch having written it would show as a NaN in the result."""
     from gipvit import ops
-    ops._mil_scratch(dev, batch, max_bag, L, C, F)
-    ops._mil_workspace[dev].fill_(255)
+    ops._scratch("mil", dev, batch, max_bag, L, C, F).fill_(255)
 
 
 def _bits(t):
     return t.contiguous().view(torch.int32)
-
-
-def _pad(x, ldx):
-    """x [N, F] as a view with row stride ldx (the padding holds NaN)."""
-    buf = torch.full((x.shape[0], ldx), float("nan"), dtype=f32)
-    buf[:, :x.shape[1]] = x
-    return buf
-
-
-def _train_gpu(dev, x, ptr, labels, packed0, perms, batch, L, C, lr, wd, ldx=None, max_bag=None, beta1=BETA1, beta2=BETA2, scale=None):
-    """The epochs on the device -> (params, m, v packed, loss_sum per epoch [epochs]), host tensors."""
-    from gipvit import ops
-    F = x.shape[1]
-    xd = (_pad(x, ldx).to(dev)[:, :F] if ldx and ldx > F else x.to(dev))
-    P = packed0.clone().to(dev)
-    m, v = torch.zeros_like(P), torch.zeros_like(P)
-    ptr_d, y = torch.from_numpy(np.asarray(ptr).astype(np.int32)).to(dev), torch.as_tensor(np.asarray(labels)).to(dev, torch.int32)
-    order = torch.from_numpy(np.asarray(perms).astype(np.int32)).to(dev)
-    epochs, n = order.shape
-    mb = int(np.diff(np.asarray(ptr)).max()) if max_bag is None else max_bag
-    loss = torch.zeros(epochs, 1, dtype=f32, device=dev)
-    _poison_workspace(dev, batch, mb, L, C, F)
-    steps = -(-n // batch)
-    for e in range(epochs):
-        ops.mil_train(P, m, v, xd, ptr_d, y, order[e], loss[e], L, C, batch, mb, e * steps, lr, cosine_scale(e, epochs) if scale is None else scale,
-                      wd, beta1, beta2, EPS)
-    torch.cuda.synchronize()
-    return P.cpu(), m.cpu(), v.cpu(), loss.cpu().reshape(-1)
 
 
 def _worst(got_packed, ref, L, C, F):

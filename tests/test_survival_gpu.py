@@ -30,6 +30,7 @@ import numpy as np
 import pytest
 import torch
 
+from probe_bits_cases import surv_train_gpu as _train_gpu, pad as _pad
 from test_mil_host import BETA1, BETA2, EPS, NAMES, cosine_scale, draw_params, pack
 from test_survival_host import (CASES, CASE_IDS, NEEDLE, case_reference, cohort, needle_perms, needle_survival, surv_predict_reference,
                                 surv_reference)
@@ -44,42 +45,11 @@ def _poison_workspace(dev, batch, max_bag, L, F):
     """The scratch ops.surv_* keep per device, all-ones bit patterns (NaN) for the next call: a slot a launch reads without an
     earlier launch having written it would show as a NaN in the result."""
     from gipvit import ops
-    ops._surv_scratch(dev, batch, max_bag, L, F)
-    ops._surv_workspace[dev].fill_(255)
+    ops._scratch("surv", dev, batch, max_bag, L, F).fill_(255)
 
 
 def _bits(t):
     return t.contiguous().view(torch.int32)
-
-
-def _pad(x, ldx):
-    buf = torch.full((x.shape[0], ldx), float("nan"), dtype=f32)
-    buf[:, :x.shape[1]] = x
-    return buf
-
-
-def _train_gpu(dev, x, ptr, time, event, packed0, perms, batch, L, lr, wd, ldx=None, max_bag=None, beta1=BETA1, beta2=BETA2, scale=None, step0=None,
-               state=None):
-    """The epochs on the device -> (params, m, v packed, loss_sum per epoch [epochs, 2]), host tensors."""
-    from gipvit import ops
-    F = x.shape[1]
-    xd = (_pad(x, ldx).to(dev)[:, :F] if ldx and ldx > F else x.to(dev))
-    P = packed0.clone().to(dev)
-    m, v = (torch.zeros_like(P), torch.zeros_like(P)) if state is None else (state[0].clone().to(dev), state[1].clone().to(dev))
-    ptr_d = torch.from_numpy(np.asarray(ptr).astype(np.int32)).to(dev)
-    t_d = torch.from_numpy(np.asarray(time, dtype=np.float32)).to(dev)
-    e_d = torch.from_numpy(np.asarray(event).astype(np.int32)).to(dev)
-    order = torch.from_numpy(np.asarray(perms).astype(np.int32)).to(dev)
-    epochs, n = order.shape
-    mb = int(np.diff(np.asarray(ptr)).max()) if max_bag is None else max_bag
-    loss = torch.zeros(epochs, 2, dtype=f32, device=dev)
-    _poison_workspace(dev, batch, mb, L, F)
-    steps = -(-n // batch)
-    for e in range(epochs):
-        ops.surv_train(P, m, v, xd, ptr_d, t_d, e_d, order[e], loss[e], L, batch, mb, e * steps if step0 is None else step0, lr,
-                       cosine_scale(e, epochs) if scale is None else scale, wd, beta1, beta2, EPS)
-    torch.cuda.synchronize()
-    return P.cpu(), m.cpu(), v.cpu(), loss.cpu()
 
 
 def _worst(got_packed, ref, L, F):
@@ -337,8 +307,7 @@ def test_cox_eval(dev, n, kind):
     want, events, excluded = cox_reference(risk, time, event)
     _, comp, conc, disc, tied = cindex_reference(risk, time, event)
     args = [torch.from_numpy(a).to(dev) for a in (risk, time, event)]
-    ops._cox_scratch(dev, n)
-    ops._cox_workspace[dev].fill_(255)
+    ops._scratch("cox_eval", dev, n).fill_(255)
     loss, counts = ops.cox_eval(*args)
     loss2, counts2 = ops.cox_eval(*args)
     torch.cuda.synchronize()

@@ -415,6 +415,7 @@ def test_surv_train_abi_errors():
     need = L.lib.gv_surv_workspace_bytes(8, 500, 128, 384)
     assert need > 0
     assert rc(workspace_bytes=need - 1) == -1 and str(need) in err() and "workspace" in err() and err().startswith("gv_surv_train")
+    assert "(gv_surv_workspace_bytes)" in err() and rc(workspace=None) == -3 and "gv_surv_workspace_bytes)" in err()
     assert rc(workspace=36864 + 4) == -2 and "workspace" in err()
 
 
@@ -434,7 +435,7 @@ def test_surv_predict_and_cox_eval_abi_errors():
     assert rc(ldx=380) == -1 and "ldx >= F" in err()
     assert rc(x=8192 + 4) == -2 and "16-byte aligned" in err()
     need = L.lib.gv_surv_workspace_bytes(64, 500, 128, 384)                  # more than 64 bags: groups of 64
-    assert rc(workspace_bytes=need - 1) == -1 and str(need) in err()
+    assert rc(workspace_bytes=need - 1) == -1 and str(need) in err() and "(gv_surv_workspace_bytes)" in err()
     small = L.lib.gv_surv_workspace_bytes(5, 500, 128, 384)
     assert 0 < small < need and rc(n_bags=5, workspace_bytes=small - 1) == -1 and str(small) in err()
     okc = dict(risk=4096, time=8192, event=12288, loss=16384, counts=20480, workspace=24576, workspace_bytes=1 << 40, n=1000)

@@ -2,11 +2,13 @@
 evaluation, on one GPU in one process.  Recorded once, no gate: nothing here is tuned.
 
 Shape: the MIL probe's measured one (tools/mil_bench.py): 1000 bags x 500 tiles, F = 384, L = 128, batch 8: 125 Adam steps per
-epoch, four launches per step (gv_surv_train) against three (gv_mil_train).  Epochs are timed with device events after a warm-up
-epoch, median of the repeats.  gv_cox_eval at n = 4096 (tied times and risks), median of the repeats after a warm-up call.
+epoch, four launches per step (gv_surv_train) against three (gv_mil_train).  A window is fresh parameters, a warm-up epoch and one
+epoch timed with device events; the rows take their windows in turn, REPEATS rounds, and report median, min and max.  gv_cox_eval
+at n = 4096 (tied times and risks), median of the repeats after a warm-up call.
 
-    python tools/surv_bench.py [OUT] [--mil-lib PATH]    # prints the table; OUT (profiles/survival.txt) also gets it
-``--mil-lib``: time gv_mil_train out of another build of the library (the commit before the survival probe) as well."""
+    python tools/surv_bench.py [OUT] [--parent-lib PATH]    # prints the table; OUT (profiles/survival.txt) also gets it
+``--parent-lib``: time gv_surv_train and gv_mil_train out of another build of the library (the parent commit's) as well, window
+by window in turn with this build's; a change that must not cost speed has each of its medians inside the parent's min .. max."""
 import ctypes
 import os
 import statistics
@@ -23,7 +25,7 @@ from gipvit.mil import init_params                        # noqa: E402
 
 dev = torch.device("cuda", 0)
 BAGS, TILES, F, LH, BATCH, LR, WD = 1000, 500, 384, 128, 8, 5e-4, 1e-4
-REPEATS, COHORT = 3, 4096
+REPEATS, COHORT = 7, 4096
 
 
 def timed(fn):
@@ -35,21 +37,19 @@ def timed(fn):
     return a.elapsed_time(b)
 
 
-def epochs(run, width):
-    out = []
-    for _ in range(REPEATS):
-        P = init_params(LH, 1, F, 0).to(dev)
-        st = (P, torch.zeros_like(P), torch.zeros_like(P), torch.zeros(2, width, device=dev))
-        run(st, 0)                                                         # warm-up epoch
-        torch.cuda.synchronize()
-        out.append(timed(lambda: run(st, 1)))
-    return out, st
+def window(run, width):
+    """Fresh parameters, a warm-up epoch, one timed epoch -> (ms, the state)."""
+    P = init_params(LH, 1, F, 0).to(dev)
+    st = (P, torch.zeros_like(P), torch.zeros_like(P), torch.zeros(2, width, device=dev))
+    run(st, 0)
+    torch.cuda.synchronize()
+    return timed(lambda: run(st, 1)), st
 
 
 def main():
     argv = [a for a in sys.argv[1:]]
-    other = argv.pop(argv.index("--mil-lib") + 1) if "--mil-lib" in argv else None
-    argv = [a for a in argv if a != "--mil-lib"]
+    other = argv.pop(argv.index("--parent-lib") + 1) if "--parent-lib" in argv else None
+    argv = [a for a in argv if a != "--parent-lib"]
     g = torch.Generator().manual_seed(0)
     x = torch.randn(BAGS * TILES, F, generator=g).to(dev)
     y = torch.zeros(BAGS, dtype=torch.int32, device=dev)
@@ -58,21 +58,36 @@ def main():
     ptr = torch.arange(0, BAGS * TILES + 1, TILES, dtype=torch.int32, device=dev)
     order = torch.from_numpy(epoch_permutations(BAGS, 2, 0).astype(np.int32)).to(dev)
     steps = -(-BAGS // BATCH)
-    surv, st = epochs(lambda s, e: ops.surv_train(s[0], s[1], s[2], x, ptr, time, event, order[e], s[3][e], LH, BATCH, TILES, e * steps, LR, 1.0, WD), 2)
-    loss = float(st[3][1, 0] / st[3][1, 1])
-    mil, _ = epochs(lambda s, e: ops.mil_train(s[0], s[1], s[2], x, ptr, y, order[e], s[3][e], LH, 1, BATCH, TILES, e * steps, LR, 1.0, WD), 1)
-    rows = [("gv_surv_train (4 launches per step)", surv), ("gv_mil_train at C = 1, this build (3 launches per step)", mil)]
+    entries = [("gv_surv_train (4 launches per step)",
+                lambda s, e: ops.surv_train(s[0], s[1], s[2], x, ptr, time, event, order[e], s[3][e], LH, BATCH, TILES, e * steps, LR, 1.0, WD), 2),
+               ("gv_mil_train at C = 1 (3 launches per step)",
+                lambda s, e: ops.mil_train(s[0], s[1], s[2], x, ptr, y, order[e], s[3][e], LH, 1, BATCH, TILES, e * steps, LR, 1.0, WD), 1)]
     if other:
         lib = ctypes.CDLL(other)
-        lib.gv_mil_train.argtypes, lib.gv_mil_train.restype = [ctypes.POINTER(L.gv_mil_train_args), ctypes.c_void_p], ctypes.c_int
-        ws = ops._mil_scratch(dev, BATCH, TILES, LH, 1, F)
+        for fn, st_ in ((lib.gv_surv_train, L.gv_surv_train_args), (lib.gv_mil_train, L.gv_mil_train_args)):
+            fn.argtypes, fn.restype = [ctypes.POINTER(st_), ctypes.c_void_p], ctypes.c_int
+        ws = ops._scratch("surv", dev, BATCH, TILES, LH, F)               # (the MIL workspace at C = 1 and four floats more)
+        tail = (ws.data_ptr(), ws.numel(), x.stride(0), x.shape[0], F, LH)
+        adam = lambda e: (BAGS, BAGS, BATCH, TILES, e * steps, LR, 1.0, WD, 0.9, 0.999, 1e-8)
 
-        def run(s, e):
+        def parent_surv(s, e):
+            a = L.gv_surv_train_args(s[0].data_ptr(), s[1].data_ptr(), s[2].data_ptr(), x.data_ptr(), ptr.data_ptr(), time.data_ptr(), event.data_ptr(),
+                                     order[e].data_ptr(), s[3][e].data_ptr(), *tail, *adam(e))
+            assert lib.gv_surv_train(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
+
+        def parent_mil(s, e):
             a = L.gv_mil_train_args(s[0].data_ptr(), s[1].data_ptr(), s[2].data_ptr(), x.data_ptr(), ptr.data_ptr(), y.data_ptr(), order[e].data_ptr(),
-                                    s[3][e].data_ptr(), ws.data_ptr(), ws.numel(), x.stride(0), x.shape[0], F, LH, 1, BAGS, BAGS, BATCH, TILES, e * steps,
-                                    LR, 1.0, WD, 0.9, 0.999, 1e-8)
+                                    s[3][e].data_ptr(), *tail, 1, *adam(e))
             assert lib.gv_mil_train(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
-        rows.append(("gv_mil_train at C = 1, the build before the probe", epochs(run, 1)[0]))
+        entries = [entries[0], ("gv_surv_train, the parent build", parent_surv, 2), entries[1], ("gv_mil_train at C = 1, the parent build", parent_mil, 1)]
+    wins = [[] for _ in entries]
+    for _ in range(REPEATS):                                               # the rows take their windows in turn
+        for k, (_, run, width) in enumerate(entries):
+            ms, st = window(run, width)
+            wins[k].append(ms)
+            if k == 0:
+                loss = float(st[3][1, 0] / st[3][1, 1])
+    rows = [(name, r) for (name, _, _), r in zip(entries, wins)]
     rng = np.random.Generator(np.random.PCG64(0))
     cr = torch.from_numpy((rng.integers(-64, 65, COHORT) / 16).astype(np.float32)).to(dev)
     ct = torch.from_numpy(rng.integers(1, 121, COHORT).astype(np.float32)).to(dev)
@@ -82,10 +97,14 @@ def main():
     cox = [timed(lambda: ops.cox_eval(cr, ct, ce)) for _ in range(REPEATS)]
     counts = ops.cox_eval(cr, ct, ce)[1].cpu().tolist()
     lines = [f"# tools/surv_bench.py on {torch.cuda.get_device_name(0)}; {BAGS} bags x {TILES} tiles, F = {F}, L = {LH}, batch {BATCH}: {steps} steps per "
-             f"epoch; device events, median of {REPEATS} after a warm-up epoch"]
+             f"epoch; device events, {REPEATS} windows per row taken in turn, each after a warm-up epoch"]
     for name, runs in rows:
         k = statistics.median(runs)
-        lines.append(f"one epoch, {name:<58} {k:9.3f} ms   = {1e3 * k / steps:.1f} us per step   runs " + " ".join(f"{v:.3f}" for v in runs))
+        lines.append(f"one epoch, {name:<44} median {k:8.3f} ms   min {min(runs):8.3f}   max {max(runs):8.3f}   = {1e3 * k / steps:.1f} us per step   runs "
+                     + " ".join(f"{v:.3f}" for v in runs))
+    for new, old in ((0, 1), (2, 3)) if other else ():
+        k, lo, hi = statistics.median(wins[new]), min(wins[old]), max(wins[old])
+        lines.append(f"{entries[new][0].split()[0]}: this build's median {k:.3f} ms is {'inside' if lo <= k <= hi else 'OUTSIDE'} the parent's {lo:.3f} .. {hi:.3f} ms")
     lines.append(f"second-epoch Cox loss per event (random times): {loss:.6f}")
     lines.append(f"gv_cox_eval, n = {COHORT} (3 launches, {counts[0]} events, {counts[1]} comparable pairs)   {1e3 * statistics.median(cox):9.1f} us   runs "
                  + " ".join(f"{1e3 * v:.1f}" for v in cox))

@@ -373,40 +373,8 @@ def check_supported(args, log=_logger.warning):
             raise SystemExit(f"--eval-metric {args.eval_metric}: the monitors of this run report {names} (a bare name is the k-NN monitor's "
                              "when that is on, else the probe's)")
     if args.mil_probe:
-        if not args.dino:
-            raise SystemExit("--mil-probe scores the DINO teacher's frozen features: it needs --dino (a supervised run has validate())")
-        if args.mil_hidden % 16 or not 16 <= args.mil_hidden <= 256:
-            raise SystemExit(f"--mil-hidden {args.mil_hidden}: a multiple of 16 in 16 .. 256 (gv_mil_train)")
-        if not (math.isfinite(args.mil_lr) and args.mil_lr > 0):
-            raise SystemExit(f"--mil-lr {args.mil_lr}: a positive finite rate")
-        if not args.mil_wd >= 0:
-            raise SystemExit(f"--mil-wd {args.mil_wd}: weight decay must be >= 0")
-        if args.mil_epochs < 1:
-            raise SystemExit(f"--mil-epochs {args.mil_epochs}: at least one pass over the bank's slides")
-        if not 1 <= args.mil_batch <= 64:
-            raise SystemExit(f"--mil-batch {args.mil_batch}: 1 .. 64 slides per step (gv_mil_train)")
-        from gipvit.archs import ARCHS, resolve_arch       # plain tables: nothing is loaded for them
-        spec = ARCHS[resolve_arch(args.model)]
-        if not 1 <= args.mil_layers <= spec["depth"]:
-            raise SystemExit(f"--mil-layers {args.mil_layers}: the last 1 .. {spec['depth']} blocks of {args.model}")
-        if args.mil_layers * spec["embed_dim"] > 4096:
-            raise SystemExit(f"--mil-layers {args.mil_layers}: {args.mil_layers * spec['embed_dim']} features per tile at width {spec['embed_dim']}, "
-                             "gv_mil_train stops at 4096")
-        if args.mil_rate < 0:
-            raise SystemExit(f"--mil-rate {args.mil_rate}: 0 = after the last epoch only, N >= 1 = every N epochs and the last")
-        if args.test_fold in (-1, "-1"):
-            raise SystemExit("--test_fold -1 with --mil-probe: no evaluation fold is left to score the slides of")
-        if args.tile_size < args.global_crop_size:
-            raise SystemExit(f"--mil-probe: the teacher sees {args.global_crop_size}-px images, the centred window of a {args.tile_size}-px "
-                             "tile (--tile-size) cannot be smaller than that")
-        if args.num_tiles > 4096:
-            raise SystemExit(f"--num_tiles {args.num_tiles} with --mil-probe: a slide's bag holds at most 4096 tiles (gv_mil_train)")
-        if args.knn_bank_tiles is not None and args.knn_bank_tiles > 4096:
-            raise SystemExit(f"--knn-bank-tiles {args.knn_bank_tiles} with --mil-probe: a slide's bag holds at most 4096 tiles (gv_mil_train)")
-        names = monitor_metric_names(args)
-        if resolve_eval_metric(args.eval_metric, bool(args.knn_monitor), bool(args.linear_probe), True) not in names:
-            raise SystemExit(f"--eval-metric {args.eval_metric}: the monitors of this run report {names} (a bare name is the k-NN monitor's "
-                             "when that is on, else the linear probe's, else the MIL probe's)")
+        check_bag_probe(args, "mil", "",
+                        lambda: resolve_eval_metric(args.eval_metric, bool(args.knn_monitor), bool(args.linear_probe), True))
     if getattr(args, "surv_probe", False):
         check_surv_probe(args)
     check_ibot(args)
@@ -520,42 +488,52 @@ def check_token_limits(args):
                              f"{ATTN_F32_MAX_TOKENS} tokens (256 px); larger tiles run in the 16-bit mode")
 
 
-def check_surv_probe(args):
-    """--surv-probe's refusals, all before any GPU work (the MIL probe's, and a survival table to train on)."""
+def check_bag_probe(args, key, metric_hint, resolve):
+    """The refusals --mil-probe and --surv-probe share, all before any GPU work and in one order.  ``key``: mil | surv, the
+    prefix of the probe's flags and of its gv_<key>_train; ``metric_hint``: what the --eval-metric refusal adds for this probe; ``resolve``:
+    the run's --eval-metric resolved with this probe on."""
+    flag, entry = f"--{key}-probe", f"gv_{key}_train"
+    opt = lambda name: getattr(args, f"{key}_{name}")
     if not args.dino:
-        raise SystemExit("--surv-probe scores the DINO teacher's frozen features: it needs --dino (a supervised run has validate())")
-    if args.surv_hidden % 16 or not 16 <= args.surv_hidden <= 256:
-        raise SystemExit(f"--surv-hidden {args.surv_hidden}: a multiple of 16 in 16 .. 256 (gv_surv_train)")
-    if not (math.isfinite(args.surv_lr) and args.surv_lr > 0):
-        raise SystemExit(f"--surv-lr {args.surv_lr}: a positive finite rate")
-    if not args.surv_wd >= 0:
-        raise SystemExit(f"--surv-wd {args.surv_wd}: weight decay must be >= 0")
-    if args.surv_epochs < 1:
-        raise SystemExit(f"--surv-epochs {args.surv_epochs}: at least one pass over the bank's slides")
-    if not 1 <= args.surv_batch <= 64:
-        raise SystemExit(f"--surv-batch {args.surv_batch}: 1 .. 64 slides per step (gv_surv_train)")
+        raise SystemExit(f"{flag} scores the DINO teacher's frozen features: it needs --dino (a supervised run has validate())")
+    if opt("hidden") % 16 or not 16 <= opt("hidden") <= 256:
+        raise SystemExit(f"--{key}-hidden {opt('hidden')}: a multiple of 16 in 16 .. 256 ({entry})")
+    if not (math.isfinite(opt("lr")) and opt("lr") > 0):
+        raise SystemExit(f"--{key}-lr {opt('lr')}: a positive finite rate")
+    if not opt("wd") >= 0:
+        raise SystemExit(f"--{key}-wd {opt('wd')}: weight decay must be >= 0")
+    if opt("epochs") < 1:
+        raise SystemExit(f"--{key}-epochs {opt('epochs')}: at least one pass over the bank's slides")
+    if not 1 <= opt("batch") <= 64:
+        raise SystemExit(f"--{key}-batch {opt('batch')}: 1 .. 64 slides per step ({entry})")
     from gipvit.archs import ARCHS, resolve_arch       # plain tables: nothing is loaded for them
-    spec = ARCHS[resolve_arch(args.model)]
-    if not 1 <= args.surv_layers <= spec["depth"]:
-        raise SystemExit(f"--surv-layers {args.surv_layers}: the last 1 .. {spec['depth']} blocks of {args.model}")
-    if args.surv_layers * spec["embed_dim"] > 4096:
-        raise SystemExit(f"--surv-layers {args.surv_layers}: {args.surv_layers * spec['embed_dim']} features per tile at width {spec['embed_dim']}, "
-                         "gv_surv_train stops at 4096")
-    if args.surv_rate < 0:
-        raise SystemExit(f"--surv-rate {args.surv_rate}: 0 = after the last epoch only, N >= 1 = every N epochs and the last")
+    spec, layers = ARCHS[resolve_arch(args.model)], opt("layers")
+    if not 1 <= layers <= spec["depth"]:
+        raise SystemExit(f"--{key}-layers {layers}: the last 1 .. {spec['depth']} blocks of {args.model}")
+    if layers * spec["embed_dim"] > 4096:
+        raise SystemExit(f"--{key}-layers {layers}: {layers * spec['embed_dim']} features per tile at width {spec['embed_dim']}, "
+                         f"{entry} stops at 4096")
+    if opt("rate") < 0:
+        raise SystemExit(f"--{key}-rate {opt('rate')}: 0 = after the last epoch only, N >= 1 = every N epochs and the last")
     if args.test_fold in (-1, "-1"):
-        raise SystemExit("--test_fold -1 with --surv-probe: no evaluation fold is left to score the slides of")
+        raise SystemExit(f"--test_fold -1 with {flag}: no evaluation fold is left to score the slides of")
     if args.tile_size < args.global_crop_size:
-        raise SystemExit(f"--surv-probe: the teacher sees {args.global_crop_size}-px images, the centred window of a {args.tile_size}-px "
+        raise SystemExit(f"{flag}: the teacher sees {args.global_crop_size}-px images, the centred window of a {args.tile_size}-px "
                          "tile (--tile-size) cannot be smaller than that")
     if args.num_tiles > 4096:
-        raise SystemExit(f"--num_tiles {args.num_tiles} with --surv-probe: a slide's bag holds at most 4096 tiles (gv_surv_train)")
+        raise SystemExit(f"--num_tiles {args.num_tiles} with {flag}: a slide's bag holds at most 4096 tiles ({entry})")
     if args.knn_bank_tiles is not None and args.knn_bank_tiles > 4096:
-        raise SystemExit(f"--knn-bank-tiles {args.knn_bank_tiles} with --surv-probe: a slide's bag holds at most 4096 tiles (gv_surv_train)")
+        raise SystemExit(f"--knn-bank-tiles {args.knn_bank_tiles} with {flag}: a slide's bag holds at most 4096 tiles ({entry})")
     names = monitor_metric_names(args)
-    if resolve_eval_metric(args.eval_metric, bool(args.knn_monitor), bool(args.linear_probe), bool(args.mil_probe), surv=True) not in names:
+    if resolve() not in names:
         raise SystemExit(f"--eval-metric {args.eval_metric}: the monitors of this run report {names} (a bare name is the k-NN monitor's when that "
-                         "is on, else the linear probe's, else the MIL probe's; the survival probe's are surv_cindex and surv_loss)")
+                         f"is on, else the linear probe's, else the MIL probe's{metric_hint})")
+
+
+def check_surv_probe(args):
+    """--surv-probe's refusals, all before any GPU work (the MIL probe's, and a survival table to train on)."""
+    check_bag_probe(args, "surv", "; the survival probe's are surv_cindex and surv_loss",
+                    lambda: resolve_eval_metric(args.eval_metric, bool(args.knn_monitor), bool(args.linear_probe), bool(args.mil_probe), surv=True))
     if args.dataset not in ("", "synthetic") and (args.dataset.startswith("tiles:") or args.data_dir) and not args.extract_features:
         from gipvit import data as D                   # (numpy and torch only: no library is loaded)
         root = args.dataset[6:] if args.dataset.startswith("tiles:") else args.data_dir
